@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- conv3p forward+backward throughput of the pointcnn2_acsd conv3p stack on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+  higher_is_better, dtype, ms_per_step = wall time of the K steps / K, ...).  Everything else below -- the
+  instrumented per-kernel pass behind `roofline`, the CPU baselines, parity, the other configurations and
+  boundaries -- runs only with --full.
+  --dump-outputs DIR: after the timed steps, what the last of them handed back to its caller, as DIR/<name>.npy
+  (cfg2: y0..y3 = the four layers' activations (B, N, 9), dX (B, N, 3), dW = the fused weight gradient; cfg5: y,
+  dX, dW), float32, 64 MiB at most (a larger array is replaced by a fixed, seeded sample of its rows).  The inputs
+  are seeded, so two builds run with the same arguments can be compared output for output.
   N > 1 with WORLD_SIZE unset (plain `python bench.py --gpus 8`): bench.py re-executes itself through
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU;
   launched by torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.
@@ -13,7 +21,7 @@ layers of the classification model (3->9 s1, 9->9 s2, 9->9 s3, 9->9 s4, SELU in 
 (BASELINE.json configs[1]; weak scaling, configs[2] = 8 x 32), followed for N>1 by the one fused RCCL all-reduce of
 the weight gradients.  Inputs are resident in HBM before the timed region.  metric = B*N*n_gpus / t_step.
 
-Extra objects on the JSON line (rank 0; everything except `roofline` only at N=1):
+Extra objects on the JSON line with --full (rank 0; everything except `roofline` only at N=1):
   roofline           dominant kernel of the headline step (by HIP-event time, measured live in a second,
                      instrumented run of the same K steps on the same streams): algorithmic bytes per launch /
                      average launch duration vs 8 TB/s.  avg_launch_us is measured WITH the side-stream overlap the
@@ -67,6 +75,7 @@ from pointwise_amd import _lib, conv3p_op as op, distributed, stack, synth  # no
 B_PER_GPU = 32
 N_POINTS = 2048
 C_IN = 3
+NBATCH = 4          # distinct cfg2 batches resident in HBM, cycled by the steps
 HBM_PEAK_GBS = 8000.0
 MFMA_F32_PEAK_TFLOPS = 157.3
 
@@ -121,6 +130,25 @@ def timed(dev, step, steps, warmup):
         step()
     torch.cuda.synchronize(dev)
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} as <path>/<name>.npy.  An array larger than its share of DUMP_LIMIT_BYTES is
+    replaced by the same seeded sample of its rows (leading dimensions flattened) in every run."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, share // rows[0].nbytes)
+            a = rows[np.sort(np.random.RandomState(0).choice(rows.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 SIMDS = 1024
@@ -632,6 +660,13 @@ def head_report(lib, dev, steps=20, warmup=3):
     return out
 
 
+def cfg2_inputs(rank):
+    """The NBATCH seeded cfg2 point batches of this rank (features == points) and the 4 layers' upstream gradients."""
+    Ps = [synth.modelnet_like(B_PER_GPU, N_POINTS, seed=1234 + 2 + 1000 * rank + 17 * i) for i in range(NBATCH)]
+    ups = [synth.upstream_grad(B_PER_GPU, N_POINTS, stack.HIDDEN, 77 + li + 1000 * rank) for li in range(4)]
+    return Ps, ups
+
+
 # ------------------------------------------------------------------------------------------- launch plumbing
 def respawn_under_torchrun(args):
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE: run the same command one rank per GPU."""
@@ -650,8 +685,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip other_configs / stateless / isolated passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also the instrumented per-kernel pass (roofline), CPU baselines, parity, other configs and "
+                         "boundaries; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip other_configs / stateless / isolated passes")
     ap.add_argument("--serial", action="store_true",
                     help="developer: no side stream at all (clean per-kernel durations under rocprofv3)")
     ap.add_argument("--workload", choices=("cfg2", "cfg5"), default="cfg2",
@@ -669,6 +709,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (the product path has no CPU fallback)")
     if torch.cuda.device_count() < args.gpus:
@@ -688,8 +730,7 @@ def main():
     # Every step gets a DIFFERENT batch (NBATCH distinct batches resident in HBM, cycled), as in training:
     # the neighbour cache therefore rebuilds its geometry every step (1 sort + 4 searches per step) and only
     # saves the repeats INSIDE a step (8 op calls share one `points`).  Nothing is carried across steps.
-    NBATCH = 4
-    Ps = [synth.modelnet_like(B_PER_GPU, N_POINTS, seed=1234 + 2 + 1000 * rank + 17 * i) for i in range(NBATCH)]
+    Ps, ups_np = cfg2_inputs(rank)
     if os.environ.get("CONV3P_BENCH_PRESORT"):   # developer experiment: clouds arrive in Morton order (gather locality)
         def morton(P):
             q = np.clip(((P - P.min(axis=1, keepdims=True)) / 0.05).astype(np.int64), 0, 1023)
@@ -700,7 +741,6 @@ def main():
             return np.argsort(code, axis=1, kind="stable")
         Ps = [np.take_along_axis(P, morton(P)[..., None], axis=1) for P in Ps]
     P = Ps[0]
-    ups_np = [synth.upstream_grad(B_PER_GPU, N_POINTS, stack.HIDDEN, 77 + li + 1000 * rank) for li in range(4)]
     tPs = [torch.from_numpy(p).to(dev) for p in Ps]
     tXs = [t.clone() for t in tPs]
     tP, tX = tPs[0], tXs[0]
@@ -728,7 +768,7 @@ def main():
         def step():
             i = counter[0] % NBATCH
             counter[0] += 1
-            stk.forward(tPs[i], tXs[i])
+            acts = stk.forward(tPs[i], tXs[i])
             if pre:
                 # the next batch's geometry (1 sort + 4 searches) goes to the side stream now and runs under this
                 # batch's backward, as a data-loader-fed training loop would do.  Every step still performs exactly
@@ -737,7 +777,7 @@ def main():
             red.wait_previous()                 # the buffer the backward writes: the last all-reduce has consumed it
             dx, fused = stk.backward(gcat)
             red.launch(fused)                   # N > 1: on the communication stream, under the next step's forward
-            return dx, fused
+            return acts, dx, fused
         return step
 
     step = make_step(st, prefetch)
@@ -754,7 +794,7 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     t_enqueued = time.perf_counter() - t0       # host side done (diagnostic: is the step host- or GPU-bound?)
     red.finish()
     torch.cuda.synchronize(dev)
@@ -762,16 +802,22 @@ def main():
     distributed.barrier()
     elapsed = distributed.max_over_ranks(time.perf_counter() - t0, dev)
     spread = rank_spread(local_elapsed, args.steps, dev) if world > 1 else None
+    if args.dump_outputs and rank == 0:
+        acts, dx, fused = last
+        dump_outputs(args.dump_outputs, dict([("y%d" % li, a) for li, a in enumerate(acts)] + [("dX", dx), ("dW", fused)]))
+    del last
 
-    # ---- per-kernel HIP-event timing of the same K steps (instrumented, not the timed region) ----
-    red.timing = True
-    kinds = profile_steps(lib, dev, step, args.steps)
-    red.finish()
-    torch.cuda.synchronize(dev)
-    red.timing = False
-    allreduce_ms = red.ms_per_step(args.steps)
-    allreduce_exposed_ms = red.exposed_ms_per_step(args.steps)
-    extra = world == 1 and not args.no_extra
+    kinds = allreduce_ms = allreduce_exposed_ms = None
+    if args.full:
+        # ---- per-kernel HIP-event timing of the same K steps (instrumented, not the timed region) ----
+        red.timing = True
+        kinds = profile_steps(lib, dev, step, args.steps)
+        red.finish()
+        torch.cuda.synchronize(dev)
+        red.timing = False
+        allreduce_ms = red.ms_per_step(args.steps)
+        allreduce_exposed_ms = red.exposed_ms_per_step(args.steps)
+    extra = args.full and world == 1 and not args.no_extra
     kinds_iso = None
     if extra and prefetch:
         # the same steps with no side stream at all: kernels run alone, one after the other
@@ -907,7 +953,7 @@ def main():
             out.update(op_boundary_native(Ps))
             out["other_configs"] = {"cfg4": cfg4_report(lib, dev, parity=not args.no_cpu), "cfg5_shard": cfg5_report(lib, dev, parity=not args.no_cpu),
                                     "classification_head": head_report(lib, dev)}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             base, cfg1, ref = cpu_baseline(P, P.copy(), st, ups_np)
             out["cpu_baseline"] = base
             out["cpu_baseline_cfg1"] = cfg1
@@ -948,12 +994,13 @@ def main_cfg5(args, lib, dev, rank, world):
         P, Pn = Ps[ctr[0] % NB_CFG5], Ps[(ctr[0] + 1) % NB_CFG5]
         ctr[0] += 1
         cache, hint = geo.cache_for(P)
-        op.conv3p(P, X, W, (1, 1, 1), stack.VOXEL, cache=cache, points_unchanged=hint)
+        y = op.conv3p(P, X, W, (1, 1, 1), stack.VOXEL, cache=cache, points_unchanged=hint)
         geo.prefetch(Pn)
         red.wait_previous()
-        op.conv3p_grad(dY, P, X, W, (1, 1, 1), stack.VOXEL, grad_filter_out=dW, cache=cache, points_unchanged=True)
+        dx, _ = op.conv3p_grad(dY, P, X, W, (1, 1, 1), stack.VOXEL, grad_filter_out=dW, cache=cache, points_unchanged=True)
         red.launch(dW)
         geo.step_done()
+        return y, dx
 
     steps, warmup = args.steps, args.warmup
     for _ in range(warmup):
@@ -963,19 +1010,24 @@ def main_cfg5(args, lib, dev, rank, world):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     red.finish()
     torch.cuda.synchronize(dev)
     local_elapsed = time.perf_counter() - t0
     distributed.barrier()
     elapsed = distributed.max_over_ranks(time.perf_counter() - t0, dev)
     spread = rank_spread(local_elapsed, steps, dev) if world > 1 else None
-    red.timing = True
-    kinds = profile_steps(lib, dev, step, min(steps, 5))
-    red.finish()
-    torch.cuda.synchronize(dev)
-    allreduce_ms = red.ms_per_step(min(steps, 5))
-    allreduce_exposed_ms = red.exposed_ms_per_step(min(steps, 5))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": last[0], "dX": last[1], "dW": dW})
+    del last
+    kinds = allreduce_ms = allreduce_exposed_ms = None
+    if args.full:
+        red.timing = True
+        kinds = profile_steps(lib, dev, step, min(steps, 5))
+        red.finish()
+        torch.cuda.synchronize(dev)
+        allreduce_ms = red.ms_per_step(min(steps, 5))
+        allreduce_exposed_ms = red.exposed_ms_per_step(min(steps, 5))
     if rank == 0:
         dt = elapsed / steps
         useful = 3 * 2 * 27 * ci * co * B * N
@@ -992,8 +1044,9 @@ def main_cfg5(args, lib, dev, rank, world):
                           "global_batch": B * world, "points_per_cloud": N, "parallelism": "dp%d" % world},
                "roofline": {"bound": "mfma", "scope": "whole step, per GPU", "achieved": round(achieved, 2),
                             "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),
-                            "flops_per_point": 3 * 2 * 27 * ci * co,
-                            "kernel_ms_per_step": {k: round(v[1] / min(steps, 5), 4) for k, v in kinds.items()}}}
+                            "flops_per_point": 3 * 2 * 27 * ci * co}}
+        if kinds is not None:
+            out["roofline"]["kernel_ms_per_step"] = {k: round(v[1] / min(steps, 5), 4) for k, v in kinds.items()}
         if world > 1:
             out["rccl_world"] = rccl_world
             out["allreduce_ms_per_step"] = None if allreduce_ms is None else round(allreduce_ms, 4)

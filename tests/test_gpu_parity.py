@@ -1346,13 +1346,13 @@ def test_random_shapes_against_oracle(dev, case):
 
 
 def test_bench_prints_one_contract_json_line(dev):
-    """bench.py's stdout is ONE JSON line with the driver's fields plus the roofline / cpu_baseline objects."""
+    """bench.py --full: stdout is ONE JSON line with the driver's fields plus the roofline / cpu_baseline objects."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
-                         capture_output=True, text=True, timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -1368,6 +1368,53 @@ def test_bench_prints_one_contract_json_line(dev):
     assert r["bound"] in ("hbm", "mfma") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-4 and r["unit"] in ("GB/s", "TFLOP/s")
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and c["cores"] >= 1 and c["sample"]
+
+
+def test_bench_plain_run_dumps_its_last_step(dev, tmp_path):
+    """bench.py without --full: the contract line and nothing of the --full legs; --dump-outputs writes what the
+    last timed step handed back (batch (warmup + steps - 1) % NBATCH), which one tuned stack step on that batch
+    reproduces."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 2
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                          "--warmup", str(warmup), "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "Mpoints/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+    assert d["roofline"] is None
+    for k in ("cpu_baseline", "parity", "other_configs", "stateless_ms_per_step", "op_boundary_native_ms_per_step"):
+        assert k not in d, k
+
+    import bench
+    names = ["y0", "y1", "y2", "y3", "dX", "dW"]
+    assert sorted(os.listdir(str(tmp_path))) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(os.path.join(str(tmp_path), n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES
+    Ps, ups = bench.cfg2_inputs(0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    tp = t(Ps[(warmup + steps - 1) % bench.NBATCH])
+    st = stack.Conv3pStack(3, None, device=dev, seed=1234)
+    st.tune(tp)
+    acts = st.forward(tp, tp.clone())
+    dx, fused = st.backward(torch.cat([t(u) for u in ups], dim=2).contiguous())
+    for li, a in enumerate(acts):
+        assert rel_err(got["y%d" % li], a.cpu().numpy()) <= 1e-5
+    assert rel_err(got["dX"], dx.cpu().numpy()) <= 2e-5
+    ref = fused.cpu().numpy()
+    o = 0
+    for f in st.filters:
+        n = f.numel()
+        assert rel_err(got["dW"][o:o + n], ref[o:o + n]) <= 2e-5
+        o += n
 
 
 @pytest.mark.parametrize("ci,co,kind,N", [(9, 9, "modelnet", 600), (3, 9, "room", 300), (36, 13, "room", 200), (9, 3, "lattice", 256)])
