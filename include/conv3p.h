@@ -168,6 +168,18 @@ typedef struct conv3p_cache_config {
 #define CONV3P_CACHE_FUSED_FORWARD 16
 #define CONV3P_CACHE_FUSED_BACKWARD 32
 #define CONV3P_CACHE_FUSED_STACK (CONV3P_CACHE_FUSED_FORWARD | CONV3P_CACHE_FUSED_BACKWARD)
+/* OPT-IN bf16 precision of the filter contractions of the matrix-core path (fp32 layers with more than 16 channels on a
+ * side that have no register-path kernel, including the channel blocks of layers wider than 256) -- torch's
+ * set_float32_matmul_precision("medium"): every operand of those contractions (the normalised neighbour sums M_f / G_f',
+ * the filter, the X and G rows of the grad_filter product) is rounded once to bf16 (round to nearest even) for
+ * v_mfma_f32_32x32x16_bf16, with fp32 accumulation: ~2e-3 relative (max error over max |result|) instead of ~1e-6.
+ * The neighbour sums themselves, the grad_filter reduction, the search and the tiles the path hands to the exact generic
+ * kernel (non-finite values, pair-buffer overflow) stay fp32.  Without the bit: exact fp32 products, bit for bit the
+ * stateless entry points.  Honoured by the *_cached_* forward / backward calls (and conv3p_layer_*) that reach the
+ * matrix-core path; ignored, bit for bit, everywhere else: the register-path shapes, fp64, the stateless entry points
+ * and the stack entry points.  conv3p_cache_bytes does not depend on it.  (cfg5 shard 128 -> 256, forward + backward:
+ * 0.61 x the fp32 time) */
+#define CONV3P_CACHE_MATMUL_BF16 64
 
 size_t conv3p_cache_bytes(int elem_bytes, int B, int N, const conv3p_cache_config *cfg);
 /* Drop the host-side bookkeeping of a cache buffer (call before freeing it). */

@@ -26,6 +26,7 @@ CACHE_PREPARE_DEEP_ORDERS = 4     # conv3p_cache_prepare_*: also the matrix-core
 CACHE_FUSED_FORWARD = 16          # conv3p_stack_*: hidden layers of the forward / backward pass as ONE launch (opt-in, see
 CACHE_FUSED_BACKWARD = 32         # include/conv3p.h)
 CACHE_FUSED_STACK = CACHE_FUSED_FORWARD | CACHE_FUSED_BACKWARD
+CACHE_MATMUL_BF16 = 64            # matrix-core path: filter contractions in bf16 (opt-in, see include/conv3p.h)
 ABI_VERSION = 5                # CONV3P_ABI_VERSION of include/conv3p.h
 STACK_MAX_LAYERS = 8
 

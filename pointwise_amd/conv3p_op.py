@@ -45,6 +45,9 @@ def _workspace(device, nbytes):
     return buf, stream
 
 
+_MATMUL_BITS = {"highest": 0, "medium": _lib.CACHE_MATMUL_BF16}
+
+
 class NeighborCache:
     """Caller-owned persistent device buffer for the *_cached entry points of include/conv3p.h.
 
@@ -52,8 +55,12 @@ class NeighborCache:
     is decided on the device by content hash, so reusing it with different clouds is always safe."""
 
     def __init__(self, B, N, dtype, device, slots=5, max_taps=27, pairs_per_point=0, max_cin=36, max_cout=41,
-                 sparse_neighbourhoods=None, fused_stack=False, trust_tensor_identity=False):
+                 sparse_neighbourhoods=None, fused_stack=False, trust_tensor_identity=False, matmul_precision="highest"):
         lib = _lib.load()
+        # precision of the matrix-core path's filter contractions, named after torch.set_float32_matmul_precision but
+        # independent of it: "highest" (exact fp32) or "medium" (bf16 operands, CONV3P_CACHE_MATMUL_BF16 of
+        # include/conv3p.h); may be changed between calls
+        self.matmul_precision = matmul_precision
         # trust_tensor_identity (opt-in; what integration/tf_conv3p_shim.cc does with TensorFlow's tensors): the cache keeps
         # a REFERENCE to the points tensor it validated last; a later op call whose `points` is that very storage, at the
         # same address, shape and torch version counter (every in-place write through torch bumps it, and a storage that
@@ -84,8 +91,19 @@ class NeighborCache:
                           if self.sparse_neighbourhoods else _lib.CACHE_DENSE_NEIGHBOURHOODS) | \
                          (_lib.CACHE_PREPARE_DEEP_ORDERS if deep_orders else 0) | \
                          (_lib.CACHE_FUSED_FORWARD if self.fused_stack in (True, "forward") else 0) | \
-                         (_lib.CACHE_FUSED_BACKWARD if self.fused_stack in (True, "backward") else 0)
+                         (_lib.CACHE_FUSED_BACKWARD if self.fused_stack in (True, "backward") else 0) | \
+                         _MATMUL_BITS[self.matmul_precision]
         return ctypes.addressof(self.cfg)
+
+    @property
+    def matmul_precision(self):
+        return self._matmul_precision
+
+    @matmul_precision.setter
+    def matmul_precision(self, mode):
+        if not isinstance(mode, str) or mode not in _MATMUL_BITS:
+            raise Conv3pInvalidArgument("matmul_precision must be one of %s, not %r" % (sorted(_MATMUL_BITS), mode))
+        self._matmul_precision = mode
 
     def _identity_hint(self, points):
         """True iff `points` is the tensor this cache validated last, unmodified (see trust_tensor_identity); otherwise it

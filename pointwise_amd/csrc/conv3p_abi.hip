@@ -37,12 +37,13 @@ inline size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
 // ----------------------------------------------------------------------------- profiling
 enum Kind { K_PREP = 0, K_SEARCH, K_FORWARD, K_BACKWARD, K_REDUCE, K_SELU, K_SELU_GRAD, K_MEMSET,
-            K_DEEP_GEMM, K_DEEP_DW, K_TRANSPOSE, K_DEEP_ORDER, K_FC_FWD, K_FC_DX, K_FC_DW, K_NKINDS };
+            K_DEEP_GEMM, K_DEEP_DW, K_TRANSPOSE, K_DEEP_ORDER, K_FC_FWD, K_FC_DX, K_FC_DW, K_DEEP_GEMM_BF16, K_DEEP_DW_BF16,
+            K_NKINDS };
 const char *const kKindName[K_NKINDS] = {"prep_kernel", "search_kernel", "forward_kernel",
                                          "backward_kernel", "reduce_partials_kernel", "selu_kernel",
                                          "selu_grad_kernel", "memset", "deep_gemm_kernel", "deep_dw_kernel",
                                          "transpose_filter_kernel", "deep_order_kernel", "fc_forward_kernel",
-                                         "fc_dx_kernel", "fc_dw_kernel"};
+                                         "fc_dx_kernel", "fc_dw_kernel", "deep_gemm_bf16_kernel", "deep_dw_bf16_kernel"};
 struct Prof {
     std::mutex mu;
     bool on = false;
@@ -403,6 +404,7 @@ template <typename T> struct Call {
     bool wide_scratch_ok = false;  // ... the blocked path of layers with more than 256 channels
     bool f64_scratch_ok = false;   // ... the blocked path of fp64 layers outside the register-path shapes
     bool order_ok[2] = {false, false};   // the deep path's forward / backward record order of this geometry is in the scratch
+    int prec = kPrecF32;           // filter contractions of the matrix-core path: kPrecBf16 = CONV3P_CACHE_MATMUL_BF16
     void *cache_key = nullptr;     // persistent cache the call runs in (host bookkeeping of the record orders)
     uint64_t gen = 0;
     bool evicted_hinted = false;   // slot re-assigned to a new stencil while prep is skipped: reset its allocators
@@ -1030,7 +1032,7 @@ int launch_deep_gemm(const Call<float> &c, const float *src, const float *Bm, fl
     if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
     if ((size_t)d.N * (size_t)kreal * 4 > 0xFFFFFFFFull) return CONV3P_ERR_UNSUPPORTED;   // (stage 1 addresses rows by 32-bit offsets)
     const BlockMap bm = make_blockmap(d);
-    Scope sc(K_DEEP_GEMM, c.s);
+    Scope sc(c.prec != kPrecF32 ? K_DEEP_GEMM_BF16 : K_DEEP_GEMM, c.s);
     auto go = [&](auto kern) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(grid_of(bm)), dim3(256), lds, c.s, c.L.pts, S.pairs, ds.dsegs, src, Bm, d.N, d.ntiles,
@@ -1038,13 +1040,18 @@ int launch_deep_gemm(const Call<float> &c, const float *src, const float *Bm, fl
                            ds.tap_split, ds.tap_cmask);
     };
     // rows shorter than 4 floats (only possible in the 32-column class) take the variant with scalar row loads
+    auto go_prec = [&](auto wide_c) {
+        constexpr bool kWide = decltype(wide_c)::value;
+        if (c.prec == kPrecBf16) go(deep_gemm_kernel<KD, ND, BWD, kWide, kPrecBf16>);
+        else go(deep_gemm_kernel<KD, ND, BWD, kWide, kPrecF32>);
+    };
     if constexpr (KD == 32) {
         if (kreal < 4) {
-            go(deep_gemm_kernel<KD, ND, BWD, false>);
+            go_prec(std::false_type{});
             return hip_ok();
         }
     }
-    go(deep_gemm_kernel<KD, ND, BWD, true>);
+    go_prec(std::true_type{});
     return hip_ok();
 }
 
@@ -1054,6 +1061,15 @@ int launch_pad_filter(const Call<float> &c, const float *filter, int kp, int np,
     Scope sc(K_TRANSPOSE, c.s);
     hipLaunchKernelGGL(pad_filter_kernel, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0,
                        c.s, filter, c.d.ntap, c.d.Cin, c.d.Cout, kp, np, transpose, wp);
+    return hip_ok();
+}
+// bf16: the B operand of the bf16 deep_gemm_kernel, in (half) the bytes of the fp32 copy
+int launch_pack_filter_bf16(const Call<float> &c, const float *filter, int kp, int np, int transpose, float *wp)
+{
+    const size_t n = (size_t)c.d.ntap * kp * np;
+    Scope sc(K_TRANSPOSE, c.s);
+    hipLaunchKernelGGL(pack_filter_bf16_kernel, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0,
+                       c.s, filter, c.d.ntap, c.d.Cin, c.d.Cout, kp, np, transpose, reinterpret_cast<__bf16 *>(wp));
     return hip_ok();
 }
 
@@ -1067,7 +1083,10 @@ int deep_forward(const Call<float> &c, const float *input, const float *filter, 
         if (c.order_ok[w]) note_deep_order(c, w);   // this path leaves both orders in place
     TRY(launch_deep_order<false>(c, ds));
     const float *Bm = filter;
-    if (d.Cin != CI || d.Cout != CO) {
+    if (c.prec != kPrecF32) {
+        TRY(launch_pack_filter_bf16(c, filter, CI, CO, 0, ds.wt));
+        Bm = ds.wt;
+    } else if (d.Cin != CI || d.Cout != CO) {
         TRY(launch_pad_filter(c, filter, CI, CO, 0, ds.wt));
         Bm = ds.wt;
     }
@@ -1086,19 +1105,24 @@ int deep_backward(const Call<float> &c, const float *grad_out, const float *inpu
     for (int w = 0; w < 2; ++w)
         if (c.order_ok[w]) note_deep_order(c, w);   // this path leaves both orders in place
     TRY(launch_deep_order<true>(c, ds));
-    TRY(launch_pad_filter(c, filter, CO, CI, 1, ds.wt));
+    if (c.prec != kPrecF32) TRY(launch_pack_filter_bf16(c, filter, CO, CI, 1, ds.wt));
+    else TRY(launch_pad_filter(c, filter, CO, CI, 1, ds.wt));
     // dX = sum_f' G_f' . W[f']^T  (K = Cout, N = Cin)
     TRY((launch_deep_gemm<CO, CI, true>(c, grad_out, ds.wt, grad_input, ds, d.Cout, d.Cin, ds.gbuf, input)));
     {
         constexpr int NH = deep_dw_parts<CI, CO>();
-        const size_t lds = (size_t)DEEP_DW_ROWS * (CI + 1) * 4 + (size_t)DEEP_DW_ROWS * (CO / NH + 1) * 4 + 256;
+        // (bf16: 2-byte images of X and G)
+        const size_t lds = c.prec == kPrecF32 ? (size_t)DEEP_DW_ROWS * (CI + 1) * 4 + (size_t)DEEP_DW_ROWS * (CO / NH + 1) * 4 + 256
+                                              : (size_t)DEEP_DW_ROWS * (CI + CO / NH) * 2 + 256;
         if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
-        Scope sc(K_DEEP_DW, c.s);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(deep_dw_kernel<CI, CO>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((deep_dw_kernel<CI, CO>), dim3(kDwItems + 64, NH), dim3(256), lds, c.s, c.L.pts, ds.tap_off,
-                           ds.gbuf, input, d.N, d.ntiles, d.ntap, ds.tile_flag, ds.items, ds.tap_total + 64, ds.partials,
-                           d.Cin, ds.tap_cmask);
+        Scope sc(c.prec != kPrecF32 ? K_DEEP_DW_BF16 : K_DEEP_DW, c.s);
+        auto go = [&](auto kern) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3(kDwItems + 64, NH), dim3(256), lds, c.s, c.L.pts, ds.tap_off, ds.gbuf, input, d.N,
+                               d.ntiles, d.ntap, ds.tile_flag, ds.items, ds.tap_total + 64, ds.partials, d.Cin, ds.tap_cmask);
+        };
+        if (c.prec == kPrecBf16) go(deep_dw_kernel<CI, CO, kPrecBf16>);
+        else go(deep_dw_kernel<CI, CO, kPrecF32>);
     }
     TRY(hip_ok());
     // flagged tiles: generic kernel adds into the zeroed rows / into its own grad_filter-shaped buffer
@@ -1419,6 +1443,8 @@ int begin_call(Call<T> &c, const Dims &d, const int32_t *stride, T voxel, size_t
     c.s = s;
     c.sparse_hint = wh.persistent && (wh.flags & CONV3P_CACHE_SPARSE_NEIGHBOURHOODS) != 0;
     c.dense_hint = wh.persistent && !c.sparse_hint && (wh.flags & CONV3P_CACHE_DENSE_NEIGHBOURHOODS) != 0;
+    // (read by deep_forward / deep_backward only: every other path ignores the bit)
+    c.prec = wh.persistent && (wh.flags & CONV3P_CACHE_MATMUL_BF16) != 0 ? kPrecBf16 : kPrecF32;
     const int ntap_max = wh.persistent ? wh.ntap_max : d.ntap;
     if (d.ntap > ntap_max) return CONV3P_ERR_WORKSPACE;
     if (wh.persistent && scratch > wh.scratch_cap) return CONV3P_ERR_WORKSPACE;

@@ -6,7 +6,7 @@
 //     dW[f']    = sum_pairs(f')  x[j,:]^T . (dY[ii,:] / count[ii,f'])
 // (same sums as tf_conv3p_atrous.cpp:480-494 and :682-698, re-associated; inside the fp32 tolerance).
 // The contractions with the filter run on v_mfma_f32_32x32x2_f32 (exact fp32, an fmaf chain per output,
-// 64 FLOP/clk/SIMD); the per-centre reductions M_f / G_f' are segmented sums on the vector ALUs:
+// 64 FLOP/clk/SIMD; opt-in: v_mfma_f32_32x32x16_bf16, kPrecBf16 below); the per-centre reductions M_f / G_f' are segmented sums on the vector ALUs:
 //   * a tile's records are put in tap-major order once (deep_order_kernel, a stable counting sort);
 //   * per tap, M_f is a branch-free segmented sum over the tap's run of records (deep_gemm_kernel stage 1);
 //   * M_f . W[f] follows from LDS, the W[f] operand streamed from L2 sixteen k-rows ahead;
@@ -419,12 +419,33 @@ __device__ __forceinline__ int qorig_early(const PointRec<float> *__restrict__ p
 // The populated taps are taken longest run first (taps running together have similar lengths).
 // LDS: M [TG][64][KDIM+4] | taps [64] | qorig [64] | scrap [256][4] | rowc [TG][64] bytes
 // ---------------------------------------------------------------------------------------------
-template <int KDIM, int NDIM, bool BWD, bool WIDE>   // WIDE: source rows have at least 4 floats (one 16-byte load per lane)
+// Precision of the filter contractions (stage 2 of deep_gemm, deep_dw): CONV3P_CACHE_MATMUL_BF16 of include/conv3p.h.
+// kPrecF32: v_mfma_f32_32x32x2_f32, exact fp32.  kPrecBf16: every operand rounded once to bf16 (round to nearest even),
+// v_mfma_f32_32x32x16_bf16, fp32 accumulation.  Stage 1 (the segmented fp32 sums M_f / G_f'), deep_reduce, the record
+// orders and the tiles handed to the exact generic kernel (non-finite values, pair-buffer overflow) are the same in both
+// modes: those tiles stay exact fp32.
+// Fragments of 32x32x16_bf16 (cdna_hip_programming.md section 3): lane l holds A[row l & 31][k = 8 (l >> 5) + j] and
+// B[k = 8 (l >> 5) + j][col l & 31], j = 0..7; C/D as 32x32x2_f32 (the epilogues and the badsum check are shared).
+constexpr int kPrecF32 = 0, kPrecBf16 = 1;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// a plain cast per value: v_cvt_pk_bf16_f32, round to nearest even
+__device__ __forceinline__ bf16x8 to_bf16x8(const float (&x)[8])
+{
+    bf16x8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (__bf16)x[j];
+    return r;
+}
+
+// WIDE: source rows have at least 4 floats (one 16-byte load per lane); PREC: kPrec* above
+template <int KDIM, int NDIM, bool BWD, bool WIDE, int PREC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_GEMM_WAVES))) void deep_gemm_kernel(const PointRec<float> *__restrict__ pts,
                                                         const PairEntry *__restrict__ pairs,
                                                         const uint2 *__restrict__ segs,
                                                         const float *__restrict__ src,
-                                                        const float *__restrict__ Bm, int N, int ntiles, int ntap,
+                                                        const float *__restrict__ Bm,   // kPrecF32: [F][KDIM][NDIM]; kPrecBf16: the image of pack_filter_bf16_kernel
+                                                        int N, int ntiles, int ntap,
                                                         const uint32_t *__restrict__ sched, int sched_cap,
                                                         float *__restrict__ out,
                                                         const uint2 *__restrict__ tap_meta,
@@ -719,7 +740,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_GEMM_W
         // k-steps each) over all of them: the B operand of group i+2 is requested before group i's MFMAs are issued
         // (three NAMED buffers, loop unrolled by three; loads unconditional from a clamped group index) -- with one
         // group of look-ahead and a register copy at the end, every group waited a full L2 latency for its operand.
-        if (o_on) {
+        if (PREC == kPrecF32 && o_on) {
             constexpr int GPT = KDIM / (2 * KG);             // k-groups per tap
             const int ng = ntp * GPT;
             const float *Bl = Bm + (lane >> 5) * NDIM + cb0 * 32 + (lane & 31);
@@ -754,6 +775,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_GEMM_W
             load_g(0, b0);
             load_g(1, b1);
             for (int gi = 0; gi < ((CONV3P_ABLATE & 65536) ? 0 : ng); gi += 3) {
+                load_g(gi + 2, b2);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_g(gi, b0);
+                if (gi + 1 >= ng) break;
+                load_g(gi + 3, b0);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_g(gi + 1, b1);
+                if (gi + 2 >= ng) break;
+                load_g(gi + 4, b1);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_g(gi + 2, b2);
+            }
+        }
+        if (PREC != kPrecF32 && o_on) {
+            // bf16: one 32x32x16 k-step per 16 k-rows, KB of them per B-operand group, the same three-buffer look-ahead.
+            // B: the packed image [F][KDIM/8][NDIM] of 8 bf16 (pack_filter_bf16_kernel) -- a lane's 8 k-values of a
+            // column are ONE 16-byte load; A: 8 consecutive k of the lane's row of M_f, two 16-byte LDS reads (rows are
+            // 16-byte aligned, LDA = KDIM + 4), rounded to bf16 here.
+            constexpr int KB = 2;
+            constexpr int GPT = KDIM / (16 * KB);             // k-groups per tap
+            const int ng = ntp * GPT;
+            const uint4 *Bh = reinterpret_cast<const uint4 *>(Bm) + (lane >> 5) * NDIM + cb0 * 32 + (lane & 31);
+            const float *Al = A + myrow * LDA + 8 * (lane >> 5);
+            auto load_g = [&](int gi, uint4 (&bv)[KB][CPW]) {
+                const int gc = gi < ng ? gi : ng - 1;
+                const uint4 *Bf = Bh + ((size_t)taps[t0 + gc / GPT] * (KDIM / 8) + (size_t)(gc % GPT) * (2 * KB)) * NDIM;
+#pragma unroll
+                for (int s2 = 0; s2 < KB; ++s2)
+#pragma unroll
+                    for (int j = 0; j < CPW; ++j) bv[s2][j] = Bf[(size_t)(2 * s2) * NDIM + j * (CSTEP * 32)];
+            };
+            auto mma_g = [&](int gi, const uint4 (&bv)[KB][CPW]) {
+                const float *arow = Al + (gi / GPT) * 64 * LDA + (gi % GPT) * (16 * KB);
+#pragma unroll
+                for (int s2 = 0; s2 < KB; ++s2) {
+                    bf16x8 a[RBW];
+#pragma unroll
+                    for (int i = 0; i < RBW; ++i) {
+                        const float4 x0 = *reinterpret_cast<const float4 *>(arow + i * 32 * LDA + 16 * s2);
+                        const float4 x1 = *reinterpret_cast<const float4 *>(arow + i * 32 * LDA + 16 * s2 + 4);
+                        a[i] = to_bf16x8({x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w});
+                    }
+#pragma unroll
+                    for (int i = 0; i < RBW; ++i)
+#pragma unroll
+                        for (int j = 0; j < CPW; ++j)
+                            acc[i * CPW + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], __builtin_bit_cast(bf16x8, bv[s2][j]),
+                                                                                      acc[i * CPW + j], 0, 0, 0);
+                }
+            };
+            uint4 b0[KB][CPW], b1[KB][CPW], b2[KB][CPW];
+            load_g(0, b0);
+            load_g(1, b1);
+            for (int gi = 0; gi < ng; gi += 3) {
                 load_g(gi + 2, b2);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_g(gi, b0);
@@ -985,7 +1060,7 @@ __global__ __launch_bounds__(256) void deep_reduce_kernel(const float *__restric
 // column block of accumulators (128 registers) plus the operands of four k-steps did not fit three waves per SIMD (35
 // spilled registers, 144 B of scratch per lane until round 5)
 template <int CIN, int COUT> constexpr int deep_dw_parts() { return CIN >= 256 && COUT >= 128 ? 4 : COUT >= 64 ? 2 : 1; }
-template <int CIN, int COUT>
+template <int CIN, int COUT, int PREC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_DW_WAVES))) void deep_dw_kernel(
     const PointRec<float> *__restrict__ pts, const uint32_t *__restrict__ tap_off, const float *__restrict__ gbuf,
     const float *__restrict__ input, int N, int ntiles, int ntap, const uint8_t *__restrict__ tile_flag,
@@ -1002,9 +1077,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_DW_WAV
     static_assert(CIN % 32 == 0 && CH % 32 == 0 && NB % WN == 0, "deep path: channel counts are 32 or multiples of 64");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int kRows = DEEP_DW_ROWS;                    // packed rows per pass
+    static_assert(PREC == kPrecF32 || kRows % 16 == 0, "bf16: whole 16-row k-steps per pass");
+    // fp32: X [kRows][LDX] | G [kRows][LDG] | qorig.  bf16: X image [kRows / 8][CIN] and G image [kRows / 8][CH] of 8 bf16
+    // (8 consecutive packed rows of one column in 16 bytes: a lane's fragment is ONE LDS read) | qorig
     float *X = reinterpret_cast<float *>(smem);            // [kRows][LDX]
     float *G = X + kRows * LDX;                            // [kRows][LDG]
-    int32_t *qorig = reinterpret_cast<int32_t *>(G + kRows * LDG);
+    uint4 *Xb = reinterpret_cast<uint4 *>(smem);
+    uint4 *Gb = Xb + (kRows / 8) * CIN;
+    int32_t *qorig = PREC == kPrecF32 ? reinterpret_cast<int32_t *>(G + kRows * LDG)
+                                      : reinterpret_cast<int32_t *>(Gb + (kRows / 8) * CH);
     if (blockIdx.x >= *nitems) return;
     const uint4 item = items[blockIdx.x];                  // {tap, first tile, end tile, partial slot}
     const int f = (int)item.x, c0 = (int)blockIdx.y * CH;
@@ -1028,20 +1109,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_DW_WAV
         if (toff[f] == toff[f + 1] || tile_flag[tile]) continue;   // uniform: nothing with this tap / generic kernel's tile
         const int b = (int)(tile / ntiles);
         // the tile's centres that have tap f: only their rows of G_f' were stored (packed, centre order) and only they
-        // enter the contraction; K is padded to a multiple of 8 with zero rows of G
+        // enter the contraction; K is padded to a multiple of 8 (bf16: 16) with zero rows of G
         const unsigned long long cm = tap_cmask[tile * (size_t)ntap + f];
-        const int nrow = __popcll(cm), npad = (nrow + 7) & ~7;
+        const int nrow = __popcll(cm), npad = PREC == kPrecF32 ? (nrow + 7) & ~7 : (nrow + 15) & ~15;
         __syncthreads();                                    // previous tile's X / G consumed (qorig too)
         if (wave == 0) {
             const int orig = pts[tile * kTile + lane].idx;
             if ((cm >> lane) & 1ull) qorig[__popcll(cm & ((1ull << lane) - 1ull))] = orig;   // packed row -> original index
         }
+        const float *gt = gbuf + (tile * (size_t)ntap + f) * 64 * COUT + c0;
         for (int r0 = 0; r0 < npad; r0 += kRows) {
-            const int cr = npad - r0 < kRows ? npad - r0 : kRows;   // rows of this pass (a multiple of 8)
+            const int cr = npad - r0 < kRows ? npad - r0 : kRows;   // rows of this pass (a multiple of 8; bf16: of 16)
             if (r0 > 0) __syncthreads();                    // previous pass consumed
+            if constexpr (PREC == kPrecF32) {
             // G rows r0 .. r0 + cr of the stored block half (16-byte loads, all of a thread's in flight together)
             {
-                const float *gt = gbuf + (tile * (size_t)ntap + f) * 64 * COUT + c0;
                 constexpr int GPT = (kRows * (CH / 4)) / 256;   // float4 per thread
                 float4 gv[GPT];
 #pragma unroll
@@ -1105,6 +1187,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP_DW_WAV
                                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][i], bv[t][j], acc[i][j], 0, 0, 0);
                 }
             }
+            } else {
+            // bf16.  A thread takes a unit of 8 consecutive packed rows x 4 consecutive columns: 8 row loads of 16 bytes
+            // (coalesced along the columns, never column-strided), transposed in registers into 4 columns of 8 rows,
+            // rounded and stored as one 16-byte value per column.
+            auto stage = [&](uint4 *dst, auto cols_c, auto load) {   // dst: image [kRows / 8][C]
+                constexpr int C = decltype(cols_c)::value;
+                constexpr int UPT = ((kRows / 8) * (C / 4) + 255) / 256;   // units per thread
+#pragma unroll
+                for (int u = 0; u < UPT; ++u) {
+                    const int e = (int)threadIdx.x + 256 * u;
+                    const int r8 = e / (C / 4), c4 = e % (C / 4);
+                    if (r8 * 8 >= cr) continue;
+                    float4 v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = load(r0 + r8 * 8 + j, 4 * c4);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        float x[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) x[j] = c == 0 ? v[j].x : c == 1 ? v[j].y : c == 2 ? v[j].z : v[j].w;
+                        dst[r8 * C + 4 * c4 + c] = __builtin_bit_cast(uint4, to_bf16x8(x));
+                    }
+                }
+            };
+            // G rows of the stored block half; rows past nrow are zero
+            stage(Gb, std::integral_constant<int, CH>{}, [&](int rr, int col) {
+                const float4 g = *reinterpret_cast<const float4 *>(gt + (size_t)(rr < nrow ? rr : 0) * COUT + col);
+                return rr < nrow ? g : make_float4(0.f, 0.f, 0.f, 0.f);
+            });
+            if (r0 == 0) __syncthreads();                   // qorig visible
+            stage(Xb, std::integral_constant<int, CIN>{}, [&](int rr, int col) {
+                const int orig = rr < nrow ? qorig[rr] : -1;
+                return orig >= 0 ? load_row4(input + ((size_t)b * N + orig) * cin, col, cin) : make_float4(0.f, 0.f, 0.f, 0.f);
+            });
+            __syncthreads();
+            if (w_on) {
+                // A[i = k][kk = row] = X[row][k], B[kk = row][j = c] = G[row][c]: cr / 16 k-steps; k-step s reads row
+                // group 2 s + half of the images
+                const uint4 *xa = Xb + half * CIN + wm * PM * 32 + (lane & 31);
+                const uint4 *gb = Gb + half * CH + wn * PN * 32 + (lane & 31);
+                for (int s = 0; s < cr / 16; ++s) {
+                    bf16x8 a[PM], bv[PN];
+#pragma unroll
+                    for (int i = 0; i < PM; ++i) a[i] = __builtin_bit_cast(bf16x8, xa[2 * s * CIN + i * 32]);
+#pragma unroll
+                    for (int j = 0; j < PN; ++j) bv[j] = __builtin_bit_cast(bf16x8, gb[2 * s * CH + j * 32]);
+#pragma unroll
+                    for (int i = 0; i < PM; ++i)
+#pragma unroll
+                        for (int j = 0; j < PN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], bv[j], acc[i][j], 0, 0, 0);
+                }
+            }
+            }
         }
     }
     // partial slot of this item: [k][c]
@@ -1136,6 +1271,22 @@ __global__ __launch_bounds__(256) void pad_filter_kernel(const float *__restrict
         if (!transpose) { if (k < cin && c < cout) v = w[(f * cin + k) * cout + c]; }
         else if (k < cout && c < cin) v = w[(f * cin + c) * cout + k];
         wp[e] = v;
+    }
+}
+
+// the same filter as the B operand of the bf16 deep_gemm_kernel: image [F][kp / 8][np][8] of bf16(value) -- k-rows in
+// groups of 8, a column's 8 values of a group in 16 bytes (half the bytes of the fp32 copy pad_filter_kernel writes)
+__global__ __launch_bounds__(256) void pack_filter_bf16_kernel(const float *__restrict__ w, int ntap, int cin, int cout,
+                                                               int kp, int np, int transpose, __bf16 *__restrict__ wp)
+{
+    const size_t n = (size_t)ntap * kp * np;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t f = e / ((size_t)kp * np), r = e % ((size_t)kp * np);
+        const int k8 = (int)(r / ((size_t)np * 8)), c = (int)(r % ((size_t)np * 8)) / 8, k = 8 * k8 + (int)(r % 8);
+        float v = 0.0f;
+        if (!transpose) { if (k < cin && c < cout) v = w[(f * cin + k) * cout + c]; }
+        else if (k < cout && c < cin) v = w[(f * cin + c) * cout + k];
+        wp[e] = (__bf16)v;
     }
 }
 
