@@ -105,17 +105,25 @@ class NeighborCache:
             raise Conv3pInvalidArgument("matmul_precision must be one of %s, not %r" % (sorted(_MATMUL_BITS), mode))
         self._matmul_precision = mode
 
+    @staticmethod
+    def _identity_key(points):
+        return (points.data_ptr(), points.untyped_storage().data_ptr(), int(points._version), tuple(points.shape), points.dtype)
+
     def _identity_hint(self, points):
-        """True iff `points` is the tensor this cache validated last, unmodified (see trust_tensor_identity); otherwise it
-        becomes the held one -- to be called only by an op call that then validates it on the device."""
+        """True iff `points` is the tensor this cache validated last, unmodified (see trust_tensor_identity).  The held
+        tensor is dropped here: the op call about to run records `points` through _validated() only once it has
+        returned OK (a call that fails may leave the cache holding neither its points nor the previous ones)."""
         if not self.trust_tensor_identity:
             return False
-        key = (points.data_ptr(), points.untyped_storage().data_ptr(), int(points._version), tuple(points.shape), points.dtype)
+        key = self._identity_key(points)
         held = self._held
-        if held is not None and held[1] == key and int(held[0]._version) == key[2]:
-            return True
-        self._held = (points, key)
-        return False
+        self._held = None
+        return held is not None and held[1] == key and int(held[0]._version) == key[2]
+
+    def _validated(self, points):
+        """An op call on `points` has returned OK: the cache now holds their geometry."""
+        if self.trust_tensor_identity:
+            self._held = (points, self._identity_key(points))
 
     def forget_points(self):
         self._held = None
@@ -221,6 +229,7 @@ def conv3p(points, input, filter, stride, voxel_size, cache=None, points_unchang
                   filter.data_ptr(), ctypes.cast(s3, ctypes.c_void_p), creal(vox), B, N, Cin, Cout, fz, fy, fx,
                   out.data_ptr(), cache.buf.data_ptr(), cache.nbytes,
                   cache.cfg_ptr(points_unchanged or cache._identity_hint(points)), stream.cuda_stream)
+            cache._validated(points)
         else:
             if _fused_selu:
                 raise Conv3pInvalidArgument("conv3p_layer needs a NeighborCache that fits these clouds")
@@ -274,11 +283,13 @@ def conv3p_grad(grad_from_next, points, input, filter, stride, voxel_size, grad_
                       creal(vox), B, N, Cin, Cout, fz, fy, fx, add.data_ptr() if add is not None else None,
                       dx.data_ptr(), dw.data_ptr(), cache.buf.data_ptr(), cache.nbytes,
                       cache.cfg_ptr(points_unchanged or cache._identity_hint(points)), stream.cuda_stream)
+                cache._validated(points)
             else:
                 _call(getattr(lib, "conv3p_backward_cached_" + sfx), grad_from_next.data_ptr(), points.data_ptr(),
                       input.data_ptr(), filter.data_ptr(), ctypes.cast(s3, ctypes.c_void_p), creal(vox), B, N, Cin,
                       Cout, fz, fy, fx, dx.data_ptr(), dw.data_ptr(), cache.buf.data_ptr(), cache.nbytes,
                       cache.cfg_ptr(points_unchanged or cache._identity_hint(points)), stream.cuda_stream)
+                cache._validated(points)
         else:
             if _fused_selu:
                 raise Conv3pInvalidArgument("conv3p_layer_grad needs a NeighborCache that fits these clouds")
@@ -323,6 +334,7 @@ def cache_prepare(points, filter_zyx, stride, voxel_size, cache, points_unchange
     if not cache.fits(B, N, points.dtype, dev, fz * fy * fx, 0, 0):
         raise Conv3pInvalidArgument("neighbour cache does not fit these clouds")
     points = points.contiguous()
+    cache.forget_points()   # the cache is about to hold these points' geometry, whatever the op calls validated last
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
         _call(getattr(lib, "conv3p_cache_prepare_" + sfx), points.data_ptr(), ctypes.cast(s3, ctypes.c_void_p),
@@ -348,6 +360,7 @@ def cache_prepare_multi(points, filter_zyx, strides, voxel_size, cache, points_u
     if not cache.fits(B, N, points.dtype, dev, fz * fy * fx, 0, 0):
         raise Conv3pInvalidArgument("neighbour cache does not fit these clouds")
     points = points.contiguous()
+    cache.forget_points()   # (as in cache_prepare)
     with torch.cuda.device(dev):
         st_ = stream if stream is not None else torch.cuda.current_stream(dev)
         _call(getattr(lib, "conv3p_cache_prepare_multi_" + sfx), points.data_ptr(), ctypes.cast(arr, ctypes.c_void_p),

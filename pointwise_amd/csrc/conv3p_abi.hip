@@ -38,12 +38,14 @@ inline size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 // ----------------------------------------------------------------------------- profiling
 enum Kind { K_PREP = 0, K_SEARCH, K_FORWARD, K_BACKWARD, K_REDUCE, K_SELU, K_SELU_GRAD, K_MEMSET,
             K_DEEP_GEMM, K_DEEP_DW, K_TRANSPOSE, K_DEEP_ORDER, K_FC_FWD, K_FC_DX, K_FC_DW, K_DEEP_GEMM_BF16, K_DEEP_DW_BF16,
+            K_GENERIC_FWD, K_GENERIC_BWD,   // the thread-per-pair kernels (global float atomics) over a whole call
             K_NKINDS };
 const char *const kKindName[K_NKINDS] = {"prep_kernel", "search_kernel", "forward_kernel",
                                          "backward_kernel", "reduce_partials_kernel", "selu_kernel",
                                          "selu_grad_kernel", "memset", "deep_gemm_kernel", "deep_dw_kernel",
                                          "transpose_filter_kernel", "deep_order_kernel", "fc_forward_kernel",
-                                         "fc_dx_kernel", "fc_dw_kernel", "deep_gemm_bf16_kernel", "deep_dw_bf16_kernel"};
+                                         "fc_dx_kernel", "fc_dw_kernel", "deep_gemm_bf16_kernel", "deep_dw_bf16_kernel",
+                                         "generic_forward_kernel", "generic_backward_kernel"};
 struct Prof {
     std::mutex mu;
     bool on = false;
@@ -337,6 +339,14 @@ inline size_t f64_blocked_bytes(const Dims &d)
     return up((size_t)grid_of(make_blockmap(d)) * nwb * 8) + 3 * up(rows * kF64Row * 8) + 2 * up(nwb * 8);
 }
 
+// Register-path shapes whose register kernels cannot take the filter (LDS), judged on the undilated stencil of the
+// call's extents -- what the workspace query (no stride argument) and the call itself both know.  Their calls run on the
+// deterministic paths of the other shapes, whose scratch is then provisioned: fp32 backward on the matrix-core kernels
+// (filters of up to 64 taps), fp64 backward and forward as channel blocks.  (A dilation large enough to tip a filter past
+// the fit on its own would find that scratch only in a cache: a stateless call takes the generic kernels.)
+bool register_backward_misfit(const Dims &d, int elem);
+bool f64_register_forward_misfit(const Dims &d);
+
 // ppp: pair slots per point of the buffer the call runs in (a cache may be configured with fewer than the default)
 size_t backward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPerPoint)
 {
@@ -346,6 +356,10 @@ size_t backward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPe
     if (f64_blocked_shape(elem, d.Cin, d.Cout)) deep = f64_blocked_bytes(d);
     if (!small_shape(elem, d.Cin, d.Cout) && deep_shape(elem, d.Cin, d.Cout))
         deep = deep_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
+    if (small_shape(elem, d.Cin, d.Cout) && register_backward_misfit(d, elem)) {
+        if (elem == 8) deep = f64_blocked_bytes(d);
+        else if (d.ntap <= 64 && deep_shape(elem, d.Cin, d.Cout)) deep = deep_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
+    }
     // register path: one partial per workgroup; generic path (also the fallback of the other two): generic_slots
     const size_t slots = small_shape(elem, d.Cin, d.Cout) ? (size_t)grid_of(make_blockmap(d)) : (size_t)generic_slots(d, elem);
     const size_t plain = nw * slots * (size_t)elem;
@@ -373,6 +387,7 @@ size_t forward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPer
         return deep_forward_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
     if (wide_shape(elem, d.Cin, d.Cout)) return mandatory_only ? 0 : wide_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp, true);
     if (f64_blocked_shape(elem, d.Cin, d.Cout)) return mandatory_only ? 0 : f64_blocked_bytes(d);
+    if (elem == 8 && small_shape(elem, d.Cin, d.Cout) && f64_register_forward_misfit(d)) return mandatory_only ? 0 : f64_blocked_bytes(d);
     return 0;
 }
 
@@ -647,7 +662,7 @@ template <typename T> int run_search(const Call<T> &c, int32_t *count, bool with
         return CONV3P_OK;
     }
     const size_t lds = search_lds_bytes(st, c.L.gtiles);
-    if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // very large filters (> ~340 taps): populations alone exceed LDS
+    if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // very large filters (> ~570 taps): populations alone exceed LDS
     const BlockMap bm = make_blockmap(d);
     {
         Scope sc(K_SEARCH, c.s);
@@ -769,7 +784,8 @@ int launch_forward(const Call<T> &c, const T *input, const T *filter, T *output,
 #ifdef CONV3P_DEV_WALK_STATS
     if (CI > 0) dev_walk_stats(c, "forward_kernel", CI, CO);
 #endif
-    Scope sc(K_FORWARD, c.s);
+    // (the generic form over a whole call has a kind of its own; over the tiles another path flagged, forward_kernel's)
+    Scope sc(CI == 0 && only_flagged == nullptr ? K_GENERIC_FWD : K_FORWARD, c.s);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(forward_kernel<T, CI, CO>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((forward_kernel<T, CI, CO>), dim3(grid_of(bm)), dim3(256), lds, c.s, c.L.pts, c.L.boxes,
@@ -816,6 +832,33 @@ template <typename T> int sparse_cap(const Stencil<T> &st, int cin, int cout, si
         }
     }
     return 0;
+}
+
+// LDS of forward_kernel for a register-path shape (what launch_forward asks for outside the transform + gather forward)
+template <typename T> size_t register_forward_lds(const Stencil<T> &st, int cin, int cout)
+{
+    return lds_common(st) + a16((size_t)st.ntap * fwd_wstr<T>(cin, cout) * sizeof(T)) + a16((size_t)st.ntap * kCntStride * sizeof(T)) +
+           256 + a16((size_t)kWavesPerBlock * 192 * 4) + a16((size_t)kWavesPerBlock * cout * 64 * sizeof(T));
+}
+template <typename T> Stencil<T> undilated_stencil(const Dims &d)
+{
+    const int32_t one[3] = {1, 1, 1};
+    return make_stencil<T>(d, one, (T)1);
+}
+bool register_backward_misfit(const Dims &d, int elem)
+{
+    if (elem == 4) {
+        const Stencil<float> st = undilated_stencil<float>(d);
+        size_t l = 0;
+        return dense_backward_lds<float>(st, d.Cin, d.Cout) > kMaxLds && sparse_cap<float>(st, d.Cin, d.Cout, l) == 0;
+    }
+    const Stencil<double> st = undilated_stencil<double>(d);
+    // (fp64 36 -> 13: three passes over column blocks of at most 5 output channels, backward_split_36_13)
+    return dense_backward_lds<double>(st, d.Cin, d.Cin == 36 && d.Cout == 13 ? 5 : d.Cout) > kMaxLds;
+}
+bool f64_register_forward_misfit(const Dims &d)
+{
+    return register_forward_lds<double>(undilated_stencil<double>(d), d.Cin, d.Cout) > kMaxLds;
 }
 
 template <typename T, int CI, int CO>
@@ -872,7 +915,7 @@ int launch_backward(const Call<T> &c, const T *grad_out, const T *input, const T
     const size_t lds = lds_common(st) + (CI > 0 ? a16((size_t)st.ntap * CO * kCntStride * sizeof(T)) + a16(256 * sizeof(T)) : 0) + 256 + tail;
     if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
     const BlockMap bm = make_blockmap(d);
-    Scope sc(K_BACKWARD, c.s);
+    Scope sc(CI == 0 && only_flagged == nullptr ? K_GENERIC_BWD : K_BACKWARD, c.s);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(backward_kernel<T, CI, CO>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((backward_kernel<T, CI, CO>), dim3(grid_of(bm)), dim3(256), lds, c.s, c.L.pts, c.L.boxes,
@@ -1294,6 +1337,7 @@ inline int f64_pack_filter(const Call<double> &c, const double *filter, int k0, 
 {
     const Dims &d = c.d;
     if (kw < bki || cw < bco) TRY(zero_async(wp, (size_t)d.ntap * bki * bco * 8, c.s));
+    Scope sc(K_TRANSPOSE, c.s);   // (the filter copies of the blocked paths; the profile tells them from the register path by it)
     hipLaunchKernelGGL(copy_block_kernel<double>, dim3(grid_1d((size_t)d.ntap * kw * cw)), dim3(256), 0, c.s,
                        filter + (size_t)k0 * d.Cout + c0, wp, d.ntap, kw, cw, (size_t)d.Cin * d.Cout, d.Cout,
                        (size_t)bki * bco, bco);
@@ -1337,23 +1381,24 @@ int f64_blocked_forward(const Call<double> &c, const double *input, const double
 }
 
 // grad_input[:, k-block] = sum over the output-channel blocks (ascending) of the block's grad_input; every block pair
-// gives its own block of grad_filter (per-workgroup partials, reduced in fixed order)
-int f64_blocked_backward(const Call<double> &c, const double *grad_out, const double *input, const double *filter,
-                         double *grad_input, double *grad_filter)
+// gives its own block of grad_filter (per-workgroup partials, reduced in fixed order).  BCO: output channels per block.
+template <int BCO>
+int f64_blocked_backward_co(const Call<double> &c, const double *grad_out, const double *input, const double *filter,
+                            double *grad_input, double *grad_filter)
 {
     const Dims &d = c.d;
-    const size_t rows = (size_t)d.B * d.N, nwb = (size_t)d.ntap * kF64BwdKi * kF64BwdCo;
+    const size_t rows = (size_t)d.B * d.N, nwb = (size_t)d.ntap * kF64BwdKi * BCO;
     const int nslots = (int)grid_of(make_blockmap(d));
     const F64Scratch w = carve_f64(c);
-    const Call<double> cp = f64_block_call(c, kF64BwdKi, kF64BwdCo);
+    const Call<double> cp = f64_block_call(c, kF64BwdKi, BCO);
     for (int k0 = 0; k0 < d.Cin; k0 += kF64BwdKi) {
         const int kw = d.Cin - k0 < kF64BwdKi ? d.Cin - k0 : kF64BwdKi;
         TRY(f64_pack_rows(c, input + k0, d.Cin, w.xp, rows, kw, kF64BwdKi));
-        for (int c0 = 0; c0 < d.Cout; c0 += kF64BwdCo) {
-            const int cw = d.Cout - c0 < kF64BwdCo ? d.Cout - c0 : kF64BwdCo;
-            TRY(f64_pack_rows(c, grad_out + c0, d.Cout, w.yp, rows, cw, kF64BwdCo));
-            TRY(f64_pack_filter(c, filter, k0, kw, c0, cw, w.wp, kF64BwdKi, kF64BwdCo));
-            TRY((launch_backward<double, kF64BwdKi, kF64BwdCo>(cp, w.yp, w.xp, w.wp, w.zp, w.parts)));
+        for (int c0 = 0; c0 < d.Cout; c0 += BCO) {
+            const int cw = d.Cout - c0 < BCO ? d.Cout - c0 : BCO;
+            TRY(f64_pack_rows(c, grad_out + c0, d.Cout, w.yp, rows, cw, BCO));
+            TRY(f64_pack_filter(c, filter, k0, kw, c0, cw, w.wp, kF64BwdKi, BCO));
+            TRY((launch_backward<double, kF64BwdKi, BCO>(cp, w.yp, w.xp, w.wp, w.zp, w.parts)));
             {
                 Scope sc(K_REDUCE, c.s);
                 hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)((nwb + kReduceW - 1) / kReduceW)), dim3(1024), 0, c.s, w.parts,
@@ -1366,11 +1411,24 @@ int f64_blocked_backward(const Call<double> &c, const double *grad_out, const do
                 hipLaunchKernelGGL(add_cols_kernel<double>, dim3(grid_1d(rows * kw)), dim3(256), 0, c.s, w.zp, grad_input + k0, rows,
                                    kw, kF64BwdKi, d.Cin);
             hipLaunchKernelGGL(copy_block_kernel<double>, dim3(grid_1d((size_t)d.ntap * kw * cw)), dim3(256), 0, c.s, w.dwp,
-                               grad_filter + (size_t)k0 * d.Cout + c0, d.ntap, kw, cw, (size_t)kF64BwdKi * kF64BwdCo, kF64BwdCo,
+                               grad_filter + (size_t)k0 * d.Cout + c0, d.ntap, kw, cw, (size_t)kF64BwdKi * BCO, BCO,
                                (size_t)d.Cin * d.Cout, d.Cout);
         }
     }
     return hip_ok();
+}
+// Blocks of kF64BwdCo output channels, else 4, else 2: the widest whose dense G fits LDS (16 x 8 up to 28 taps, 16 x 4 up
+// to 57, 16 x 2 up to 115), chosen before anything is enqueued; CONV3P_ERR_UNSUPPORTED past that.
+int f64_blocked_backward(const Call<double> &c, const double *grad_out, const double *input, const double *filter,
+                         double *grad_input, double *grad_filter)
+{
+    if (dense_backward_lds<double>(c.st, kF64BwdKi, kF64BwdCo) <= kMaxLds)
+        return f64_blocked_backward_co<kF64BwdCo>(c, grad_out, input, filter, grad_input, grad_filter);
+    if (kF64BwdCo > 4 && dense_backward_lds<double>(c.st, kF64BwdKi, 4) <= kMaxLds)
+        return f64_blocked_backward_co<4>(c, grad_out, input, filter, grad_input, grad_filter);
+    if (kF64BwdCo > 2 && dense_backward_lds<double>(c.st, kF64BwdKi, 2) <= kMaxLds)
+        return f64_blocked_backward_co<2>(c, grad_out, input, filter, grad_input, grad_filter);
+    return CONV3P_ERR_UNSUPPORTED;
 }
 
 int buf_check(const void *p, size_t have, size_t need)
@@ -1458,7 +1516,8 @@ int begin_call(Call<T> &c, const Dims &d, const int32_t *stride, T voxel, size_t
         c.wide_scratch_ok = wide_shape((int)sizeof(T), d.Cin, d.Cout) && have >= wide_scratch_bytes(d, (size_t)d.B * c.L.pairs_per_cloud);
         c.deep_fwd_ok = deep_shape((int)sizeof(T), d.Cin, d.Cout) && have >= deep_forward_bytes(d, (size_t)d.B * c.L.pairs_per_cloud);
         c.wide_fwd_ok = wide_shape((int)sizeof(T), d.Cin, d.Cout) && have >= wide_scratch_bytes(d, (size_t)d.B * c.L.pairs_per_cloud, true);
-        c.f64_scratch_ok = f64_blocked_shape((int)sizeof(T), d.Cin, d.Cout) && have >= f64_blocked_bytes(d);
+        // (register-path shapes too: the blocks take the filters their own kernels cannot)
+        c.f64_scratch_ok = sizeof(T) == 8 && d.Cin >= 1 && d.Cout >= 1 && have >= f64_blocked_bytes(d);
     }
     const unsigned long long tag = stencil_tag(d, stride, (double)voxel, (int)sizeof(T));
     if (!wh.persistent) {
@@ -1635,7 +1694,9 @@ int forward_impl(const T *points, const T *input, const T *filter, const int32_t
         }
     }
     if constexpr (sizeof(T) == 8) {
-        if (c.f64_scratch_ok && !c.strided) {   // fp64 outside the register-path shapes: 16 x 8 channel blocks on <double, 16, 8>
+        // fp64 outside the register-path shapes, and register-path shapes whose forward_kernel does not fit LDS (36 -> 13
+        // past 31 taps): 16 x 8 channel blocks on <double, 16, 8>
+        if (c.f64_scratch_ok && !c.strided) {
             const int rc = f64_blocked_forward(c, input, filter, output);
             if (rc != CONV3P_ERR_UNSUPPORTED) return rc != CONV3P_OK || !act ? rc : selu_impl<T>(output, output, out_elems, stream);
         }
@@ -1844,14 +1905,15 @@ int backward_impl(const T *grad_out, const T *points, const T *input, const T *f
     }
     if (rc == CONV3P_ERR_UNSUPPORTED && !defer && sizeof(T) == 8 && Cin == 36 && Cout == 13 &&
         small_shape((int)sizeof(T), Cin, Cout)) {
-        // (filters of more than 27 taps do not fit LDS even in column blocks: its first launch says so before anything is
-        // written, and the generic kernels below take the call -- found by tools/fuzz_gpu.py, 3 x 5 x 3 taps in fp64)
+        // (filters of more than 33 taps do not fit LDS even in column blocks: its first launch says so before anything is
+        // written, and the channel blocks below take the call -- found by tools/fuzz_gpu.py, 3 x 5 x 3 taps in fp64)
         const int src = backward_split_36_13<T>(c, grad_out, input, filter, grad_input, grad_filter);
         if (src != CONV3P_ERR_UNSUPPORTED) return src;
     }
     if constexpr (sizeof(T) == 4) {
         int cip = 0, cop = 0;
-        if (rc == CONV3P_ERR_UNSUPPORTED && c.deep_scratch_ok && deep_class(4, Cin, Cout, cip, cop)) {
+        // (also the register-path shapes whose register backward cannot take the filter: 36 -> 13 with 33 .. 64 taps)
+        if (rc == CONV3P_ERR_UNSUPPORTED && c.deep_scratch_ok && !c.strided && deep_class(4, Cin, Cout, cip, cop)) {
 #define X(ci, co)                                                                                    \
     if (cip == ci && cop == co) {                                                                    \
         int drc = deep_backward<ci, co>(c, grad_out, input, filter, grad_input, grad_filter);        \

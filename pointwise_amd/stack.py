@@ -171,6 +171,7 @@ class Conv3pStack:
         if self._side is None:
             self._side = _side_stream(points.device)
         B, N = points.shape[0], points.shape[1]
+        cache.forget_points()   # (the stack's calls re-validate the cache: an op call's identity record is void)
         with torch.cuda.device(points.device):
             ok = self._c_call("prefetch", points.data_ptr(), self._real(VOXEL), B, N, cache.buf.data_ptr(), cache.nbytes,
                               cache.cfg_ptr(False), self._side.cuda_stream, main.cuda_stream)
@@ -200,6 +201,7 @@ class Conv3pStack:
                 self._side = _side_stream(points.device)
             side = self._side.cuda_stream
         fptrs, _ = self._ptr_tables()
+        cache.forget_points()   # (the stack's calls re-validate the cache: an op call's identity record is void)
         with torch.cuda.device(points.device):
             ok = self._c_call("forward", points.data_ptr(), features.data_ptr(), ctypes.cast(fptrs, ctypes.c_void_p),
                               self._real(VOXEL), B, N, concat.data_ptr(), head.data_ptr() if head is not None else None,
@@ -234,6 +236,7 @@ class Conv3pStack:
         dx = torch.empty_like(features)
         cache = self._cache
         fptrs, gptrs = self._ptr_tables()
+        cache.forget_points()   # (the stack's calls re-validate the cache: an op call's identity record is void)
         with torch.cuda.device(points.device):
             ok = self._c_call("backward", points.data_ptr(), features.data_ptr(),
                               ctypes.cast(fptrs, ctypes.c_void_p), self._real(VOXEL), B, N, concat.data_ptr(),

@@ -73,6 +73,57 @@ def test_cache_bytes():
     assert lib.conv3p_cache_init(None, 16, None) == _lib.ERR_INVALID_ARGUMENT
 
 
+# conv3p_workspace_bytes / conv3p_cache_bytes of the models' layer configurations (3 x 3 x 3 filters): cfg1 (B=1, N=2048),
+# cfg2 (B=32, N=2048), cfg4 (B=16, N=4096), cfg5 (B=16, N=8192), fp32 and fp64.  Only configurations past a register-path
+# fit may grow their scratch (a 36 -> 13 fp32 filter of 33 .. 64 taps: the matrix-core path's; fp64: the channel blocks').
+# (pass, elem, B, N, Cin, Cout) -> bytes
+MODEL_WORKSPACE_BYTES = {
+    (0, 4, 1, 2048, 3, 9): 4788736, (1, 4, 1, 2048, 3, 9): 5535232,
+    (0, 4, 32, 2048, 3, 9): 153131776, (1, 4, 32, 2048, 3, 9): 156117760,
+    (0, 4, 32, 2048, 9, 9): 153131776, (1, 4, 32, 2048, 9, 9): 162089728,
+    (0, 4, 16, 4096, 9, 9): 153131520, (1, 4, 16, 4096, 9, 9): 162089472,
+    (0, 4, 16, 4096, 36, 13): 266377728, (1, 4, 16, 4096, 36, 13): 204888576,
+    (0, 4, 16, 8192, 128, 256): 849429504, (1, 4, 16, 8192, 128, 256): 4619453440,
+    (0, 8, 1, 2048, 3, 9): 4822272, (1, 8, 1, 2048, 3, 9): 6315264,
+    (0, 8, 32, 2048, 3, 9): 154205184, (1, 8, 32, 2048, 3, 9): 160177152,
+    (0, 8, 32, 2048, 9, 9): 154205184, (1, 8, 32, 2048, 9, 9): 172121088,
+    (0, 8, 16, 4096, 9, 9): 154204928, (1, 8, 16, 4096, 9, 9): 172120832,
+    (0, 8, 16, 4096, 36, 13): 154204928, (1, 8, 16, 4096, 36, 13): 257719040,
+    (0, 8, 16, 8192, 128, 256): 415417088, (1, 8, 16, 8192, 128, 256): 415417088,
+}
+# (elem, B, N, slots, max_taps, pairs_per_point, max_Cin, max_Cout) -> bytes (the stacks' and the bench's caches)
+MODEL_CACHE_BYTES = {
+    (4, 32, 2048, 4, 27, 0, 9, 9): 1101646080, (4, 32, 2048, 5, 27, 0, 36, 41): 1491344640,
+    (4, 16, 4096, 5, 27, 0, 36, 41): 1491343872, (4, 16, 4096, 5, 27, 0, 36, 13): 1255496192,
+    (4, 16, 8192, 1, 27, 0, 128, 256): 4619453440, (4, 1, 2048, 1, 27, 0, 3, 9): 24996864,
+    (8, 32, 2048, 4, 27, 0, 9, 9): 655257600, (8, 32, 2048, 5, 27, 0, 36, 41): 854412288,
+    (8, 16, 4096, 5, 27, 0, 36, 41): 854411520, (8, 16, 4096, 5, 27, 0, 36, 13): 854411520,
+    (8, 16, 8192, 1, 27, 0, 128, 256): 515435264, (8, 1, 2048, 1, 27, 0, 3, 9): 12741888,
+}
+
+
+def test_scratch_sizes_of_the_models_configurations_are_pinned():
+    lib = _lib.load()
+    for (p, es, B, N, ci, co), want in MODEL_WORKSPACE_BYTES.items():
+        assert lib.conv3p_workspace_bytes(p, es, B, N, ci, co, 3, 3, 3) == want, (p, es, B, N, ci, co)
+    for (es, B, N, sl, mt, ppp, mi, mo), want in MODEL_CACHE_BYTES.items():
+        got = lib.conv3p_cache_bytes(es, B, N, ctypes.byref(_lib.CacheConfig(sl, mt, ppp, mi, mo)))
+        assert got == want, (es, B, N, sl, mt, ppp, mi, mo)
+
+
+def test_scratch_grows_only_past_a_register_fit():
+    """Register-path shapes whose register kernels cannot take the filter get the scratch of the path that does: fp32 36 ->
+    13 with 33 .. 64 taps (matrix-core), fp64 shapes past their dense G (channel blocks).  Below the fit nothing changes."""
+    lib = _lib.load()
+    f = lambda p, es, ci, co, ext: lib.conv3p_workspace_bytes(p, es, 2, 500, ci, co, *ext)
+    for es, ci, co, below, above in ((4, 36, 13, (2, 4, 4), (1, 3, 11)), (8, 9, 9, (2, 2, 7), (1, 3, 11)),
+                                     (8, 3, 9, (2, 4, 4), (1, 3, 11))):
+        # (per tap, the partials of the register path grow by 1/32 from 32 to 33 taps; the other path's scratch far more)
+        assert f(1, es, ci, co, above) > 1.25 * f(1, es, ci, co, below) * 33 / 32, (es, ci, co)
+    assert f(0, 8, 36, 13, (2, 4, 4)) > 1.5 * f(0, 8, 36, 13, (3, 3, 3))   # fp64 36 -> 13 forward past 31 taps: blocks
+    assert f(1, 4, 36, 13, (1, 5, 13)) < f(1, 4, 36, 13, (4, 4, 4))          # 65 taps: generic again, no matrix-core scratch
+
+
 def test_invalid_arguments_without_touching_the_gpu():
     """The C entry points validate before any HIP call; NULL pointers are fine for this."""
     lib = _lib.load()
