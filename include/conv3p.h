@@ -308,7 +308,9 @@ int conv3p_layer_backward_cached_f64(const double *grad_out, const double *point
  * head.  filters / grad_filters are HOST arrays of n_hidden (+1) DEVICE pointers, each tensor laid out as Conv3p's
  * filter.  `cache` as for the *_cached entry points, with slots >= number of distinct strides.
  * Shapes outside the register-resident list return CONV3P_ERR_UNSUPPORTED: compose the stack
- * from the per-op entry points then.
+ * from the per-op entry points then.  The backward also refuses, before anything is launched, a description whose hidden
+ * layers past the first do not fit the register kernels' backward (fp64 9 -> 9 past 28 taps), even where the forward ran.
+ * Every layer of a supported description runs on deterministic kernels where its op would.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_STACK_MAX_LAYERS 8
 typedef struct conv3p_stack_desc {

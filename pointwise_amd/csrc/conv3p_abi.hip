@@ -1747,12 +1747,15 @@ int prepare_multi_impl(const T *points, const int32_t *strides, int K, T voxel, 
     if (!points) return CONV3P_ERR_INVALID_ARGUMENT;
     if (K > wh.nslots) return CONV3P_ERR_WORKSPACE;     // the stencils would evict each other
     hipStream_t s = static_cast<hipStream_t>(stream);
+    // Every stencil takes the search a single prepare would give it (run_search): the fused search where it fits, the
+    // tile-pair search otherwise.  The two build their pair lists in different orders, so a stencil batched into the other
+    // search would give sums of other bits (e.g. the odd stencils of a stack whose other strides make an even, windowed one).
     SearchJobs<T> jobs;
     FusedJobs<T> fjobs;
-    SchedJobs sjobs;
-    int njobs = 0;
+    SchedJobs sjobs, fsjobs;
+    int njobs = 0, nfused = 0;
     size_t lds = 0;
-    bool any_window = false, all_fused = true;
+    bool any_window = false;
     Call<T> c;
     for (int k = 0; k < K; ++k) {
         TRY(begin_call<T>(c, d, strides + 3 * k, voxel, 0, wh, s));
@@ -1762,12 +1765,15 @@ int prepare_multi_impl(const T *points, const int32_t *strides, int K, T voxel, 
         const Stencil<T> &st = c.st;
         const auto &S = c.L.slot[c.slot];
         TRY(run_cloud_min<T>(points, c));
+        if (fused_ok(c) && fused_mask_depth((int)sizeof(T), c.d.ntiles, c.st.ntap, c.st.maxfull) > 0) {
+            fjobs.job[nfused] = make_fused_job(c);
+            fsjobs.job[nfused++] = make_sched_job(c, c.slot, true);
+            continue;
+        }
         any_window |= st.window != 0;
         const size_t l = search_lds_bytes(st, c.L.gtiles);
         if (l > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
         lds = l > lds ? l : lds;
-        all_fused &= fused_ok(c) && fused_mask_depth((int)sizeof(T), c.d.ntiles, c.st.ntap, c.st.maxfull) > 0;
-        fjobs.job[njobs] = make_fused_job(c);
         SearchJob<T> &j = jobs.job[njobs++];
         j.st = st;
         j.cc = c.cc;
@@ -1780,8 +1786,8 @@ int prepare_multi_impl(const T *points, const int32_t *strides, int K, T voxel, 
         j.qbm_hi = S.qbm_hi;
         sjobs.job[njobs - 1] = make_sched_job(c, c.slot, true);
     }
+    if (nfused > 0) TRY(launch_fused<T>(c, fjobs, fsjobs, nfused));
     if (njobs == 0) return CONV3P_OK;
-    if (all_fused) return launch_fused<T>(c, fjobs, sjobs, njobs);
     for (int k = 0; k < njobs; ++k)   // (the tile-pair search lets fewer false positives through: its own threshold)
         sjobs.job[k].limit = kShortListsPerPoint * (unsigned long long)c.d.B * (unsigned long long)c.d.N;
 #ifndef CONV3P_DEV_JOBS_IN_ORDER
@@ -1903,7 +1909,9 @@ int backward_impl(const T *grad_out, const T *points, const T *input, const T *f
         defer->job = ReduceJob<T>{region, grad_filter, nslots, (unsigned)nw};
         return CONV3P_OK;
     }
-    if (rc == CONV3P_ERR_UNSUPPORTED && !defer && sizeof(T) == 8 && Cin == 36 && Cout == 13 &&
+    // (the fp64 column split and channel blocks below reduce and write grad_filter themselves: under `defer` they leave
+    // defer->job empty, as the matrix-core path does, and the stack's reduction skips the layer)
+    if (rc == CONV3P_ERR_UNSUPPORTED && sizeof(T) == 8 && Cin == 36 && Cout == 13 &&
         small_shape((int)sizeof(T), Cin, Cout)) {
         // (filters of more than 33 taps do not fit LDS even in column blocks: its first launch says so before anything is
         // written, and the channel blocks below take the call -- found by tools/fuzz_gpu.py, 3 x 5 x 3 taps in fp64)
@@ -1934,7 +1942,7 @@ int backward_impl(const T *grad_out, const T *points, const T *input, const T *f
         }
     }
     if constexpr (sizeof(T) == 8) {
-        if (rc == CONV3P_ERR_UNSUPPORTED && c.f64_scratch_ok && !c.strided && !defer) {
+        if (rc == CONV3P_ERR_UNSUPPORTED && c.f64_scratch_ok && !c.strided) {
             const int brc = f64_blocked_backward(c, grad_out, input, filter, grad_input, grad_filter);
             if (brc != CONV3P_ERR_UNSUPPORTED)
                 return brc != CONV3P_OK || !act ? brc
@@ -2524,6 +2532,26 @@ int stack_backward_fused(const conv3p_stack_desc *sd, const T *points, const T *
     }
 }
 
+// The hidden layers past the first read and write column blocks of `concat` (row strides), which only the register kernels
+// take: each must be a register shape whose backward fits LDS (fp64: the dense G; fp32: the dense G or the populated rows).
+// Checked before anything is launched, so that a description the backward cannot serve (fp64 9 -> 9 past 28 taps, hidden
+// widths outside the list) returns CONV3P_ERR_UNSUPPORTED with every output untouched.
+template <typename T> int stack_backward_fits(const conv3p_stack_desc *sd, T voxel, int B, int N)
+{
+    const int H = sd->hidden;
+    for (int l = 1; l < sd->n_hidden; ++l) {
+        if (!small_shape((int)sizeof(T), H, H)) return CONV3P_ERR_UNSUPPORTED;
+        Dims d{B, N, H, H, sd->fz, sd->fy, sd->fx, 0, 0};
+        TRY(check(d, sd->strides[l], (double)voxel, true));
+        const Stencil<T> st = make_stencil<T>(d, sd->strides[l], voxel);
+        if (dense_backward_lds<T>(st, H, H) <= kMaxLds) continue;
+        size_t lds = 0;
+        if (sizeof(T) == 4 && sparse_cap<T>(st, H, H, lds) > 0) continue;
+        return CONV3P_ERR_UNSUPPORTED;
+    }
+    return CONV3P_OK;
+}
+
 template <typename T>
 int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *input, const T *const *filters, T voxel,
                         int B, int N, const T *concat, const T *head_out, const T *grad_concat, const T *grad_head,
@@ -2537,6 +2565,7 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
         (!has_head && !grad_concat))
         return CONV3P_ERR_INVALID_ARGUMENT;
     if (has_head && grad_concat) return CONV3P_ERR_UNSUPPORTED;   // (see conv3p.h: not needed by either model) -- before any launch
+    TRY(stack_backward_fits<T>(sd, voxel, B, N));
     TRY(buf_check(scratch, scratch_bytes, stack_scratch_bytes<T>(sd, B, N)));
     const size_t rows = (size_t)B * N;
     const int H = sd->hidden, CW = sd->n_hidden * H, nh = sd->n_hidden;

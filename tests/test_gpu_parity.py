@@ -12,6 +12,7 @@ import torch
 from oracle import oracle
 from pointwise_amd import _lib, conv3p_op as op, stack, synth
 from tests.parity_util import TOL, exact_from_oracle_lists, make_case, rel_err
+from tests.stack_ref import stack_reference
 
 pytestmark = pytest.mark.gpu
 VOX = 0.1
@@ -409,29 +410,15 @@ def test_scenenn_model_shapes(dev, ci, co, N):
 
 # ------------------------------------------------------------------ the models' layer stacks (row A8)
 def _oracle_stack(P, X, filters, layers, ups, num_class, nthreads=1):
-    fwd = lambda *a: oracle.forward(*a, nthreads=nthreads) if nthreads > 1 else oracle.forward(*a)
-    acts, x = [], X
-    for li in range(4):
-        s = layers[li][2]
-        x = stack.selu_numpy(fwd(P, x, filters[li], (s, s, s), VOX))
-        acts.append(x)
-    dws = [None] * len(layers)
+    """Conv3pStack's layers on the general stack reference (tests/stack_ref.py): activations, grad_input and the fused
+    grad_filter of all layers."""
+    strides = [(s, s, s) for _, _, s in layers]
     if num_class is not None:
-        concat = np.concatenate(acts, axis=2)
-        logits = stack.selu_numpy(fwd(P, concat, filters[4], (1, 1, 1), VOX))
-        acts.append(logits)
-        g = stack.selu_grad_numpy(logits, ups[0])
-        dconcat, dws[4] = oracle.backward(g, P, concat, filters[4], (1, 1, 1), VOX, **({"nthreads": nthreads} if nthreads > 1 else {}))
-        ext = [np.ascontiguousarray(dconcat[:, :, 9 * i:9 * i + 9]) for i in range(4)]
+        acts, dx, dws = stack_reference(P, X, filters, strides, stack.HIDDEN, grad_head=ups[0], nthreads=nthreads)
     else:
-        ext = ups
-    carry = None
-    for li in (3, 2, 1, 0):
-        s = layers[li][2]
-        g = stack.selu_grad_numpy(acts[li], ext[li] if carry is None else ext[li] + carry)
-        kw = {"nthreads": nthreads} if nthreads > 1 else {}
-        carry, dws[li] = oracle.backward(g, P, acts[li - 1] if li > 0 else X, filters[li], (s, s, s), VOX, **kw)
-    return acts, carry, np.concatenate([d.reshape(-1) for d in dws])
+        acts, dx, dws = stack_reference(P, X, filters, strides, stack.HIDDEN, grad_concat=np.concatenate(ups, axis=2),
+                                        nthreads=nthreads)
+    return acts, dx, np.concatenate([d.reshape(-1) for d in dws])
 
 
 _REF_MEMO = {}
