@@ -257,25 +257,43 @@ Layout<T> carve(int B, int N, int ntiles, int ntap_max, int nslots, int pairs_pe
     return L;
 }
 
-// ----------------------------------------------------------------------------- dispatch table
+// ----------------------------------------------------------------------------- routes
 // (Cin, Cout) pairs with register-resident rows: the layers of the reference's two models
 // (pointcnn2_acsd.py:48-66: Cin->9, 9->9; pointcnn_scene_seg_acsd.py:51-57: +36->num_class,
 // 13 classes for S3DIS) plus a few neighbours.  Everything else takes the generic path.
 #define CONV3P_SMALL_SHAPES(X) X(3, 9) X(6, 9) X(9, 9) X(12, 9) X(36, 13) X(3, 3) X(9, 3)
 
-inline bool small_shape(int elem, int cin, int cout)
-{
-#ifdef CONV3P_DEV_SKIP_SMALL   // developer build only (-DCONV3P_DEV_SKIP_SMALL): time the other paths on the models' shapes
-    return false;
-#endif
-    (void)elem;   // fp32 and fp64 (the kernels are templates on T; shapes whose LDS does not fit fall back at launch)
-#define X(ci, co) if (cin == ci && cout == co) return true;
-    CONV3P_SMALL_SHAPES(X)
-#undef X
-    return false;
-}
+// The kernel family that serves one pass of a call and what it needs.  plan_forward / plan_backward (below) are the one
+// place that chooses it, from the call's dtype, channels, stencil, strides, hints and precision, before anything is
+// launched; the workspace and cache sizes are the same planners applied to the undilated stencil.
+enum class Family { Register, Split36x13, MatrixCore, Wide, F64Blocks, Generic, Unsupported };
+struct Route {
+    Family family = Family::Generic;
+    int cip = 0, cop = 0;       // MatrixCore: the padded (instantiated) channel class
+    int co = 0;                 // F64Blocks backward: output channels per block (8, 4 or 2)
+    int cap = 0;                // Register, fp32 backward: rows of the populated-rows G (0: the dense-G kernel only)
+    bool regime = false;        // ... and the dense-G kernel after it, the slot's regime word letting exactly one of them run
+    bool tap = false;           // Register, fp32 forward: transform + gather
+    size_t lds = 0;             // dynamic LDS of the route's kernel (Split36x13: its 5-column pass; MatrixCore, Wide: unused)
+    size_t lds4 = 0;            // Split36x13: its 4-column passes
+    size_t sparse_lds = 0;      // Register, fp32 backward: the populated-rows kernel
+    size_t generic_lds = 0;     // the generic kernel (also over the tiles the matrix-core kernels flag)
+    int slots = 1;              // Register, Generic backward: grad_filter partials
+    size_t scratch = 0;         // bytes of per-call scratch the route uses (backward: at least the generic fallback's)
+    size_t mandatory = 0;       // ... of them, what the call cannot run without (the rest only lets it take this route)
+    bool self_reduces = true;   // backward: writes grad_filter itself (Register leaves per-workgroup partials instead)
+};
+// What a route depends on besides the dtype, Dims and stencil.  have: bytes of scratch of the buffer (SIZE_MAX when
+// sizing one); pair_slots, ngroups: the buffer's pair storage and search groups (scratch of the matrix-core path).
+struct PlanArgs {
+    bool strided = false;       // some tensor is a column block of a wider buffer (register kernels only)
+    bool sparse_hint = false, dense_hint = false;
+    int prec = kPrecF32;
+    size_t pair_slots = 0;
+    int ngroups = 1;
+    size_t have = SIZE_MAX;
+};
 
-inline bool deep_shape(int elem, int cin, int cout);
 struct DeepScratch;
 size_t deep_scratch_bytes(const Dims &d, size_t pair_slots);
 size_t deep_forward_bytes(const Dims &d, size_t pair_slots);
@@ -332,64 +350,14 @@ constexpr int kF64BwdKi = CONV3P_F64_BWD_KI, kF64BwdCo = CONV3P_F64_BWD_CO;   //
 constexpr int kF64Ki = kF64FwdKi > kF64BwdKi ? kF64FwdKi : kF64BwdKi;         // (scratch: sized for the larger of the two)
 constexpr int kF64Co = kF64FwdCo > kF64BwdCo ? kF64FwdCo : kF64BwdCo;
 constexpr int kF64Row = kF64Ki > kF64Co ? kF64Ki : kF64Co;
-inline bool f64_blocked_shape(int elem, int cin, int cout) { return elem == 8 && cin >= 1 && cout >= 1 && !small_shape(elem, cin, cout); }
 inline size_t f64_blocked_bytes(const Dims &d)
 {
     const size_t rows = (size_t)d.B * d.N, nwb = (size_t)d.ntap * kF64Ki * kF64Co;
     return up((size_t)grid_of(make_blockmap(d)) * nwb * 8) + 3 * up(rows * kF64Row * 8) + 2 * up(nwb * 8);
 }
 
-// Register-path shapes whose register kernels cannot take the filter (LDS), judged on the undilated stencil of the
-// call's extents -- what the workspace query (no stride argument) and the call itself both know.  Their calls run on the
-// deterministic paths of the other shapes, whose scratch is then provisioned: fp32 backward on the matrix-core kernels
-// (filters of up to 64 taps), fp64 backward and forward as channel blocks.  (A dilation large enough to tip a filter past
-// the fit on its own would find that scratch only in a cache: a stateless call takes the generic kernels.)
-bool register_backward_misfit(const Dims &d, int elem);
-bool f64_register_forward_misfit(const Dims &d);
-
-// ppp: pair slots per point of the buffer the call runs in (a cache may be configured with fewer than the default)
-size_t backward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPerPoint)
-{
-    const size_t nw = (size_t)d.ntap * d.Cin * d.Cout;
-    size_t deep = 0;
-    if (wide_shape(elem, d.Cin, d.Cout)) deep = wide_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
-    if (f64_blocked_shape(elem, d.Cin, d.Cout)) deep = f64_blocked_bytes(d);
-    if (!small_shape(elem, d.Cin, d.Cout) && deep_shape(elem, d.Cin, d.Cout))
-        deep = deep_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
-    if (small_shape(elem, d.Cin, d.Cout) && register_backward_misfit(d, elem)) {
-        if (elem == 8) deep = f64_blocked_bytes(d);
-        else if (d.ntap <= 64 && deep_shape(elem, d.Cin, d.Cout)) deep = deep_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
-    }
-    // register path: one partial per workgroup; generic path (also the fallback of the other two): generic_slots
-    const size_t slots = small_shape(elem, d.Cin, d.Cout) ? (size_t)grid_of(make_blockmap(d)) : (size_t)generic_slots(d, elem);
-    const size_t plain = nw * slots * (size_t)elem;
-    return deep > plain ? deep : plain;
-}
-
-// Shapes whose forward runs as transform + gather (conv3p_forward_taps.hpp): fp32 register-path shapes with at least
-// 16 inputs and at most 16 outputs.  Their scratch: Z [B N][ntap][16] floats.
-inline bool tap_forward_shape(int elem, int cin, int cout)
-{
-#ifdef CONV3P_DEV_NO_TAP_FORWARD   // developer A/B build
-    return false;
-#endif
-    return elem == 4 && small_shape(elem, cin, cout) && cin >= 16 && cin % 4 == 0 && cout <= 16;
-}
+// The transform + gather forward's scratch (conv3p_forward_taps.hpp): Z [B N][ntap][16] floats.
 inline size_t tap_forward_bytes(const Dims &d) { return (size_t)d.B * d.N * (size_t)d.ntap * kZRow * 4; }
-
-// mandatory_only: what the forward cannot run without.  The transform + gather forward's Z array is optional (without
-// it the layer runs on forward_kernel, same results): a persistent cache sized for narrower layers must not be refused
-// for it (Call::tap_scratch_ok decides per call).
-size_t forward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPerPoint, bool mandatory_only = false)
-{
-    if (tap_forward_shape(elem, d.Cin, d.Cout)) return mandatory_only ? 0 : tap_forward_bytes(d);
-    if (!small_shape(elem, d.Cin, d.Cout) && deep_shape(elem, d.Cin, d.Cout))
-        return deep_forward_bytes(d, (size_t)d.B * d.N * (size_t)ppp);
-    if (wide_shape(elem, d.Cin, d.Cout)) return mandatory_only ? 0 : wide_scratch_bytes(d, (size_t)d.B * d.N * (size_t)ppp, true);
-    if (f64_blocked_shape(elem, d.Cin, d.Cout)) return mandatory_only ? 0 : f64_blocked_bytes(d);
-    if (elem == 8 && small_shape(elem, d.Cin, d.Cout) && f64_register_forward_misfit(d)) return mandatory_only ? 0 : f64_blocked_bytes(d);
-    return 0;
-}
 
 bool cache_cfg_ok(const conv3p_cache_config *cfg);
 
@@ -412,12 +380,7 @@ template <typename T> struct Call {
     int slot;
     CacheCtl cc;
     hipStream_t s;
-    bool deep_scratch_ok = false;  // the scratch region can hold the deep path's side arrays
-    bool deep_fwd_ok = false;      // ... what its FORWARD needs of them (no G tiles, no partials)
-    bool wide_fwd_ok = false;      // ... the forward of the blocked path (packs placed after the forward-only deep part)
-    bool tap_scratch_ok = false;   // ... the transform + gather forward's Z array
-    bool wide_scratch_ok = false;  // ... the blocked path of layers with more than 256 channels
-    bool f64_scratch_ok = false;   // ... the blocked path of fp64 layers outside the register-path shapes
+    size_t scratch = 0;            // bytes of the scratch region (L.partials)
     bool order_ok[2] = {false, false};   // the deep path's forward / backward record order of this geometry is in the scratch
     int prec = kPrecF32;           // filter contractions of the matrix-core path: kPrecBf16 = CONV3P_CACHE_MATMUL_BF16
     void *cache_key = nullptr;     // persistent cache the call runs in (host bookkeeping of the record orders)
@@ -428,8 +391,6 @@ template <typename T> struct Call {
     // conv3p_layer_*: SELU fused into the op (pointcnn2_acsd.py:48-49).  forward: output = selu(conv);
     // backward: grad_input = (dX + addend) * selu'(input)
     bool act = false;
-    bool sparse_hint = false;      // CONV3P_CACHE_SPARSE_NEIGHBOURHOODS: short pair lists expected (see conv3p.h)
-    bool dense_hint = false;       // CONV3P_CACHE_DENSE_NEIGHBOURHOODS: long ones (neither: decided on the device)
     bool accum = false;            // backward: add to the grad_input already there (column-split passes)
     const T *addend = nullptr;
     RowLd ld{0, 0, 0, 0, 0};       // row strides of the feature tensors; filled with the dense values by set_ld()
@@ -747,20 +708,20 @@ template <typename T> void dev_walk_stats(const Call<T> &c, const char *what, in
 }
 #endif
 
+// lds: the route's (plan_forward); tap: the transform + gather forward (fp32 Cin >= 16, Cout <= 16 register shapes)
 template <typename T, int CI, int CO>
-int launch_forward(const Call<T> &c, const T *input, const T *filter, T *output, const uint8_t *only_flagged = nullptr)
+int launch_forward(const Call<T> &c, size_t lds, bool tap, const T *input, const T *filter, T *output,
+                   const uint8_t *only_flagged = nullptr)
 {
     const Dims &d = c.d;
     const Stencil<T> &st = c.st;
     const auto &S = c.L.slot[c.slot];
     if constexpr (sizeof(T) == 4 && CI >= 16 && CI % 4 == 0 && CO <= 16) {
         // transform + gather (conv3p_forward_taps.hpp): Z = X . W[f] for every point and tap, then 64 bytes per pair
-        if (only_flagged == nullptr && c.tap_scratch_ok) {
+        if (tap) {
             float *z = c.L.partials;
             const size_t rows = (size_t)d.B * d.N;
             const BlockMap bm = make_blockmap(d);
-            const size_t glds = lds_common(st) + a16((size_t)st.ntap * kCntStride * 4) + 256 +
-                                a16((size_t)kWavesPerBlock * 192 * 4) + a16((size_t)kWavesPerBlock * CO * 64 * 4);
 #ifdef CONV3P_DEV_WALK_STATS
             dev_walk_stats(c, "tap_gather_kernel", CI, CO);
 #endif
@@ -768,18 +729,13 @@ int launch_forward(const Call<T> &c, const T *input, const T *filter, T *output,
             hipLaunchKernelGGL((tap_transform_kernel<CI, CO>), dim3((unsigned)((rows + 127) / 128)), dim3(256), 0, c.s, input,
                                filter, z, rows, st.ntap, c.ld.in);
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(tap_gather_kernel<CO>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
-            hipLaunchKernelGGL((tap_gather_kernel<CO>), dim3(grid_of(bm)), dim3(256), glds, c.s, c.L.pts, c.L.boxes, S.count,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((tap_gather_kernel<CO>), dim3(grid_of(bm)), dim3(256), lds, c.s, c.L.pts, c.L.boxes, S.count,
                                S.pairs, S.segs, S.qsegs, z, st, d.N, d.ntiles, c.L.ngroups, bm, output, c.act ? 1 : 0,
                                st.window ? c.L.cmin : nullptr, S.tcount, c.ld, sched_of(S));
             return hip_ok();
         }
     }
-    const size_t lds = lds_common(st) + (CI > 0 ? a16((size_t)st.ntap * fwd_wstr<T>(CI, CO) * sizeof(T)) : 0) +
-                       a16((size_t)st.ntap * kCntStride * sizeof(T)) +
-                       256 + a16((size_t)kWavesPerBlock * 192 * 4) +
-                       (CI > 0 ? a16((size_t)kWavesPerBlock * CO * 64 * sizeof(T)) : 0);
-    if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
     const BlockMap bm = make_blockmap(d);
 #ifdef CONV3P_DEV_WALK_STATS
     if (CI > 0) dev_walk_stats(c, "forward_kernel", CI, CO);
@@ -795,17 +751,31 @@ int launch_forward(const Call<T> &c, const T *input, const T *filter, T *output,
     return hip_ok();
 }
 
-// Rows of the populated-rows G matrix (conv3p_backward_sparse.hpp) that fit LDS next to the kernel's other arrays with
-// four (else three, else two) workgroups per CU; 0: use backward_kernel's dense G.
-// LDS of backward_kernel's dense G for a register-path shape (what launch_backward asks for)
+// LDS of forward_kernel<T, cin, cout> (cin == 0: its generic form)
+template <typename T> size_t forward_lds(const Stencil<T> &st, int cin, int cout)
+{
+    return lds_common(st) + (cin > 0 ? a16((size_t)st.ntap * fwd_wstr<T>(cin, cout) * sizeof(T)) : 0) +
+           a16((size_t)st.ntap * kCntStride * sizeof(T)) + 256 + a16((size_t)kWavesPerBlock * 192 * 4) +
+           (cin > 0 ? a16((size_t)kWavesPerBlock * cout * 64 * sizeof(T)) : 0);
+}
+// LDS of tap_gather_kernel<cout>
+inline size_t tap_gather_lds(const Stencil<float> &st, int cout)
+{
+    return lds_common(st) + a16((size_t)st.ntap * kCntStride * 4) + 256 + a16((size_t)kWavesPerBlock * 192 * 4) +
+           a16((size_t)kWavesPerBlock * cout * 64 * 4);
+}
+// LDS of backward_kernel<T, cin, cout>, the dense-G kernel (cin == 0: its generic form); its reduce buffer [4][cin][64]
+// aliases { Wt | X tile | SoA }
 template <typename T> size_t dense_backward_lds(const Stencil<T> &st, int cin, int cout)
 {
     const size_t nw = (size_t)st.ntap * cin * cout;
-    size_t tail = a16(nw * sizeof(T)) + a16((size_t)64 * cin * sizeof(T)) + a16((size_t)kWavesPerBlock * 192 * 4);
-    const size_t red = a16((size_t)kWavesPerBlock * cin * 64 * sizeof(T));
+    size_t tail = (cin > 0 ? a16(nw * sizeof(T)) + a16((size_t)64 * cin * sizeof(T)) : 0) + a16((size_t)kWavesPerBlock * 192 * 4);
+    const size_t red = cin > 0 ? a16((size_t)kWavesPerBlock * cin * 64 * sizeof(T)) : 0;
     if (tail < red) tail = red;
-    return lds_common(st) + a16((size_t)st.ntap * cout * kCntStride * sizeof(T)) + a16(256 * sizeof(T)) + 256 + tail;
+    return lds_common(st) + (cin > 0 ? a16((size_t)st.ntap * cout * kCntStride * sizeof(T)) + a16(256 * sizeof(T)) : 0) + 256 + tail;
 }
+// Rows of the populated-rows G matrix (conv3p_backward_sparse.hpp) that fit LDS next to the kernel's other arrays with
+// four (else three, else two) workgroups per CU; 0: use backward_kernel's dense G.
 template <typename T> int sparse_cap(const Stencil<T> &st, int cin, int cout, size_t &lds)
 {
     // (phase B holds the output channels in one 16-wide block; 33 .. 64 taps: the narrow layers' 64-bit tap sets, 65 .. 128:
@@ -833,97 +803,106 @@ template <typename T> int sparse_cap(const Stencil<T> &st, int cin, int cout, si
     }
     return 0;
 }
-
-// LDS of forward_kernel for a register-path shape (what launch_forward asks for outside the transform + gather forward)
-template <typename T> size_t register_forward_lds(const Stencil<T> &st, int cin, int cout)
-{
-    return lds_common(st) + a16((size_t)st.ntap * fwd_wstr<T>(cin, cout) * sizeof(T)) + a16((size_t)st.ntap * kCntStride * sizeof(T)) +
-           256 + a16((size_t)kWavesPerBlock * 192 * 4) + a16((size_t)kWavesPerBlock * cout * 64 * sizeof(T));
-}
 template <typename T> Stencil<T> undilated_stencil(const Dims &d)
 {
     const int32_t one[3] = {1, 1, 1};
     return make_stencil<T>(d, one, (T)1);
 }
-bool register_backward_misfit(const Dims &d, int elem)
+
+// The populated-rows kernel: narrow dilated layers when the pair lists are short, layers of >= 16 inputs always (their
+// dense G plus the transposed filter take 151 KiB of LDS, one workgroup per CU; the populated rows fit two), and filters
+// whose dense G does not fit LDS at all.  regime: launched for the short-lists case only -- the dense-G kernel follows and
+// the slot's regime word (tile_sched_kernel, from the lists just built) lets exactly one of them run: the choice needs
+// neither the caller nor a host synchronisation, at the price of one empty launch (~5 us).
+template <typename T, int CI, int CO>
+int launch_backward_sparse(const Call<T> &c, const Route &r, const T *grad_out, const T *input, const T *filter,
+                           T *grad_input, T *partials)
 {
-    if (elem == 4) {
-        const Stencil<float> st = undilated_stencil<float>(d);
-        size_t l = 0;
-        return dense_backward_lds<float>(st, d.Cin, d.Cout) > kMaxLds && sparse_cap<float>(st, d.Cin, d.Cout, l) == 0;
+    if constexpr (CI > 0 && CO <= 16 && sizeof(T) == 4) {
+        const Dims &d = c.d;
+        const Stencil<T> &st = c.st;
+        const auto &S = c.L.slot[c.slot];
+        const BlockMap bm = make_blockmap(d);
+        Scope sc(K_BACKWARD, c.s);
+        auto go = [&](auto kern) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.sparse_lds);
+            hipLaunchKernelGGL(kern, dim3(grid_of(bm)), dim3(256), r.sparse_lds, c.s, c.L.pts, c.L.boxes,
+                               S.count, S.pairs, S.segs, S.qsegs, S.qbm, S.qbm_hi, grad_out, input, filter, st, d.N, d.ntiles, c.L.ngroups,
+                               bm, grad_input, partials, (c.act ? 1 : 0) | (c.accum ? 2 : 0), c.addend,
+                               st.window ? c.L.cmin : nullptr, c.ld, r.cap, sched_of(S),
+                               r.regime ? S.regime : static_cast<const uint32_t *>(nullptr));
+        };
+        if constexpr (CI < 16) {
+            if (st.ntap > 64) go(backward_sparse_kernel<T, CI, CO, 2>);        // 128-bit tap sets
+            else if (st.ntap > 32) go(backward_sparse_kernel<T, CI, CO, 1>);   // 64-bit tap sets
+            else go(backward_sparse_kernel<T, CI, CO, 0>);
+        } else {
+            go(backward_sparse_kernel<T, CI, CO, 0>);
+        }
+        return hip_ok();
+    } else {
+        return CONV3P_ERR_UNSUPPORTED;   // (never planned: fp64 and wide outputs have no populated-rows kernel)
     }
-    const Stencil<double> st = undilated_stencil<double>(d);
-    // (fp64 36 -> 13: three passes over column blocks of at most 5 output channels, backward_split_36_13)
-    return dense_backward_lds<double>(st, d.Cin, d.Cin == 36 && d.Cout == 13 ? 5 : d.Cout) > kMaxLds;
-}
-bool f64_register_forward_misfit(const Dims &d)
-{
-    return register_forward_lds<double>(undilated_stencil<double>(d), d.Cin, d.Cout) > kMaxLds;
 }
 
+// The dense-G kernel (CI == 0: its generic form).  lds: the route's (plan_backward); regime: see launch_backward_sparse.
 template <typename T, int CI, int CO>
-int launch_backward(const Call<T> &c, const T *grad_out, const T *input, const T *filter, T *grad_input,
-                    T *partials = nullptr, const uint8_t *only_flagged = nullptr, int gen_slots = 1)
+int launch_backward(const Call<T> &c, size_t lds, const T *grad_out, const T *input, const T *filter, T *grad_input,
+                    T *partials, const uint8_t *only_flagged = nullptr, int gen_slots = 1, const uint32_t *regime = nullptr)
 {
     const Dims &d = c.d;
     const Stencil<T> &st = c.st;
     const auto &S = c.L.slot[c.slot];
-    const size_t nw = (size_t)st.ntap * d.Cin * d.Cout;
-    const uint32_t *regime = nullptr;   // non-null: the populated-rows kernel was launched for the short-lists case
-#ifndef CONV3P_DEV_DENSE_BACKWARD   // developer A/B build: always the dense-G kernel
-    if constexpr (CI > 0 && CO <= 16 && sizeof(T) == 4) {
-        size_t slds = 0;
-        // narrow layers: on the caller's hint (short pair lists); layers of >= 16 inputs: always -- their dense G
-        // plus the transposed filter take 151 KiB of LDS (one workgroup per CU), the populated rows fit two
-        // layers of >= 16 inputs: always (their dense G plus the transposed filter take 151 KiB of LDS, one workgroup per
-        // CU; the populated rows fit two).  Narrow dilated layers: when the pair lists are short -- on the caller's hint
-        // (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS) this kernel alone; without it BOTH kernels are launched and the slot's
-        // regime word (tile_sched_kernel, from the lists just built) lets exactly one of them run: the choice needs
-        // neither the caller nor a host synchronisation, at the price of one empty launch (~5 us).
-        // (a filter whose dense G does not fit LDS -- more than ~60 taps at 9 output channels -- has only this kernel: no
-        // regime word, no hint can send it to the dense one)
-        const bool dense_fits = dense_backward_lds<T>(st, CI, CO) <= kMaxLds;
-        const int cap = only_flagged == nullptr && !(CI < 16 && c.dense_hint && dense_fits) ? sparse_cap<T>(st, CI, CO, slds) : 0;
-        const bool by_regime = CI < 16 && !c.sparse_hint && dense_fits;
-        if (cap > 0) {
-            const BlockMap bm = make_blockmap(d);
-            Scope sc(K_BACKWARD, c.s);
-            auto go = [&](auto kern) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds);
-                hipLaunchKernelGGL(kern, dim3(grid_of(bm)), dim3(256), slds, c.s, c.L.pts, c.L.boxes,
-                                   S.count, S.pairs, S.segs, S.qsegs, S.qbm, S.qbm_hi, grad_out, input, filter, st, d.N, d.ntiles, c.L.ngroups,
-                                   bm, grad_input, partials ? partials : c.L.partials, (c.act ? 1 : 0) | (c.accum ? 2 : 0), c.addend,
-                                   st.window ? c.L.cmin : nullptr, c.ld, cap, sched_of(S),
-                                   by_regime ? S.regime : static_cast<const uint32_t *>(nullptr));
-            };
-            if constexpr (CI < 16) {
-                if (st.ntap > 64) go(backward_sparse_kernel<T, CI, CO, 2>);        // 128-bit tap sets
-                else if (st.ntap > 32) go(backward_sparse_kernel<T, CI, CO, 1>);   // 64-bit tap sets
-                else go(backward_sparse_kernel<T, CI, CO, 0>);
-            } else {
-                go(backward_sparse_kernel<T, CI, CO, 0>);
-            }
-            if (!by_regime) return hip_ok();
-            regime = S.regime;
-        }
-    }
-#endif
-    // reduce buffer [4][CI][64] aliases { Wt | X tile | SoA }
-    size_t tail = (CI > 0 ? a16(nw * sizeof(T)) + a16((size_t)64 * CI * sizeof(T)) : 0) + a16((size_t)kWavesPerBlock * 192 * 4);
-    const size_t red = CI > 0 ? a16((size_t)kWavesPerBlock * CI * 64 * sizeof(T)) : 0;
-    if (tail < red) tail = red;
-    const size_t lds = lds_common(st) + (CI > 0 ? a16((size_t)st.ntap * CO * kCntStride * sizeof(T)) + a16(256 * sizeof(T)) : 0) + 256 + tail;
-    if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
     const BlockMap bm = make_blockmap(d);
     Scope sc(CI == 0 && only_flagged == nullptr ? K_GENERIC_BWD : K_BACKWARD, c.s);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(backward_kernel<T, CI, CO>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((backward_kernel<T, CI, CO>), dim3(grid_of(bm)), dim3(256), lds, c.s, c.L.pts, c.L.boxes,
                        S.count, S.pairs, S.segs, S.qsegs, grad_out, input, filter, st, d.N, d.ntiles, c.L.ngroups,
-                       d.Cin, d.Cout, bm, grad_input, partials ? partials : c.L.partials, only_flagged,
+                       d.Cin, d.Cout, bm, grad_input, partials, only_flagged,
                        ((CI > 0 && c.act) ? 1 : 0) | ((CI > 0 && c.accum) ? 2 : 0), c.addend, gen_slots,
                        st.window ? c.L.cmin : nullptr, c.ld, sched_of(S), regime);
     return hip_ok();
+}
+
+// A register-path shape's pass as the route says (the table of instantiations below)
+template <typename T, int CI, int CO>
+int register_forward(const Call<T> &c, const Route &r, const T *input, const T *filter, T *output)
+{
+    return launch_forward<T, CI, CO>(c, r.lds, r.tap, input, filter, output);
+}
+template <typename T, int CI, int CO>
+int register_backward(const Call<T> &c, const Route &r, const T *grad_out, const T *input, const T *filter, T *grad_input,
+                      T *partials)
+{
+    if (r.cap > 0) TRY((launch_backward_sparse<T, CI, CO>(c, r, grad_out, input, filter, grad_input, partials)));
+    if (r.cap > 0 && !r.regime) return CONV3P_OK;
+    return launch_backward<T, CI, CO>(c, r.lds, grad_out, input, filter, grad_input, partials, nullptr, 1,
+                                      r.cap > 0 ? c.L.slot[c.slot].regime : nullptr);
+}
+template <typename T> struct RegisterShape {
+    int cin, cout;
+    int (*forward)(const Call<T> &, const Route &, const T *, const T *, T *);
+    int (*backward)(const Call<T> &, const Route &, const T *, const T *, const T *, T *, T *);
+};
+template <typename T> const RegisterShape<T> kRegisterShapes[] = {
+#define X(ci, co) {ci, co, register_forward<T, ci, co>, register_backward<T, ci, co>},
+    CONV3P_SMALL_SHAPES(X)
+#undef X
+};
+template <typename T> const RegisterShape<T> *register_shape(int cin, int cout)
+{
+    for (const RegisterShape<T> &e : kRegisterShapes<T>)
+        if (e.cin == cin && e.cout == cout) return &e;
+    return nullptr;
+}
+inline bool small_shape(int elem, int cin, int cout)
+{
+#ifdef CONV3P_DEV_SKIP_SMALL   // developer build only (-DCONV3P_DEV_SKIP_SMALL): time the other paths on the models' shapes
+    return false;
+#endif
+    (void)elem;   // fp32 and fp64 (the kernels are templates on T; the planner sends shapes whose LDS does not fit elsewhere)
+    return register_shape<float>(cin, cout) != nullptr;
 }
 
 int zero_async(void *p, size_t bytes, hipStream_t s)
@@ -940,24 +919,6 @@ int zero_async(void *p, size_t bytes, hipStream_t s)
 #define CONV3P_DEEP_SHAPES(X) X(128, 256) X(256, 256) X(256, 128) X(32, 32) X(32, 64) X(32, 128) X(64, 32) X(64, 64) X(64, 128) X(128, 32) X(128, 64) X(128, 128)
 
 inline int deep_pad(int c) { return c <= 32 ? 32 : c <= 64 ? 64 : c <= 128 ? 128 : c <= 256 ? 256 : 0; }
-// padded (Cin, Cout) of a layer the deep path takes, or false
-inline bool deep_class(int elem, int cin, int cout, int &cip, int &cop)
-{
-    if (elem != 4 || cin < 1 || cout < 1) return false;
-    cip = deep_pad(cin);
-    cop = deep_pad(cout);
-    if (cip == 0 || cop == 0) return false;
-    // (padded to the instantiated sizes; 129 .. 256 channels on either side: the 128 -> 256, 256 -> 256 and 256 -> 128 classes)
-#define X(ci, co) if (cip == ci && cop == co) return true;
-    CONV3P_DEEP_SHAPES(X)
-#undef X
-    return false;
-}
-inline bool deep_shape(int elem, int cin, int cout)
-{
-    int a, b;
-    return deep_class(elem, cin, cout, a, b);
-}
 
 constexpr int kDwItems = 1024;        // target number of deep_dw_kernel work items (2 rounds at 2 per CU)
 struct DeepScratch {   // carved from the per-call scratch region
@@ -1039,6 +1000,15 @@ size_t deep_order_bytes(const Dims &d, size_t pair_slots)
 
 void note_deep_order(const Call<float> &c, int which);
 
+// LDS of deep_order_kernel (ngroups: search groups of the layout)
+inline size_t deep_order_lds(int ntap, int ngroups) { return (size_t)(2 + 4 * kOrderR + 64) * ntap * 4 + 256 + (size_t)(2 * 64 * ngroups + 1 + 8) * 4; }
+// LDS of deep_dw_kernel<ci, co, prec> (nh: its column parts; bf16: 2-byte images of X and G)
+inline size_t deep_dw_lds(int ci, int co, int nh, int prec)
+{
+    return prec == kPrecF32 ? (size_t)DEEP_DW_ROWS * (ci + 1) * 4 + (size_t)DEEP_DW_ROWS * (co / nh + 1) * 4 + 256
+                            : (size_t)DEEP_DW_ROWS * (ci + co / nh) * 2 + 256;
+}
+
 template <bool BWD> int launch_deep_order(const Call<float> &c, const DeepScratch &ds)
 {
     const Dims &d = c.d;
@@ -1046,7 +1016,7 @@ template <bool BWD> int launch_deep_order(const Call<float> &c, const DeepScratc
     if (c.order_ok[BWD ? 1 : 0]) return CONV3P_OK;   // built for this geometry by an earlier call, scratch untouched since
     const auto &S = c.L.slot[c.slot];
     const int ng = c.L.ngroups;
-    const size_t lds = (size_t)(2 + 4 * kOrderR + 64) * d.ntap * 4 + 256 + (size_t)(2 * 64 * ng + 1 + 8) * 4;
+    const size_t lds = deep_order_lds(d.ntap, ng);
     if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
     Scope sc(K_DEEP_ORDER, c.s);
     if (BWD) TRY(zero_async(ds.tap_total, 65 * 4, c.s));
@@ -1118,7 +1088,7 @@ int launch_pack_filter_bf16(const Call<float> &c, const float *filter, int kp, i
 
 // CI, CO: the padded instantiation; c.d.Cin / c.d.Cout: the layer's real channel counts
 template <int CI, int CO>
-int deep_forward(const Call<float> &c, const float *input, const float *filter, float *output)
+int deep_forward(const Call<float> &c, const Route &r, const float *input, const float *filter, float *output)
 {
     const Dims &d = c.d;
     const DeepScratch ds = carve_deep(d, (size_t)d.B * c.L.pairs_per_cloud, c.L.partials, 0);
@@ -1135,11 +1105,11 @@ int deep_forward(const Call<float> &c, const float *input, const float *filter, 
     }
     TRY((launch_deep_gemm<CI, CO, false>(c, input, Bm, output, ds, d.Cin, d.Cout)));
     // tiles the deep kernels could not take (pair buffer overflow, non-finite rows): generic kernel, flagged tiles
-    return launch_forward<float, 0, 0>(c, input, filter, output, ds.tile_flag);
+    return launch_forward<float, 0, 0>(c, r.generic_lds, false, input, filter, output, ds.tile_flag);
 }
 
 template <int CI, int CO>
-int deep_backward(const Call<float> &c, const float *grad_out, const float *input, const float *filter,
+int deep_backward(const Call<float> &c, const Route &r, const float *grad_out, const float *input, const float *filter,
                   float *grad_input, float *grad_filter)
 {
     const Dims &d = c.d;
@@ -1154,10 +1124,7 @@ int deep_backward(const Call<float> &c, const float *grad_out, const float *inpu
     TRY((launch_deep_gemm<CO, CI, true>(c, grad_out, ds.wt, grad_input, ds, d.Cout, d.Cin, ds.gbuf, input)));
     {
         constexpr int NH = deep_dw_parts<CI, CO>();
-        // (bf16: 2-byte images of X and G)
-        const size_t lds = c.prec == kPrecF32 ? (size_t)DEEP_DW_ROWS * (CI + 1) * 4 + (size_t)DEEP_DW_ROWS * (CO / NH + 1) * 4 + 256
-                                              : (size_t)DEEP_DW_ROWS * (CI + CO / NH) * 2 + 256;
-        if (lds > kMaxLds) return CONV3P_ERR_UNSUPPORTED;
+        const size_t lds = deep_dw_lds(CI, CO, NH, c.prec);
         Scope sc(c.prec != kPrecF32 ? K_DEEP_DW_BF16 : K_DEEP_DW, c.s);
         auto go = [&](auto kern) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1171,13 +1138,41 @@ int deep_backward(const Call<float> &c, const float *grad_out, const float *inpu
     // flagged tiles: generic kernel adds into the zeroed rows / into its own grad_filter-shaped buffer
     float *extra = ds.partials + (size_t)(kDwItems + 64) * CI * CO;
     TRY(zero_async(extra, nw * 4, c.s));
-    TRY((launch_backward<float, 0, 0>(c, grad_out, input, filter, grad_input, extra, ds.tile_flag)));
+    TRY((launch_backward<float, 0, 0>(c, r.generic_lds, grad_out, input, filter, grad_input, extra, ds.tile_flag)));
     {
         Scope sc(K_REDUCE, c.s);
         hipLaunchKernelGGL(deep_reduce_kernel, dim3((unsigned)((d.Cin * d.Cout + 255) / 256), (unsigned)d.ntap), dim3(256), 0,
                            c.s, ds.partials, ds.tap_rng, extra, CI * CO, CO, d.Cin, d.Cout, grad_filter);
     }
     return hip_ok();
+}
+
+// The matrix-core path's instantiations, by padded (Cin, Cout)
+struct DeepShape {
+    int cip, cop;
+    int dw_parts;   // deep_dw_kernel's column parts
+    int (*forward)(const Call<float> &, const Route &, const float *, const float *, float *);
+    int (*backward)(const Call<float> &, const Route &, const float *, const float *, const float *, float *, float *);
+};
+const DeepShape kDeepShapes[] = {
+#define X(ci, co) {ci, co, deep_dw_parts<ci, co>(), deep_forward<ci, co>, deep_backward<ci, co>},
+    CONV3P_DEEP_SHAPES(X)
+#undef X
+};
+inline const DeepShape *deep_shape(int cip, int cop)
+{
+    for (const DeepShape &e : kDeepShapes)
+        if (e.cip == cip && e.cop == cop) return &e;
+    return nullptr;
+}
+// padded (Cin, Cout) of a layer the matrix-core path takes (fp32; 129 .. 256 channels on either side: the 128 -> 256,
+// 256 -> 256 and 256 -> 128 classes), or false
+inline bool deep_class(int elem, int cin, int cout, int &cip, int &cop)
+{
+    if (elem != 4 || cin < 1 || cout < 1) return false;
+    cip = deep_pad(cin);
+    cop = deep_pad(cout);
+    return cip != 0 && cop != 0 && deep_shape(cip, cop) != nullptr;
 }
 
 // ----------------------------------------------------------------------------- layers of more than 256 channels
@@ -1198,7 +1193,8 @@ inline WideScratch carve_wide(const Call<float> &c, bool forward_only = false)
     // (a forward-only workspace ends after the forward's part of the block scratch: the packs follow that; a cache sized
     // for the backward keeps ONE placement for both passes)
     const size_t slots = (size_t)d.B * c.L.pairs_per_cloud;
-    char *p = reinterpret_cast<char *>(c.L.partials) + up(forward_only && !c.wide_scratch_ok ? deep_forward_bytes(db, slots) : deep_scratch_bytes(db, slots));
+    const bool forward_part = forward_only && c.scratch < wide_scratch_bytes(d, slots);
+    char *p = reinterpret_cast<char *>(c.L.partials) + up(forward_part ? deep_forward_bytes(db, slots) : deep_scratch_bytes(db, slots));
     WideScratch w{};
     w.xp = reinterpret_cast<float *>(p); p += up(rows * kWideBlk * 4);
     w.yp = reinterpret_cast<float *>(p); p += up(rows * kWideBlk * 4);
@@ -1228,7 +1224,7 @@ inline int wide_pack_filter(const Call<float> &c, const float *filter, int k0, i
 // out[:, c0 .. c0 + cw) = sum over the input-channel blocks of conv(input[:, k0 .. k0 + kw), filter[:, k-block, c-block]):
 // every block runs on the matrix-core kernels from packed copies (the same geometry and record order for all of them),
 // the blocks' results are added in ascending k0 -- deterministic.
-int wide_forward(const Call<float> &c, const float *input, const float *filter, float *output)
+int wide_forward(const Call<float> &c, const Route &r, const float *input, const float *filter, float *output)
 {
     const Dims &d = c.d;
     const size_t rows = (size_t)d.B * d.N;
@@ -1246,11 +1242,7 @@ int wide_forward(const Call<float> &c, const float *input, const float *filter, 
             cp.act = false;
             cp.order_ok[0] = have_order;
             set_ld(cp, nullptr, kwp, cwp);
-            int rc = CONV3P_ERR_UNSUPPORTED;
-#define X(ci, co) if (kwp == ci && cwp == co) rc = deep_forward<ci, co>(cp, w.xp, w.wp, w.zp);
-            CONV3P_DEEP_SHAPES(X)
-#undef X
-            if (rc != CONV3P_OK) return rc;
+            TRY(deep_shape(kwp, cwp)->forward(cp, r, w.xp, w.wp, w.zp));
             have_order = true;
             if (k0 == 0)
                 hipLaunchKernelGGL(copy_cols_kernel<float>, dim3(grid_1d(rows * cw)), dim3(256), 0, c.s, w.zp, output + c0, rows, cw,
@@ -1265,8 +1257,8 @@ int wide_forward(const Call<float> &c, const float *input, const float *filter, 
 
 // grad_input[:, k-block] = sum over the output-channel blocks (ascending c0) of the block's grad_input; every
 // (k-block, c-block) pair gives its own block of grad_filter.
-int wide_backward(const Call<float> &c, const float *grad_out, const float *input, const float *filter, float *grad_input,
-                  float *grad_filter)
+int wide_backward(const Call<float> &c, const Route &r, const float *grad_out, const float *input, const float *filter,
+                  float *grad_input, float *grad_filter)
 {
     const Dims &d = c.d;
     const size_t rows = (size_t)d.B * d.N;
@@ -1287,11 +1279,7 @@ int wide_backward(const Call<float> &c, const float *grad_out, const float *inpu
             cp.addend = nullptr;
             cp.order_ok[1] = have_order;
             set_ld(cp, nullptr, kwp, cwp);
-            int rc = CONV3P_ERR_UNSUPPORTED;
-#define X(ci, co) if (kwp == ci && cwp == co) rc = deep_backward<ci, co>(cp, w.yp, w.xp, w.wp, w.zp, w.dwp);
-            CONV3P_DEEP_SHAPES(X)
-#undef X
-            if (rc != CONV3P_OK) return rc;
+            TRY(deep_shape(kwp, cwp)->backward(cp, r, w.yp, w.xp, w.wp, w.zp, w.dwp));
             have_order = true;
             if (c0 == 0)
                 hipLaunchKernelGGL(copy_cols_kernel<float>, dim3(grid_1d(rows * kw)), dim3(256), 0, c.s, w.zp, grad_input + k0, rows,
@@ -1356,7 +1344,7 @@ inline Call<double> f64_block_call(const Call<double> &c, int bki, int bco)
 }
 
 // out[:, c-block] = sum over the input-channel blocks (ascending) of the block kernel's result: deterministic
-int f64_blocked_forward(const Call<double> &c, const double *input, const double *filter, double *output)
+int f64_blocked_forward(const Call<double> &c, const Route &r, const double *input, const double *filter, double *output)
 {
     const Dims &d = c.d;
     const size_t rows = (size_t)d.B * d.N;
@@ -1368,7 +1356,7 @@ int f64_blocked_forward(const Call<double> &c, const double *input, const double
         for (int c0 = 0; c0 < d.Cout; c0 += kF64FwdCo) {
             const int cw = d.Cout - c0 < kF64FwdCo ? d.Cout - c0 : kF64FwdCo;
             TRY(f64_pack_filter(c, filter, k0, kw, c0, cw, w.wp, kF64FwdKi, kF64FwdCo));
-            TRY((launch_forward<double, kF64FwdKi, kF64FwdCo>(cp, w.xp, w.wp, w.yp)));
+            TRY((launch_forward<double, kF64FwdKi, kF64FwdCo>(cp, r.lds, false, w.xp, w.wp, w.yp)));
             if (k0 == 0)
                 hipLaunchKernelGGL(copy_cols_kernel<double>, dim3(grid_1d(rows * cw)), dim3(256), 0, c.s, w.yp, output + c0, rows, cw,
                                    kF64FwdCo, d.Cout);
@@ -1383,8 +1371,8 @@ int f64_blocked_forward(const Call<double> &c, const double *input, const double
 // grad_input[:, k-block] = sum over the output-channel blocks (ascending) of the block's grad_input; every block pair
 // gives its own block of grad_filter (per-workgroup partials, reduced in fixed order).  BCO: output channels per block.
 template <int BCO>
-int f64_blocked_backward_co(const Call<double> &c, const double *grad_out, const double *input, const double *filter,
-                            double *grad_input, double *grad_filter)
+int f64_blocked_backward_co(const Call<double> &c, const Route &r, const double *grad_out, const double *input,
+                            const double *filter, double *grad_input, double *grad_filter)
 {
     const Dims &d = c.d;
     const size_t rows = (size_t)d.B * d.N, nwb = (size_t)d.ntap * kF64BwdKi * BCO;
@@ -1398,7 +1386,7 @@ int f64_blocked_backward_co(const Call<double> &c, const double *grad_out, const
             const int cw = d.Cout - c0 < BCO ? d.Cout - c0 : BCO;
             TRY(f64_pack_rows(c, grad_out + c0, d.Cout, w.yp, rows, cw, BCO));
             TRY(f64_pack_filter(c, filter, k0, kw, c0, cw, w.wp, kF64BwdKi, BCO));
-            TRY((launch_backward<double, kF64BwdKi, BCO>(cp, w.yp, w.xp, w.wp, w.zp, w.parts)));
+            TRY((launch_backward<double, kF64BwdKi, BCO>(cp, r.lds, w.yp, w.xp, w.wp, w.zp, w.parts)));
             {
                 Scope sc(K_REDUCE, c.s);
                 hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)((nwb + kReduceW - 1) / kReduceW)), dim3(1024), 0, c.s, w.parts,
@@ -1417,18 +1405,13 @@ int f64_blocked_backward_co(const Call<double> &c, const double *grad_out, const
     }
     return hip_ok();
 }
-// Blocks of kF64BwdCo output channels, else 4, else 2: the widest whose dense G fits LDS (16 x 8 up to 28 taps, 16 x 4 up
-// to 57, 16 x 2 up to 115), chosen before anything is enqueued; CONV3P_ERR_UNSUPPORTED past that.
-int f64_blocked_backward(const Call<double> &c, const double *grad_out, const double *input, const double *filter,
-                         double *grad_input, double *grad_filter)
+// r.co: output channels per block, the widest whose dense G fits LDS (plan_backward)
+int f64_blocked_backward(const Call<double> &c, const Route &r, const double *grad_out, const double *input,
+                         const double *filter, double *grad_input, double *grad_filter)
 {
-    if (dense_backward_lds<double>(c.st, kF64BwdKi, kF64BwdCo) <= kMaxLds)
-        return f64_blocked_backward_co<kF64BwdCo>(c, grad_out, input, filter, grad_input, grad_filter);
-    if (kF64BwdCo > 4 && dense_backward_lds<double>(c.st, kF64BwdKi, 4) <= kMaxLds)
-        return f64_blocked_backward_co<4>(c, grad_out, input, filter, grad_input, grad_filter);
-    if (kF64BwdCo > 2 && dense_backward_lds<double>(c.st, kF64BwdKi, 2) <= kMaxLds)
-        return f64_blocked_backward_co<2>(c, grad_out, input, filter, grad_input, grad_filter);
-    return CONV3P_ERR_UNSUPPORTED;
+    if (r.co == kF64BwdCo) return f64_blocked_backward_co<kF64BwdCo>(c, r, grad_out, input, filter, grad_input, grad_filter);
+    if (r.co == 4) return f64_blocked_backward_co<4>(c, r, grad_out, input, filter, grad_input, grad_filter);
+    return f64_blocked_backward_co<2>(c, r, grad_out, input, filter, grad_input, grad_filter);
 }
 
 int buf_check(const void *p, size_t have, size_t need)
@@ -1436,6 +1419,182 @@ int buf_check(const void *p, size_t have, size_t need)
     if (need == 0) return CONV3P_OK;
     if (!p || (reinterpret_cast<uintptr_t>(p) % kAlign) != 0 || have < need) return CONV3P_ERR_WORKSPACE;
     return CONV3P_OK;
+}
+
+// ----------------------------------------------------------------------------- the planners
+// Can the matrix-core kernels take (cip x cop) blocks of this call?  kreal: real width of deep_gemm's A rows (stage 1
+// addresses them by 32-bit offsets)
+inline bool deep_fits(const Dims &d, const PlanArgs &a, int cip, int cop, int kreal, bool backward)
+{
+    if (d.ntap > 64 || deep_order_lds(d.ntap, a.ngroups) > kMaxLds) return false;   // (64-bit tap sets)
+    if ((size_t)d.N * (size_t)kreal * 4 > 0xFFFFFFFFull) return false;
+    return !backward || deep_dw_lds(cip, cop, deep_shape(cip, cop)->dw_parts, a.prec) <= kMaxLds;
+}
+// ... every block of a layer of more than 256 channels (wide_forward / wide_backward)
+inline bool wide_fits(const Dims &d, const PlanArgs &a, bool backward)
+{
+    for (int k0 = 0; k0 < d.Cin; k0 += kWideBlk)
+        for (int c0 = 0; c0 < d.Cout; c0 += kWideBlk) {
+            const int kwp = wide_pad(std::min(kWideBlk, d.Cin - k0)), cwp = wide_pad(std::min(kWideBlk, d.Cout - c0));
+            if (!deep_fits(d, a, kwp, cwp, backward ? cwp : kwp, backward)) return false;
+        }
+    return true;
+}
+
+// The forward's route.  Register shapes: forward_kernel while its filter copy fits LDS (fp32 shapes of >= 16 inputs and
+// <= 16 outputs: transform + gather where the buffer has room for Z, which is optional); past that fp32 takes the
+// matrix-core kernels (up to 64 taps) and fp64 its channel blocks.  Other shapes: fp32 on the matrix-core kernels, in
+// blocks above 256 channels; fp64 in channel blocks.  A family whose kernels do not fit, or whose scratch the buffer
+// does not have, leaves the call to the generic kernels; strided tensors only the register kernels take.
+template <typename T> Route plan_forward(const Dims &d, const Stencil<T> &st, const PlanArgs &a)
+{
+    constexpr int elem = (int)sizeof(T);
+    Route g;
+    g.lds = g.generic_lds = forward_lds<T>(st, 0, 0);
+    if (g.lds > kMaxLds) g.family = Family::Unsupported;
+    Route un = g;
+    un.family = Family::Unsupported;
+    Route r = g;
+    int cip = 0, cop = 0;
+    const bool small = small_shape(elem, d.Cin, d.Cout);
+    if (small) {
+        r.family = Family::Register;
+        if constexpr (elem == 4) {
+#ifndef CONV3P_DEV_NO_TAP_FORWARD   // developer A/B build
+            if (d.Cin >= 16 && d.Cin % 4 == 0 && d.Cout <= 16 && tap_forward_bytes(d) <= a.have) {
+                r.tap = true;
+                r.lds = tap_gather_lds(st, d.Cout);
+                r.scratch = tap_forward_bytes(d);
+                return r;
+            }
+#endif
+        }
+        r.lds = forward_lds<T>(st, d.Cin, d.Cout);
+        if (r.lds <= kMaxLds) return r;
+        if (a.strided) return un;
+        if (elem == 4 && d.ntap > 64) return g;
+    } else if (a.strided) {
+        return un;
+    }
+    r = g;
+    if (deep_class(elem, d.Cin, d.Cout, cip, cop)) {
+        r.family = deep_fits(d, a, cip, cop, d.Cin, false) ? Family::MatrixCore : g.family;
+        r.cip = cip;
+        r.cop = cop;
+        r.scratch = deep_forward_bytes(d, a.pair_slots);
+        r.mandatory = small ? 0 : r.scratch;
+    } else if (wide_shape(elem, d.Cin, d.Cout)) {
+        r.family = wide_fits(d, a, false) ? Family::Wide : g.family;
+        r.scratch = wide_scratch_bytes(d, a.pair_slots, true);
+    } else if (elem == 8 && d.Cin >= 1 && d.Cout >= 1) {
+        const size_t lds = forward_lds<T>(st, kF64FwdKi, kF64FwdCo);
+        if (lds <= kMaxLds) {
+            r.family = Family::F64Blocks;
+            r.lds = lds;
+        }
+        r.scratch = f64_blocked_bytes(d);
+    }
+    if (r.scratch > a.have) r.family = g.family, r.lds = g.lds;
+    return r;
+}
+
+// The backward's route.  Register shapes: their register kernels while the dense G or the populated rows fit LDS (the fp64
+// 36 -> 13 head in three column passes of them after that); past that fp32 takes the matrix-core kernels (up to 64
+// taps) and fp64 its channel blocks.  Other shapes as in the forward.  Scratch: at least the grad_filter partials of the
+// generic kernels, the fallback of every family (register shapes: one per workgroup, as their register kernels take).
+template <typename T> Route plan_backward(const Dims &d, const Stencil<T> &st, const PlanArgs &a)
+{
+    constexpr int elem = (int)sizeof(T);
+    const bool small = small_shape(elem, d.Cin, d.Cout);
+    const int grid = (int)grid_of(make_blockmap(d));
+    Route g;
+    g.lds = g.generic_lds = dense_backward_lds<T>(st, 0, 0);
+    if (g.lds > kMaxLds) g.family = Family::Unsupported;
+    g.slots = generic_slots(d, elem);
+    g.scratch = (size_t)d.ntap * d.Cin * d.Cout * (size_t)(small ? grid : g.slots) * elem;
+    if (small) g.slots = std::min(g.slots, grid);
+    Route un = g;
+    un.family = Family::Unsupported;
+    Route r = g;
+    int cip = 0, cop = 0;
+    if (small) {
+        const size_t dense = dense_backward_lds<T>(st, d.Cin, d.Cout);
+        size_t slds = 0;
+        int cap = 0;
+#ifndef CONV3P_DEV_DENSE_BACKWARD   // developer A/B build: always the dense-G kernel
+        if (elem == 4) cap = sparse_cap<T>(st, d.Cin, d.Cout, slds);
+#endif
+        if (dense <= kMaxLds || cap > 0) {
+            r.family = Family::Register;
+            r.lds = dense;
+            r.slots = grid;
+            r.self_reduces = false;
+            // Populated rows: layers of >= 16 inputs, and filters whose dense G does not fit, always.  Narrow dilated
+            // layers: on the caller's SPARSE hint alone; on neither hint the regime word picks one of the two kernels on
+            // the device; on the DENSE hint the dense G.
+            if (cap > 0 && !(d.Cin < 16 && a.dense_hint && dense <= kMaxLds)) {
+                r.cap = cap;
+                r.sparse_lds = slds;
+                r.regime = d.Cin < 16 && !a.sparse_hint && dense <= kMaxLds;
+            }
+            return r;
+        }
+        // (fp64 36 -> 13: the dense G of 5 output channels fits up to 33 taps)
+        if (elem == 8 && d.Cin == 36 && d.Cout == 13 && dense_backward_lds<T>(st, 36, 5) <= kMaxLds) {
+            r.family = Family::Split36x13;
+            r.lds = dense_backward_lds<T>(st, 36, 5);
+            r.lds4 = dense_backward_lds<T>(st, 36, 4);
+            return r;
+        }
+        if (a.strided) return un;
+        if (elem == 4 && d.ntap > 64) return g;
+    } else if (a.strided) {
+        return un;
+    }
+    if (deep_class(elem, d.Cin, d.Cout, cip, cop)) {
+        r.family = deep_fits(d, a, cip, cop, d.Cout, true) ? Family::MatrixCore : g.family;
+        r.cip = cip;
+        r.cop = cop;
+        r.scratch = std::max(g.scratch, deep_scratch_bytes(d, a.pair_slots));
+    } else if (wide_shape(elem, d.Cin, d.Cout)) {
+        r.family = wide_fits(d, a, true) ? Family::Wide : g.family;
+        r.scratch = std::max(g.scratch, wide_scratch_bytes(d, a.pair_slots));
+    } else if (elem == 8 && d.Cin >= 1 && d.Cout >= 1) {
+        // blocks of kF64BwdCo output channels, else 4, else 2: the widest whose dense G fits (16 x 8 up to 28 taps, 16 x 4
+        // up to 57, 16 x 2 up to 115)
+        for (int co : {kF64BwdCo, 4, 2})
+            if (co <= kF64BwdCo && dense_backward_lds<T>(st, kF64BwdKi, co) <= kMaxLds) {
+                r.family = Family::F64Blocks;
+                r.co = co;
+                r.lds = dense_backward_lds<T>(st, kF64BwdKi, co);
+                break;
+            }
+        r.scratch = std::max(g.scratch, f64_blocked_bytes(d));
+    }
+    if (r.scratch > a.have) r.family = g.family, r.lds = g.lds;
+    return r;
+}
+
+// Workspace sizes: the planners on the undilated stencil of the call's extents -- what the workspace query (no stride
+// argument) and the call itself both know -- with no hints and room for everything.  ppp: pair slots per point of the
+// buffer (a cache may be configured with fewer than the default).  (A dilation large enough to tip a register shape past
+// its fit on its own finds the scratch of the next family only in a cache: a stateless call takes the generic kernels.)
+size_t backward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPerPoint)
+{
+    PlanArgs a;
+    a.pair_slots = (size_t)d.B * d.N * (size_t)ppp;
+    return elem == 4 ? plan_backward<float>(d, undilated_stencil<float>(d), a).scratch
+                     : plan_backward<double>(d, undilated_stencil<double>(d), a).scratch;
+}
+// mandatory_only: what the forward cannot run without (a persistent cache sized for narrower layers is not refused for
+// the optional rest)
+size_t forward_scratch_bytes(const Dims &d, int elem, int ppp = kDefaultPairsPerPoint, bool mandatory_only = false)
+{
+    PlanArgs a;
+    a.pair_slots = (size_t)d.B * d.N * (size_t)ppp;
+    const Route r = elem == 4 ? plan_forward<float>(d, undilated_stencil<float>(d), a)
+                              : plan_forward<double>(d, undilated_stencil<double>(d), a);
+    return mandatory_only ? r.mandatory : r.scratch;
 }
 
 // ----------------------------------------------------------------------------- cache (host side)
@@ -1491,34 +1650,41 @@ struct Where {
     size_t scratch_cap;   // persistent: bytes of scratch the layout was sized with
     int flags;            // CONV3P_CACHE_* of this call
 };
+inline int call_prec(const Where &wh) { return wh.persistent && (wh.flags & CONV3P_CACHE_MATMUL_BF16) != 0 ? kPrecBf16 : kPrecF32; }
 
+// What a call's route depends on besides its shape and stencil.  scratch: bytes of per-call scratch of a stateless call
+template <typename T> PlanArgs plan_args(const Dims &d, const Where &wh, bool strided, size_t scratch)
+{
+    const Layout<T> L = carve<T>(d.B, d.N, d.ntiles, wh.persistent ? wh.ntap_max : d.ntap, 1, wh.ppp, 0, nullptr);
+    PlanArgs a;
+    a.strided = strided;
+    a.sparse_hint = wh.persistent && (wh.flags & CONV3P_CACHE_SPARSE_NEIGHBOURHOODS) != 0;
+    a.dense_hint = wh.persistent && !a.sparse_hint && (wh.flags & CONV3P_CACHE_DENSE_NEIGHBOURHOODS) != 0;
+    a.prec = call_prec(wh);
+    a.pair_slots = (size_t)d.B * L.pairs_per_cloud;
+    a.ngroups = L.ngroups;
+    a.have = wh.persistent ? wh.scratch_cap : scratch;
+    return a;
+}
+
+// keep_orders: the route may find the matrix-core path's record orders left in the scratch region
 template <typename T>
 int begin_call(Call<T> &c, const Dims &d, const int32_t *stride, T voxel, size_t scratch, const Where &wh,
-               hipStream_t s)
+               hipStream_t s, bool keep_orders = false)
 {
     c.d = d;
     c.st = make_stencil<T>(d, stride, voxel);
     c.s = s;
-    c.sparse_hint = wh.persistent && (wh.flags & CONV3P_CACHE_SPARSE_NEIGHBOURHOODS) != 0;
-    c.dense_hint = wh.persistent && !c.sparse_hint && (wh.flags & CONV3P_CACHE_DENSE_NEIGHBOURHOODS) != 0;
     // (read by deep_forward / deep_backward only: every other path ignores the bit)
-    c.prec = wh.persistent && (wh.flags & CONV3P_CACHE_MATMUL_BF16) != 0 ? kPrecBf16 : kPrecF32;
+    c.prec = call_prec(wh);
     const int ntap_max = wh.persistent ? wh.ntap_max : d.ntap;
     if (d.ntap > ntap_max) return CONV3P_ERR_WORKSPACE;
     if (wh.persistent && scratch > wh.scratch_cap) return CONV3P_ERR_WORKSPACE;
-    c.L = carve<T>(d.B, d.N, d.ntiles, ntap_max, wh.nslots, wh.ppp, wh.persistent ? wh.scratch_cap : scratch, wh.buf);
+    c.scratch = wh.persistent ? wh.scratch_cap : scratch;
+    c.L = carve<T>(d.B, d.N, d.ntiles, ntap_max, wh.nslots, wh.ppp, c.scratch, wh.buf);
     TRY(buf_check(wh.buf, wh.bytes, c.L.bytes));
-    {
-        const size_t have = wh.persistent ? wh.scratch_cap : scratch;
-        c.deep_scratch_ok = deep_shape((int)sizeof(T), d.Cin, d.Cout) &&
-                            have >= deep_scratch_bytes(d, (size_t)d.B * c.L.pairs_per_cloud);
-        c.tap_scratch_ok = tap_forward_shape((int)sizeof(T), d.Cin, d.Cout) && have >= tap_forward_bytes(d);
-        c.wide_scratch_ok = wide_shape((int)sizeof(T), d.Cin, d.Cout) && have >= wide_scratch_bytes(d, (size_t)d.B * c.L.pairs_per_cloud);
-        c.deep_fwd_ok = deep_shape((int)sizeof(T), d.Cin, d.Cout) && have >= deep_forward_bytes(d, (size_t)d.B * c.L.pairs_per_cloud);
-        c.wide_fwd_ok = wide_shape((int)sizeof(T), d.Cin, d.Cout) && have >= wide_scratch_bytes(d, (size_t)d.B * c.L.pairs_per_cloud, true);
-        // (register-path shapes too: the blocks take the filters their own kernels cannot)
-        c.f64_scratch_ok = sizeof(T) == 8 && d.Cin >= 1 && d.Cout >= 1 && have >= f64_blocked_bytes(d);
-    }
+    // (a forward's route needs only part of the matrix-core scratch: the orders count only where all of it is there)
+    keep_orders = keep_orders && c.scratch >= deep_scratch_bytes(d, (size_t)d.B * c.L.pairs_per_cloud);
     const unsigned long long tag = stencil_tag(d, stride, (double)voxel, (int)sizeof(T));
     if (!wh.persistent) {
         c.slot = 0;
@@ -1570,7 +1736,7 @@ int begin_call(Call<T> &c, const Dims &d, const int32_t *stride, T voxel, size_t
     c.cache_key = wh.buf;
     c.gen = h.gen;
     for (int w = 0; w < 2; ++w)
-        c.order_ok[w] = c.skip_search && c.deep_scratch_ok && h.order_slot[w] == slot && h.order_gen[w] == h.gen && h.gen != 0;
+        c.order_ok[w] = c.skip_search && keep_orders && h.order_slot[w] == slot && h.order_gen[w] == h.gen && h.gen != 0;
     // a call with channels may use the scratch region for anything (partials, Z, ...): the orders count as gone unless
     // the matrix-core path, which leaves them in place, says otherwise (deep_forward / deep_backward re-note them)
     if (d.Cin > 0) h.order_gen[0] = h.order_gen[1] = 0;
@@ -1662,47 +1828,30 @@ int forward_impl(const T *points, const T *input, const T *filter, const int32_t
     Call<T> c;
     c.act = act;
     set_ld(c, ldp, Cin, Cout);
-    if (c.strided && !small_shape((int)sizeof(T), Cin, Cout)) return CONV3P_ERR_UNSUPPORTED;   // dense tensors only
-    TRY(begin_call<T>(c, d, stride, voxel, forward_scratch_bytes(d, (int)sizeof(T), wh.ppp, wh.persistent), wh, s));
+    const size_t scratch = forward_scratch_bytes(d, (int)sizeof(T), wh.ppp, wh.persistent);
+    const Route r = plan_forward<T>(d, make_stencil<T>(d, stride, voxel), plan_args<T>(d, wh, c.strided, scratch));
+    if (r.family == Family::Unsupported) return CONV3P_ERR_UNSUPPORTED;   // (before anything is launched or recorded)
+    TRY(begin_call<T>(c, d, stride, voxel, scratch, wh, s, r.family == Family::MatrixCore));
     TRY(run_prep<T>(points, c));
     TRY(run_cloud_min<T>(points, c));
     TRY(run_search<T>(c, c.L.slot[c.slot].count, true));
-#define X(ci, co)                                                                                    \
-    if (Cin == ci && Cout == co && small_shape((int)sizeof(T), Cin, Cout)) {                         \
-        int rc = launch_forward<T, ci, co>(c, input, filter, output);                                \
-        if (rc != CONV3P_ERR_UNSUPPORTED) return rc;                                                 \
+    switch (r.family) {
+    case Family::Register:   // (SELU fused into the kernels)
+        return register_shape<T>(Cin, Cout)->forward(c, r, input, filter, output);
+    case Family::MatrixCore:
+        if constexpr (sizeof(T) == 4) TRY(deep_shape(r.cip, r.cop)->forward(c, r, input, filter, output));
+        break;
+    case Family::Wide:
+        if constexpr (sizeof(T) == 4) TRY(wide_forward(c, r, input, filter, output));
+        break;
+    case Family::F64Blocks:
+        if constexpr (sizeof(T) == 8) TRY(f64_blocked_forward(c, r, input, filter, output));
+        break;
+    default:
+        TRY(zero_async(output, out_elems * sizeof(T), s));   // .cpp:451
+        TRY((launch_forward<T, 0, 0>(c, r.lds, false, input, filter, output)));
+        break;
     }
-    CONV3P_SMALL_SHAPES(X)
-#undef X
-    if (c.strided) return CONV3P_ERR_UNSUPPORTED;   // (a register-path shape whose LDS did not fit)
-    if constexpr (sizeof(T) == 4) {
-        int cip = 0, cop = 0;
-        if (c.deep_fwd_ok && deep_class(4, Cin, Cout, cip, cop)) {
-#define X(ci, co)                                                                                    \
-    if (cip == ci && cop == co) {                                                                    \
-        int rc = deep_forward<ci, co>(c, input, filter, output);                                     \
-        if (rc != CONV3P_ERR_UNSUPPORTED) return rc != CONV3P_OK || !act ? rc : selu_impl<T>(output, output, out_elems, stream); \
-    }
-            CONV3P_DEEP_SHAPES(X)
-#undef X
-        }
-    }
-    if constexpr (sizeof(T) == 4) {
-        if (c.wide_fwd_ok) {   // more than 256 channels on a side: blocks of <= 256 x 256 on the matrix-core kernels
-            const int rc = wide_forward(c, input, filter, output);
-            if (rc != CONV3P_ERR_UNSUPPORTED) return rc != CONV3P_OK || !act ? rc : selu_impl<T>(output, output, out_elems, stream);
-        }
-    }
-    if constexpr (sizeof(T) == 8) {
-        // fp64 outside the register-path shapes, and register-path shapes whose forward_kernel does not fit LDS (36 -> 13
-        // past 31 taps): 16 x 8 channel blocks on <double, 16, 8>
-        if (c.f64_scratch_ok && !c.strided) {
-            const int rc = f64_blocked_forward(c, input, filter, output);
-            if (rc != CONV3P_ERR_UNSUPPORTED) return rc != CONV3P_OK || !act ? rc : selu_impl<T>(output, output, out_elems, stream);
-        }
-    }
-    TRY(zero_async(output, out_elems * sizeof(T), s));                   // .cpp:451
-    TRY((launch_forward<T, 0, 0>(c, input, filter, output)));
     return act ? selu_impl<T>(output, output, out_elems, stream) : CONV3P_OK;   // paths without a fused epilogue
 }
 
@@ -1823,12 +1972,13 @@ int prepare_multi_impl(const T *points, const int32_t *strides, int K, T voxel, 
 // output channels: grad_out is read through its row stride from a column offset, the filter block is packed into
 // scratch, every pass adds its grad_input contribution to the previous ones (the SELU epilogue, if any, in the last
 // pass), and the grad_filter blocks are reduced and scattered back.  Deterministic like the single-pass kernel.
+// r.lds, r.lds4: the kernel's LDS for the 5- and 4-column passes.
 template <typename T>
-int backward_split_36_13(const Call<T> &c, const T *grad_out, const T *input, const T *filter, T *grad_input,
-                         T *grad_filter)
+int backward_split_36_13(const Call<T> &c, const Route &r, const T *grad_out, const T *input, const T *filter,
+                         T *grad_input, T *grad_filter)
 {
     if constexpr (sizeof(T) != 8) {
-        return CONV3P_ERR_UNSUPPORTED;
+        return CONV3P_ERR_UNSUPPORTED;   // (never planned)
     } else {
         const Dims &d = c.d;
         const int widths[3] = {5, 4, 4};
@@ -1849,9 +1999,8 @@ int backward_split_36_13(const Call<T> &c, const T *grad_out, const T *input, co
             cp.accum = p > 0;
             cp.act = c.act && p == 2;
             cp.addend = p == 2 ? c.addend : nullptr;
-            const int rc = cw == 5 ? launch_backward<T, 36, 5>(cp, grad_out + c0, input, Wp, grad_input, region)
-                                   : launch_backward<T, 36, 4>(cp, grad_out + c0, input, Wp, grad_input, region);
-            if (rc != CONV3P_OK) return rc;
+            TRY((cw == 5 ? launch_backward<T, 36, 5>(cp, r.lds, grad_out + c0, input, Wp, grad_input, region)
+                         : launch_backward<T, 36, 4>(cp, r.lds4, grad_out + c0, input, Wp, grad_input, region)));
             {
                 Scope sc(K_REDUCE, c.s);
                 hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3((unsigned)((nwp + kReduceW - 1) / kReduceW)), dim3(1024), 0, c.s, region,
@@ -1892,81 +2041,47 @@ int backward_impl(const T *grad_out, const T *points, const T *input, const T *f
     c.act = act;
     c.addend = addend;
     set_ld(c, ldp, Cin, Cout);
-    if (c.strided && !small_shape((int)sizeof(T), Cin, Cout)) return CONV3P_ERR_UNSUPPORTED;   // dense tensors only
-    TRY(begin_call<T>(c, d, stride, voxel, backward_scratch_bytes(d, (int)sizeof(T), wh.ppp), wh, s));
+    const size_t scratch = backward_scratch_bytes(d, (int)sizeof(T), wh.ppp);
+    const Route r = plan_backward<T>(d, make_stencil<T>(d, stride, voxel), plan_args<T>(d, wh, c.strided, scratch));
+    if (r.family == Family::Unsupported) return CONV3P_ERR_UNSUPPORTED;   // (before anything is launched or recorded)
+    TRY(begin_call<T>(c, d, stride, voxel, scratch, wh, s, r.family == Family::MatrixCore));
     TRY(run_prep<T>(points, c));
     TRY(run_cloud_min<T>(points, c));
     TRY(run_search<T>(c, c.L.slot[c.slot].count, true));
-    int rc = CONV3P_ERR_UNSUPPORTED;
-    int nslots = (int)grid_of(make_blockmap(d));
-    T *region = defer ? defer->region : nullptr;
-#define X(ci, co)                                                                                    \
-    if (Cin == ci && Cout == co && small_shape((int)sizeof(T), Cin, Cout))                           \
-        rc = launch_backward<T, ci, co>(c, grad_out, input, filter, grad_input, region);
-    CONV3P_SMALL_SHAPES(X)
-#undef X
-    if (defer && rc == CONV3P_OK) {
-        defer->job = ReduceJob<T>{region, grad_filter, nslots, (unsigned)nw};
+    // the register kernels leave per-workgroup grad_filter partials: in the stack's region when it reduces them later
+    T *partials = defer && !r.self_reduces ? defer->region : c.L.partials;
+    switch (r.family) {
+    case Family::Register:   // (SELU fused into the kernels)
+        TRY(register_shape<T>(Cin, Cout)->backward(c, r, grad_out, input, filter, grad_input, partials));
+        break;
+    case Family::Split36x13:   // (SELU fused into its last pass)
+        return backward_split_36_13<T>(c, r, grad_out, input, filter, grad_input, grad_filter);
+    case Family::MatrixCore:
+        if constexpr (sizeof(T) == 4) TRY(deep_shape(r.cip, r.cop)->backward(c, r, grad_out, input, filter, grad_input, grad_filter));
+        break;
+    case Family::Wide:
+        if constexpr (sizeof(T) == 4) TRY(wide_backward(c, r, grad_out, input, filter, grad_input, grad_filter));
+        break;
+    case Family::F64Blocks:
+        if constexpr (sizeof(T) == 8) TRY(f64_blocked_backward(c, r, grad_out, input, filter, grad_input, grad_filter));
+        break;
+    default:
+        TRY(zero_async(grad_input, dx_elems * sizeof(T), s));
+        TRY(zero_async(c.L.partials, nw * (size_t)r.slots * sizeof(T), s));
+        TRY((launch_backward<T, 0, 0>(c, r.lds, grad_out, input, filter, grad_input, c.L.partials, nullptr, r.slots)));
+        break;
+    }
+    if (defer && !r.self_reduces) {   // reduced later, together with the stack's other layers
+        defer->job = ReduceJob<T>{partials, grad_filter, r.slots, (unsigned)nw};
         return CONV3P_OK;
     }
-    // (the fp64 column split and channel blocks below reduce and write grad_filter themselves: under `defer` they leave
-    // defer->job empty, as the matrix-core path does, and the stack's reduction skips the layer)
-    if (rc == CONV3P_ERR_UNSUPPORTED && sizeof(T) == 8 && Cin == 36 && Cout == 13 &&
-        small_shape((int)sizeof(T), Cin, Cout)) {
-        // (filters of more than 33 taps do not fit LDS even in column blocks: its first launch says so before anything is
-        // written, and the channel blocks below take the call -- found by tools/fuzz_gpu.py, 3 x 5 x 3 taps in fp64)
-        const int src = backward_split_36_13<T>(c, grad_out, input, filter, grad_input, grad_filter);
-        if (src != CONV3P_ERR_UNSUPPORTED) return src;
-    }
-    if constexpr (sizeof(T) == 4) {
-        int cip = 0, cop = 0;
-        // (also the register-path shapes whose register backward cannot take the filter: 36 -> 13 with 33 .. 64 taps)
-        if (rc == CONV3P_ERR_UNSUPPORTED && c.deep_scratch_ok && !c.strided && deep_class(4, Cin, Cout, cip, cop)) {
-#define X(ci, co)                                                                                    \
-    if (cip == ci && cop == co) {                                                                    \
-        int drc = deep_backward<ci, co>(c, grad_out, input, filter, grad_input, grad_filter);        \
-        if (drc != CONV3P_ERR_UNSUPPORTED)                                                           \
-            return drc != CONV3P_OK || !act ? drc                                                    \
-                       : selu_grad_impl<T>(input, grad_input, addend, grad_input, (size_t)B * N, Cin, nullptr, stream); \
-    }
-            CONV3P_DEEP_SHAPES(X)
-#undef X
-        }
-    }
-    if constexpr (sizeof(T) == 4) {
-        if (rc == CONV3P_ERR_UNSUPPORTED && c.wide_scratch_ok) {
-            const int wrc = wide_backward(c, grad_out, input, filter, grad_input, grad_filter);
-            if (wrc != CONV3P_ERR_UNSUPPORTED)
-                return wrc != CONV3P_OK || !act ? wrc
-                           : selu_grad_impl<T>(input, grad_input, addend, grad_input, (size_t)B * N, Cin, nullptr, stream);
-        }
-    }
-    if constexpr (sizeof(T) == 8) {
-        if (rc == CONV3P_ERR_UNSUPPORTED && c.f64_scratch_ok && !c.strided) {
-            const int brc = f64_blocked_backward(c, grad_out, input, filter, grad_input, grad_filter);
-            if (brc != CONV3P_ERR_UNSUPPORTED)
-                return brc != CONV3P_OK || !act ? brc
-                           : selu_grad_impl<T>(input, grad_input, addend, grad_input, (size_t)B * N, Cin, nullptr, stream);
-        }
-    }
-    bool generic = false;
-    if (rc == CONV3P_ERR_UNSUPPORTED && c.strided) return rc;
-    if (rc == CONV3P_ERR_UNSUPPORTED) {
-        generic = true;
-        nslots = generic_slots(d, (int)sizeof(T));
-        if (small_shape((int)sizeof(T), Cin, Cout) && nslots > (int)grid_of(make_blockmap(d))) nslots = (int)grid_of(make_blockmap(d));
-        TRY(zero_async(grad_input, dx_elems * sizeof(T), s));
-        TRY(zero_async(c.L.partials, nw * (size_t)nslots * sizeof(T), s));
-        rc = launch_backward<T, 0, 0>(c, grad_out, input, filter, grad_input, nullptr, nullptr, nslots);
-    }
-    TRY(rc);
-    {
+    if (r.family == Family::Register || r.family == Family::Generic) {
         Scope sc(K_REDUCE, s);
         hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3((unsigned)((nw + kReduceW - 1) / kReduceW)), dim3(1024), 0, s,
-                           c.L.partials, nslots, nw, grad_filter);
+                           c.L.partials, r.slots, nw, grad_filter);
+        TRY(hip_ok());
     }
-    TRY(hip_ok());
-    if (act && generic)   // generic path has no fused epilogue
+    if (act && r.family != Family::Register)   // paths without a fused epilogue
         return selu_grad_impl<T>(input, grad_input, addend, grad_input, (size_t)B * N, Cin, nullptr, stream);
     return CONV3P_OK;
 }
@@ -2021,39 +2136,22 @@ size_t layout_bytes(int elem, int B, int N, int ntap, int nslots, int ppp, size_
 
 size_t cache_scratch_bytes(int elem, int B, int N, int max_taps, int max_Cin, int max_Cout, int ppp)
 {
-    // the largest need of any (Cin <= max_Cin, Cout <= max_Cout, taps <= max_taps) call: register-path shapes take
-    // one partial per workgroup, every other shape the generic path's capped set of partials, deep shapes their own
-    Dims d{B, N, max_Cin, max_Cout, 1, 1, max_taps, max_taps, (N + kTile - 1) / kTile};
-    const size_t grid = (size_t)grid_of(make_blockmap(d));
-    size_t b = (size_t)max_taps * max_Cin * max_Cout * (size_t)generic_slots(d, elem) * (size_t)elem;
-#define X(ci, co)                                                                                    \
-    if (ci <= max_Cin && co <= max_Cout) {                                                           \
-        const size_t need = (size_t)max_taps * ci * co * grid * (size_t)elem;                        \
-        if (need > b) b = need;                                                                      \
-    }
-    CONV3P_SMALL_SHAPES(X)
-#undef X
-#define X(ci, co)                                                                                    \
-    if (ci <= max_Cin && co <= max_Cout && tap_forward_shape(elem, ci, co) && tap_forward_bytes(d) > b) b = tap_forward_bytes(d);
-    CONV3P_SMALL_SHAPES(X)
-#undef X
-#define X(ci, co)                                                                                    \
-    if (elem == 4 && max_Cin > 0 && max_Cout > 0 && ci <= deep_pad(max_Cin) && co <= deep_pad(max_Cout)) { \
-        Dims dd{B, N, ci, co, 1, 1, max_taps, max_taps, (N + kTile - 1) / kTile};                    \
-        const size_t need = deep_scratch_bytes(dd, (size_t)B * N * (size_t)ppp);                     \
-        if (need > b) b = need;                                                                      \
-    }
-    CONV3P_DEEP_SHAPES(X)
-#undef X
-    if (elem == 8) {   // (any fp64 shape outside the register-path list may come: the blocked path's scratch)
-        Dims db{B, N, max_Cin, max_Cout, 1, 1, max_taps, max_taps, (N + kTile - 1) / kTile};
-        if (f64_blocked_bytes(db) > b) b = f64_blocked_bytes(db);
-    }
-    if (wide_shape(elem, max_Cin, max_Cout)) {
-        Dims dw{B, N, max_Cin, max_Cout, 1, 1, max_taps, max_taps, (N + kTile - 1) / kTile};
-        const size_t need = wide_scratch_bytes(dw, (size_t)B * N * (size_t)ppp);
-        if (need > b) b = need;
-    }
+    // the largest need of any (Cin <= max_Cin, Cout <= max_Cout, taps <= max_taps) call: the routes of the largest shape
+    // and of the register-path shapes, both passes; the matrix-core classes the smaller fp32 shapes pad to; and any fp64
+    // shape outside the register-path list (the blocked path's scratch does not depend on the channels)
+    const int ntiles = (N + kTile - 1) / kTile;
+    size_t b = 0;
+    auto take = [&](int cin, int cout) {
+        const Dims d{B, N, cin, cout, 1, 1, max_taps, max_taps, ntiles};
+        b = std::max({b, backward_scratch_bytes(d, elem, ppp), forward_scratch_bytes(d, elem, ppp)});
+    };
+    take(max_Cin, max_Cout);
+    for (const RegisterShape<float> &e : kRegisterShapes<float>)
+        if (e.cin <= max_Cin && e.cout <= max_Cout) take(e.cin, e.cout);
+    for (const DeepShape &e : kDeepShapes)
+        if (elem == 4 && max_Cin > 0 && max_Cout > 0 && e.cip <= deep_pad(max_Cin) && e.cop <= deep_pad(max_Cout))
+            b = std::max(b, deep_scratch_bytes(Dims{B, N, e.cip, e.cop, 1, 1, max_taps, max_taps, ntiles}, (size_t)B * N * (size_t)ppp));
+    if (elem == 8) b = std::max(b, f64_blocked_bytes(Dims{B, N, max_Cin, max_Cout, 1, 1, max_taps, max_taps, ntiles}));
     return b;
 }
 
@@ -2245,12 +2343,6 @@ uint32_t *fused_sync(void *cache, int B, int kind, uint32_t arrivals, uint32_t &
     return h.sync + (size_t)kind * h.sync_clouds * kSyncLineWords;
 }
 
-template <typename T> size_t forward_lds_bytes(const Stencil<T> &st, int ci, int co)
-{
-    return lds_common(st) + a16((size_t)st.ntap * fwd_wstr<T>(ci, co) * sizeof(T)) + a16((size_t)st.ntap * kCntStride * sizeof(T)) + 256 +
-           a16((size_t)kWavesPerBlock * 192 * 4) + a16((size_t)kWavesPerBlock * co * 64 * sizeof(T));
-}
-
 // Can the hidden layers of this stack run as fused launches on this cache?  Decided from the description alone, BEFORE any
 // call touches the cache's host record.  (fp32; in_channels 3 or 9 -> 9 -> 9 ...; odd dilated extents; one search group;
 // enough slots for the strides not to evict each other; the whole grid resident at once; census passed.)
@@ -2303,10 +2395,14 @@ int stack_forward_fused(const conv3p_stack_desc *sd, const T *points, const T *i
         Dims d0{B, N, sd->in_channels, H, sd->fz, sd->fy, sd->fx, sd->fz * sd->fy * sd->fx, ntiles};
         const BlockMap bm = make_blockmap(d0);
         size_t lds = 0;
-        for (int l = 0; l < nh; ++l) {
+        for (int l = 0; l < nh; ++l) {   // (the layers' register routes: their forward_kernel's LDS)
             Dims d = d0;
             d.Cin = l == 0 ? sd->in_channels : H;
-            lds = std::max(lds, forward_lds_bytes<T>(make_stencil<T>(d, sd->strides[l], voxel), d.Cin, H));
+            PlanArgs pa;
+            pa.strided = true;
+            const Route r = plan_forward<T>(d, make_stencil<T>(d, sd->strides[l], voxel), pa);
+            if (r.family != Family::Register) return CONV3P_ERR_UNSUPPORTED;
+            lds = std::max(lds, r.lds);
         }
         const void *kern = sd->in_channels == 3 ? reinterpret_cast<const void *>(stack_forward_kernel<T, 3, 9>)
                                                 : reinterpret_cast<const void *>(stack_forward_kernel<T, 9, 9>);
@@ -2479,11 +2575,13 @@ int stack_backward_fused(const conv3p_stack_desc *sd, const T *points, const T *
         const BlockMap bm = make_blockmap(d);
         size_t lds = 0;
         int caps[kStackMaxFused];
-        for (int l = nh - 1; l >= 1; --l) {
-            size_t sl = 0;
-            caps[l] = sparse_cap<T>(make_stencil<T>(d, sd->strides[l], voxel), H, H, sl);
-            if (caps[l] <= 0 || sl > 40960) return CONV3P_ERR_UNSUPPORTED;   // (undilated layers: dense G; four workgroups per CU)
-            lds = std::max(lds, sl);
+        for (int l = nh - 1; l >= 1; --l) {   // (the layers' register routes on the SPARSE hint: their populated rows)
+            PlanArgs pa;
+            pa.strided = pa.sparse_hint = true;
+            const Route r = plan_backward<T>(d, make_stencil<T>(d, sd->strides[l], voxel), pa);
+            caps[l] = r.family == Family::Register ? r.cap : 0;
+            if (caps[l] <= 0 || r.sparse_lds > 40960) return CONV3P_ERR_UNSUPPORTED;   // (undilated layers: dense G; four workgroups per CU)
+            lds = std::max(lds, r.sparse_lds);
         }
         const void *kern = reinterpret_cast<const void *>(stack_backward_kernel<T, 9>);
         if ((int)grid_of(bm) > fused_capacity(kern, lds, fd.cus)) return CONV3P_ERR_UNSUPPORTED;
@@ -2533,21 +2631,18 @@ int stack_backward_fused(const conv3p_stack_desc *sd, const T *points, const T *
 }
 
 // The hidden layers past the first read and write column blocks of `concat` (row strides), which only the register kernels
-// take: each must be a register shape whose backward fits LDS (fp64: the dense G; fp32: the dense G or the populated rows).
-// Checked before anything is launched, so that a description the backward cannot serve (fp64 9 -> 9 past 28 taps, hidden
-// widths outside the list) returns CONV3P_ERR_UNSUPPORTED with every output untouched.
+// take: each must plan to them.  Checked before anything is launched, so that a description the backward cannot serve
+// (fp64 9 -> 9 past 28 taps, hidden widths outside the list) returns CONV3P_ERR_UNSUPPORTED with every output untouched.
 template <typename T> int stack_backward_fits(const conv3p_stack_desc *sd, T voxel, int B, int N)
 {
     const int H = sd->hidden;
     for (int l = 1; l < sd->n_hidden; ++l) {
-        if (!small_shape((int)sizeof(T), H, H)) return CONV3P_ERR_UNSUPPORTED;
         Dims d{B, N, H, H, sd->fz, sd->fy, sd->fx, 0, 0};
         TRY(check(d, sd->strides[l], (double)voxel, true));
-        const Stencil<T> st = make_stencil<T>(d, sd->strides[l], voxel);
-        if (dense_backward_lds<T>(st, H, H) <= kMaxLds) continue;
-        size_t lds = 0;
-        if (sizeof(T) == 4 && sparse_cap<T>(st, H, H, lds) > 0) continue;
-        return CONV3P_ERR_UNSUPPORTED;
+        PlanArgs pa;
+        pa.strided = true;
+        if (plan_backward<T>(d, make_stencil<T>(d, sd->strides[l], voxel), pa).family != Family::Register)
+            return CONV3P_ERR_UNSUPPORTED;
     }
     return CONV3P_OK;
 }
