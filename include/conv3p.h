@@ -409,6 +409,37 @@ int conv3p_fc_backward_f32(const float *x, const float *W, const float *y, const
                            int act, float *dx, float *dW, float *db, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The per-point loss head of the segmentation model as one fused pass
+ * (/root/reference/scene_seg/pointcnn_scene_seg_acsd.py:60-71: softmax cross-entropy over every point, mean over all
+ * B*N points) together with the statistics the reference's loops compute after every batch with a Python double loop
+ * (/root/reference/scene_seg/train_scene_seg_s3dis.py:134-145, eval_scene_seg_s3dis.py:88-98).
+ *
+ * act (rows, num_class) row-major: the SELU'd output of the last layer, rows = B*N, 2 <= num_class <= 128;
+ * labels int32[rows].  Per row, with m = max_c act[r][c]:
+ *   row loss      = log(sum_c exp(act[r][c] - m)) + m - act[r][label]
+ *   grad_act[r]   = (softmax(act[r]) - onehot(label)) * grad_scale       (NULL: evaluation, no gradient)
+ *   pred[r]       = first index of the maximum, as np.argmax             (may be NULL)
+ *   *loss_sum     = sum of the row losses (double, device), NOT scaled: the mean is *loss_sum * grad_scale
+ *   counts        = int64[2 + 3 * num_class] (device): {correct, invalid, seen[C], correct_class[C], predicted[C]}
+ * grad_scale = 1 / (number of points the mean runs over; those of all ranks in data-parallel runs).
+ * A label outside [0, num_class) makes an ignored row: loss 0 (what tf.one_hot gives), gradient row 0, counted in
+ * `invalid` only; the denominator is the caller's.  Labels are thereby validated on the device without a host
+ * synchronisation.  A NaN in a row reaches *loss_sum and that row's gradient.
+ * Two launches on `stream`, no memset, no atomics on global memory: bitwise reproducible; grad_act and pred of a row
+ * do not depend on the other rows.  Scratch from conv3p_seg_head_workspace_bytes (either element type).
+ * Status: CONV3P_ERR_INVALID_ARGUMENT for rows == 0, num_class < 2 or NULL act / labels / loss_sum / counts;
+ * CONV3P_ERR_UNSUPPORTED when four 64-row tiles of (num_class | 1) elements do not fit in the CU's LDS (fp32: up to
+ * 128 classes; fp64: up to 79, so 64 works and 128 does not); CONV3P_ERR_WORKSPACE; nothing is launched on an error.
+ * ------------------------------------------------------------------------------------------- */
+size_t conv3p_seg_head_workspace_bytes(size_t rows, int num_class);
+int conv3p_seg_head_f32(const float *act, const int32_t *labels, size_t rows, int num_class, float grad_scale,
+                        float *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, int num_class, double grad_scale,
+                        double *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
 /* Kernel-level timing with HIP events recorded on the caller's stream (bench.py uses it
  * to derive the roofline of the dominant kernel).  Off by default; when enabled every
  * kernel launch of this library is bracketed by an event pair.  read() synchronises the

@@ -76,6 +76,9 @@ SYMBOLS = {
     "conv3p_augment_f32": (_i, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i, _i, _vp, _vp]),
     "conv3p_sort_xyz_order_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "conv3p_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "conv3p_seg_head_workspace_bytes": (_sz, [_sz, _i]),
+    "conv3p_seg_head_f32": (_i, [_vp, _vp, _sz, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_seg_head_f64": (_i, [_vp, _vp, _sz, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

@@ -18,6 +18,7 @@
 #include "conv3p_stack_fused.hpp"
 #include "conv3p_prestep.hpp"
 #include "conv3p_head.hpp"
+#include "conv3p_seg_head.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -39,13 +40,14 @@ inline size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 enum Kind { K_PREP = 0, K_SEARCH, K_FORWARD, K_BACKWARD, K_REDUCE, K_SELU, K_SELU_GRAD, K_MEMSET,
             K_DEEP_GEMM, K_DEEP_DW, K_TRANSPOSE, K_DEEP_ORDER, K_FC_FWD, K_FC_DX, K_FC_DW, K_DEEP_GEMM_BF16, K_DEEP_DW_BF16,
             K_GENERIC_FWD, K_GENERIC_BWD,   // the thread-per-pair kernels (global float atomics) over a whole call
+            K_SEG_HEAD,                     // seg_head_kernel + seg_head_finish_kernel (conv3p_seg_head.hpp)
             K_NKINDS };
 const char *const kKindName[K_NKINDS] = {"prep_kernel", "search_kernel", "forward_kernel",
                                          "backward_kernel", "reduce_partials_kernel", "selu_kernel",
                                          "selu_grad_kernel", "memset", "deep_gemm_kernel", "deep_dw_kernel",
                                          "transpose_filter_kernel", "deep_order_kernel", "fc_forward_kernel",
                                          "fc_dx_kernel", "fc_dw_kernel", "deep_gemm_bf16_kernel", "deep_dw_bf16_kernel",
-                                         "generic_forward_kernel", "generic_backward_kernel"};
+                                         "generic_forward_kernel", "generic_backward_kernel", "seg_head_kernel"};
 struct Prof {
     std::mutex mu;
     bool on = false;
@@ -2752,6 +2754,43 @@ bool cache_cfg_ok(const conv3p_cache_config *cfg)
            cfg->max_Cin >= 0 && cfg->max_Cout >= 0;
 }
 
+// ----------------------------------------------------------------------------- the segmentation head
+// Waves per workgroup and grid of one segmentation-head call.  A (T, C) is supported when four wave tiles and the
+// counters fit in the CU's LDS (one wave per SIMD at least: fp32 up to 128 classes, fp64 up to 79); the workgroup is
+// four waves while that leaves three or more workgroups per CU (13 classes: 13.5 KB, 41: 42.5 KB), then two, then one.
+struct SegPlan { int nw; unsigned grid; size_t lds, part_bytes; };
+template <typename T> bool seg_plan(size_t rows, int C, SegPlan &p)
+{
+    if (C > kSegMaxClass || seg_lds_bytes<T>(4, C) > kMaxLds) return false;
+    p.nw = seg_lds_bytes<T>(4, C) <= 48 * 1024 ? 4 : seg_lds_bytes<T>(2, C) <= 48 * 1024 ? 2 : 1;
+    p.lds = seg_lds_bytes<T>(p.nw, C);
+    const size_t tiles = (rows + 63) / 64, wgs = (tiles + p.nw - 1) / p.nw;
+    p.grid = (unsigned)(wgs < (size_t)kSegMaxGrid ? wgs : (size_t)kSegMaxGrid);
+    p.part_bytes = up((size_t)p.grid * seg_record_bytes(C));
+    return true;
+}
+
+template <typename T>
+int seg_head_impl(const T *act, const int32_t *labels, size_t rows, int C, T grad_scale, T *grad_act, int32_t *pred,
+                  double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (rows == 0 || C < 2 || !act || !labels || !loss_sum || !counts) return CONV3P_ERR_INVALID_ARGUMENT;
+    SegPlan p;
+    if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;   // (int32 partial counters)
+    TRY(buf_check(workspace, workspace_bytes, p.part_bytes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char *part = static_cast<char *>(workspace);
+    {
+        Scope sc(K_SEG_HEAD, s);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(seg_head_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        hipLaunchKernelGGL(seg_head_kernel<T>, dim3(p.grid), dim3(64 * p.nw), p.lds, s, act, labels, rows, C, grad_scale,
+                           grad_act, pred, part);
+        hipLaunchKernelGGL(seg_head_finish_kernel, dim3(1), dim3(kSegFinishThreads), 0, s, part, (int)p.grid, C, loss_sum,
+                           reinterpret_cast<long long *>(counts));
+    }
+    return hip_ok();
+}
+
 }  // namespace
 
 extern "C" {
@@ -3147,6 +3186,27 @@ int conv3p_fc_backward_f32(const float *x, const float *W, const float *y, const
                            M, K, N, dx);
     }
     return hip_ok();
+}
+
+size_t conv3p_seg_head_workspace_bytes(size_t rows, int num_class)
+{
+    if (rows == 0 || num_class < 2 || num_class > kSegMaxClass) return 0;
+    const size_t tiles = (rows + 63) / 64;   // (one-wave workgroups, the most records either element type takes)
+    return up((tiles < (size_t)kSegMaxGrid ? tiles : (size_t)kSegMaxGrid) * seg_record_bytes(num_class));
+}
+int conv3p_seg_head_f32(const float *act, const int32_t *labels, size_t rows, int num_class, float grad_scale,
+                        float *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
+                        size_t workspace_bytes, void *stream)
+{
+    return seg_head_impl<float>(act, labels, rows, num_class, grad_scale, grad_act, pred, loss_sum, counts, workspace,
+                                workspace_bytes, stream);
+}
+int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, int num_class, double grad_scale,
+                        double *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
+                        size_t workspace_bytes, void *stream)
+{
+    return seg_head_impl<double>(act, labels, rows, num_class, grad_scale, grad_act, pred, loss_sum, counts, workspace,
+                                 workspace_bytes, stream);
 }
 
 int conv3p_profile_enable(int on)
