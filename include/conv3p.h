@@ -440,6 +440,43 @@ int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, i
                         double *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The optimizer step of all three training drivers: tf.train.MomentumOptimizer(learning_rate, momentum)
+ * (train_modelnet40_acsd.py:81, scene_seg/train_scene_seg_s3dis.py:83, train_scene_seg_scenenn.py:86),
+ * i.e. TensorFlow's non-Nesterov ApplyMomentum, in place, per element:
+ *   accum = accum * momentum + grad
+ *   param = param - accum * lr
+ * Each statement is two separately rounded operations (no fused multiply-add): bit-equal to numpy's `a * m + g` and
+ * `w - a * lr` in the element type.  A NaN or Inf in grad propagates to that element, as in TensorFlow.  lr is the
+ * value of the schedule (train_modelnet40_acsd.py:78-79, a host computation) for this step.
+ *
+ * conv3p_momentum_step_f32 / _f64   n_tensors <= CONV3P_OPT_MAX_TENSORS tensors in ONE launch on `stream`.  params,
+ *   grads, accums, numels are HOST arrays of n_tensors entries (as the tables of conv3p_stack_*), read before the call
+ *   returns; the pointers in them are device pointers aligned to the element size (16-byte accesses are used wherever
+ *   the three pointers of a tensor share their offset inside a 16-byte line).  A tensor of 0 elements is legal and
+ *   its pointers may be NULL.  The result does not depend on how tensors are grouped into calls.
+ *   Status, decided before any launch: n_tensors < 0 or > CONV3P_OPT_MAX_TENSORS, a NULL array (n_tensors > 0), a NULL
+ *   or misaligned entry with a non-zero count -> CONV3P_ERR_INVALID_ARGUMENT; n_tensors == 0 or all counts zero ->
+ *   CONV3P_OK, nothing launched.
+ *
+ * conv3p_fc_backward_step_f32   conv3p_fc_backward_f32 (pointcnn2_acsd.py:71, the minimize() of
+ *   train_modelnet40_acsd.py:82 on its weights) with the update in the epilogue of the dW pass: W, b and their
+ *   accumulators are updated in place, dW and db never reach memory (two reads and two writes of W's size instead of
+ *   one write, three reads and two writes).  dx (may be NULL) is computed from W as it was BEFORE the call.  W, accum_W,
+ *   b, accum_b afterwards are bit-equal to conv3p_fc_backward_f32 followed by conv3p_momentum_step_f32.
+ *   b and accum_b may both be NULL (one without the other: CONV3P_ERR_INVALID_ARGUMENT).  Constraints, scratch and
+ *   status codes of conv3p_fc_backward_f32, except M == 0 with K * N > 0: CONV3P_ERR_INVALID_ARGUMENT (no batch, no
+ *   gradient to step with).
+ * ------------------------------------------------------------------------------------------- */
+#define CONV3P_OPT_MAX_TENSORS 16
+int conv3p_momentum_step_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
+                             const size_t *numels, float lr, float momentum, void *stream);
+int conv3p_momentum_step_f64(int n_tensors, double *const *params, const double *const *grads, double *const *accums,
+                             const size_t *numels, double lr, double momentum, void *stream);
+int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float *y, const float *dy, int M, int K, int N,
+                                int act, float *dx, float *accum_W, float *accum_b, float lr, float momentum,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 /* Kernel-level timing with HIP events recorded on the caller's stream (bench.py uses it
  * to derive the roofline of the dominant kernel).  Off by default; when enabled every
  * kernel launch of this library is bracketed by an event pair.  read() synchronises the

@@ -29,6 +29,7 @@ CACHE_FUSED_STACK = CACHE_FUSED_FORWARD | CACHE_FUSED_BACKWARD
 CACHE_MATMUL_BF16 = 64            # matrix-core path: filter contractions in bf16 (opt-in, see include/conv3p.h)
 ABI_VERSION = 5                # CONV3P_ABI_VERSION of include/conv3p.h
 STACK_MAX_LAYERS = 8
+OPT_MAX_TENSORS = 16             # CONV3P_OPT_MAX_TENSORS
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -79,6 +80,10 @@ SYMBOLS = {
     "conv3p_seg_head_workspace_bytes": (_sz, [_sz, _i]),
     "conv3p_seg_head_f32": (_i, [_vp, _vp, _sz, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_seg_head_f64": (_i, [_vp, _vp, _sz, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_momentum_step_f32": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp]),
+    "conv3p_momentum_step_f64": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "conv3p_fc_backward_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float,
+                                         _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

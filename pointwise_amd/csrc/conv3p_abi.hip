@@ -19,6 +19,7 @@
 #include "conv3p_prestep.hpp"
 #include "conv3p_head.hpp"
 #include "conv3p_seg_head.hpp"
+#include "conv3p_optim.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -2793,6 +2794,43 @@ int seg_head_impl(const T *act, const int32_t *labels, size_t rows, int C, T gra
 
 }  // namespace
 
+namespace {
+static_assert(kOptMaxTensors == CONV3P_OPT_MAX_TENSORS, "conv3p_optim.hpp and conv3p.h disagree");
+
+// status first, then (only if there is anything to do) the table by value and one launch
+template <typename T>
+int momentum_step_impl(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, T lr,
+                       T momentum, void *stream)
+{
+    if (n < 0 || n > kOptMaxTensors) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (n == 0) return CONV3P_OK;
+    if (!params || !grads || !accums || !numels) return CONV3P_ERR_INVALID_ARGUMENT;
+    OptTable<T> tab;
+    size_t chunks = 0;
+    for (int i = 0; i < kOptMaxTensors; ++i) {
+        const size_t ne = i < n ? numels[i] : 0;
+        if (ne != 0) {
+            if (!params[i] || !grads[i] || !accums[i]) return CONV3P_ERR_INVALID_ARGUMENT;
+            if (((reinterpret_cast<size_t>(params[i]) | reinterpret_cast<size_t>(grads[i]) |
+                  reinterpret_cast<size_t>(accums[i])) & (sizeof(T) - 1)) != 0)
+                return CONV3P_ERR_INVALID_ARGUMENT;
+        }
+        tab.param[i] = ne ? params[i] : nullptr;
+        tab.grad[i] = ne ? grads[i] : nullptr;
+        tab.accum[i] = ne ? accums[i] : nullptr;
+        tab.numel[i] = ne;
+        chunks += (ne + kOptChunk - 1) / kOptChunk;
+        tab.chunk_end[i] = chunks;
+    }
+    if (chunks == 0) return CONV3P_OK;
+    tab.chunks = chunks;
+    const unsigned grid = (unsigned)(chunks < (size_t)kOptMaxGrid ? chunks : (size_t)kOptMaxGrid);
+    hipLaunchKernelGGL(momentum_step_kernel<T>, dim3(grid), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream), tab, lr,
+                       momentum);
+    return hip_ok();
+}
+}  // namespace
+
 extern "C" {
 
 size_t conv3p_workspace_bytes(int pass, int elem_bytes, int B, int N, int Cin, int Cout, int fz, int fy,
@@ -3207,6 +3245,68 @@ int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, i
 {
     return seg_head_impl<double>(act, labels, rows, num_class, grad_scale, grad_act, pred, loss_sum, counts, workspace,
                                  workspace_bytes, stream);
+}
+
+int conv3p_momentum_step_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
+                             const size_t *numels, float lr, float momentum, void *stream)
+{
+    return momentum_step_impl<float>(n_tensors, params, grads, accums, numels, lr, momentum, stream);
+}
+int conv3p_momentum_step_f64(int n_tensors, double *const *params, const double *const *grads, double *const *accums,
+                             const size_t *numels, double lr, double momentum, void *stream)
+{
+    return momentum_step_impl<double>(n_tensors, params, grads, accums, numels, lr, momentum, stream);
+}
+
+int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float *y, const float *dy, int M, int K, int N,
+                                int act, float *dx, float *accum_W, float *accum_b, float lr, float momentum,
+                                void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (M < 0 || K < 0 || N < 0 || (act != 0 && act != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((b == nullptr) != (accum_b == nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((size_t)K * N == 0) return CONV3P_OK;
+    if (M == 0) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!x || !W || !dy || !accum_W || (act && !y)) return CONV3P_ERR_INVALID_ARGUMENT;
+    FcPlan p;
+    if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, p.dz_bytes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *dz = static_cast<float *>(workspace);
+    const int dw_steps = M <= 32 ? 16 : M <= 64 ? 32 : 64;
+    if ((size_t)2 * dw_steps * (N + 1) * 4 > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // before anything is launched
+    hipLaunchKernelGGL(fc_dz_step_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, y, dy, M, N, act, dz, b, accum_b,
+                       lr, momentum);
+    TRY(hip_ok());
+    auto waves_for = [&](int slots) {                                      // as conv3p_fc_backward_f32
+        const int tiles = (K + 31) / 32;
+        int nw = (tiles + slots - 1) / slots;
+        return nw < 4 ? 4 : (nw > 8 ? 8 : nw);
+    };
+    if (dx != nullptr) {                                                   // FIRST: dx = dz . W^T needs the old W
+        Scope sc(K_FC_DX, s);
+        const int psteps = (N / 8 + 7) / 8 * 8;
+        size_t lds = (size_t)32 * (8 * psteps + 4) * 4;
+        const int nw = waves_for(lds <= 80 * 1024 ? 512 : 256);
+        if (lds < (size_t)nw * 32 * 33 * 4) lds = (size_t)nw * 32 * 33 * 4;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fc_dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(fc_dx_kernel, dim3((unsigned)((K + 32 * nw - 1) / (32 * nw)), (unsigned)p.mblocks), dim3(64 * nw), lds, s, dz, W,
+                           M, K, N, dx);
+    }
+    TRY(hip_ok());
+    {
+        Scope sc(K_FC_DW, s);                                              // (no profile kind of its own: the table is pinned)
+        auto launch = [&](auto kern, int steps) {
+            const size_t lds = (size_t)2 * steps * (N + 1) * 4;
+            const int nw = waves_for(lds <= 80 * 1024 ? 512 : 256);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3((unsigned)((K + 32 * nw - 1) / (32 * nw))), dim3(64 * nw), lds, s, x, dz, M, K, N, W,
+                               accum_W, lr, momentum);
+        };
+        if (M <= 32) launch(fc_dw_step_kernel<16>, 16);
+        else if (M <= 64) launch(fc_dw_step_kernel<32>, 32);
+        else launch(fc_dw_step_kernel<64>, 64);
+    }
+    return hip_ok();
 }
 
 int conv3p_profile_enable(int on)

@@ -127,6 +127,7 @@ class ClassificationHead:
         self.dW2 = torch.empty_like(self.W2)
         self.db2 = torch.empty_like(self.b2)
         self._saved = None
+        self._fc1_stepped = False                      # the last backward() updated W1 / b1 itself: dW1 / db1 not written
 
     def forward(self, feat, training=True, keep_mask=None):
         B = feat.shape[0]
@@ -150,8 +151,13 @@ class ClassificationHead:
         dlogits.scatter_add_(1, idx, -torch.ones_like(idx, dtype=dlogits.dtype))
         return e, dlogits / float(global_batch if global_batch is not None else logits.shape[0])
 
-    def backward(self, dlogits):
-        """-> dL/dfeat (B, N, 36); parameter gradients in self.dW1, db1, dW2, db2."""
+    def backward(self, dlogits, optimizer=None):
+        """-> dL/dfeat (B, N, 36); parameter gradients in self.dW1, db1, dW2, db2.
+
+        optimizer (an optim.MomentumOptimizer that owns W1 and b1; single-GPU runs): fc1's gradient pass applies the
+        update itself (optimizer.fused_fc_step) -- W1 and b1 are stepped on return, dW1 / db1 are NOT written and
+        gradients() reports None for them; W2, b2 and everything else are the caller's optimizer.step().  Data-parallel
+        runs keep the default: the gradient has to cross ranks before anything is updated."""
         view, fc1, drop, mask, fc2, shape = self._saved
         ddrop, _, _ = fully_connected_grad(drop, self.W2, fc2, dlogits, selu=True, dW_out=self.dW2, db_out=self.db2)
         if mask is not None:
@@ -159,11 +165,19 @@ class ClassificationHead:
             dfc1 = ddrop * (a * mask)
         else:
             dfc1 = ddrop
-        dview, _, _ = fully_connected_grad(view, self.W1, fc1, dfc1, selu=True, dW_out=self.dW1, db_out=self.db1)
+        self._fc1_stepped = optimizer is not None and optimizer.owns(self.W1, self.b1)
+        if self._fc1_stepped:
+            dview = optimizer.fused_fc_step(view.contiguous(), self.W1, self.b1, fc1, dfc1.contiguous(), selu=True)
+        else:
+            dview, _, _ = fully_connected_grad(view, self.W1, fc1, dfc1, selu=True, dW_out=self.dW1, db_out=self.db1)
         return dview.reshape(shape)
 
     def parameters(self):
         return [self.W1, self.b1, self.W2, self.b2]
 
     def gradients(self):
+        """In parameters() order; None for W1 and b1 when the last backward() stepped them itself (what
+        MomentumOptimizer.step skips)."""
+        if self._fc1_stepped:
+            return [None, None, self.dW2, self.db2]
         return [self.dW1, self.db1, self.dW2, self.db2]

@@ -8,7 +8,8 @@ Segmentation (/root/reference/scene_seg/pointcnn_scene_seg_acsd.py:51-57):
 
 Only the conv3p layers and the SELU between them are here (the hot path of SURVEY.md section 8, row A8);
 the classification model's dense head and loss are in head.py, the segmentation model's per-point loss head (whose
-gradient is what backward([dL/dact]) takes) in seg_head.py; optimizer and data pipeline of the reference are out of scope.
+gradient is what backward([dL/dact]) takes) in seg_head.py, the optimizer (filters + grad_views is what its step takes) in
+optim.py; the data pipeline of the reference is out of scope.
 forward() keeps the activations; backward() takes dL/d(activation) of every layer that has an external
 consumer (the concat for classification, the logits for segmentation) and returns dL/dinput and the weight
 gradients, written into ONE fused buffer so that data-parallel training needs a single all-reduce.
