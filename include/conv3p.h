@@ -477,6 +477,58 @@ int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float 
                                 int act, float *dx, float *accum_W, float *accum_b, float lr, float momentum,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The tail of the classification model's training step as two launches: everything between fc1's output and fc1's
+ * backward (/root/reference/pointcnn2_acsd.py:73-90: dropout_selu, fully_connected num_class selu, mean sparse softmax
+ * cross-entropy; /root/reference/selu.py:35-70), the statistics of /root/reference/train_modelnet40_acsd.py:136-146
+ * (argmax, correct clouds, per-class seen / correct) and, in the _step form, minimize()'s update of W2 / b2
+ * (train_modelnet40_acsd.py:82).  fp32.
+ *
+ * fc1 (M, H): the SELU'd output of fc1, 16-byte aligned; W2 (H, C); b2 (C); labels int32[M].  Per row m:
+ *   drop[m]     = training && rate > 0 ? a * (fc1[m] * keep + alpha' * (1 - keep)) + b : fc1[m]      (selu.py:56-62; a, b,
+ *                 alpha' of selu.py:36-61 for keep_prob = 1 - rate, computed in double, used in fp32)
+ *   logits[m]   = selu(drop[m] . W2 + b2)                                 (M, C), required
+ *   pred[m]     = first index of the row maximum, as np.argmax           (may be NULL)
+ *   row loss    = log(sum_c exp(logits - max)) + max - logits[label]
+ *   dz[m]       = (softmax(logits[m]) - onehot(label)) * grad_scale * selu'(logits[m])   (through the output, as fc_backward)
+ *   dfc1[m]     = (dz[m] . W2^T) * (dropout ? a * keep : 1)              (M, H): the dy of conv3p_fc_backward_f32 for fc1
+ * and across rows, in ascending row order with a fixed association:
+ *   dW2 (H, C)  = drop^T . dz,   db2 (C) = sum_m dz[m]
+ *   *loss_sum   = sum of the row losses (double, device), NOT scaled
+ *   counts      = int64[2 + 3 C] (device): {correct, invalid, seen[C], correct_class[C], predicted[C]}, the layout of
+ *                 conv3p_seg_head_*
+ * A label outside [0, C) makes an ignored row: loss 0, dz and dfc1 rows +0, counted in `invalid` only; no host
+ * synchronisation.  A NaN in a row of fc1 reaches *loss_sum and that row of dfc1 (and dW2, db2), no other row.
+ *
+ * keep: keep_mask (M, H) float 0 / 1, 16-byte aligned; or keep_mask == NULL: drawn with Philox4x32-10, key = (low, high
+ * 32 bits of seed), counter = (e >> 2, 0, low, high 32 bits of step) with e = m * H + h, output word e & 3,
+ * u = (word >> 8) * 2^-24, keep = floorf((float)(1 - rate) + u) (selu.py:53-55): a function of (seed, step, m, h) alone.
+ * keep_out (uint8 (M, H), may be NULL) receives the mask whenever dropout is applied, from either source.
+ *
+ * dfc1 == NULL: evaluation -- no gradient work, dW2 / db2 are not touched; logits, pred, *loss_sum and counts are
+ * produced.  training == 0 switches the dropout off (drop = fc1) with or without gradients.
+ * conv3p_cls_tail_step_f32: accum_W2 (H, C) and accum_b2 (C) in place of dW2 / db2: the second launch applies
+ * ApplyMomentum (see conv3p_momentum_step_f32) to W2, b2 and the accumulators in place; dW2 / db2 are never written,
+ * dfc1 comes from W2 as it was BEFORE the call; W2, b2 and the accumulators afterwards are bit-equal to
+ * conv3p_cls_tail_f32 followed by conv3p_momentum_step_f32.
+ * Two launches on `stream`, no memset, no atomic on global memory: bitwise reproducible; logits, pred and dfc1 of a row
+ * do not depend on the other rows of the call.  Scratch from conv3p_cls_tail_workspace_bytes (0 for a refused shape).
+ * Status, decided before any launch: CONV3P_ERR_INVALID_ARGUMENT for NULL fc1 / W2 / b2 / labels / logits / loss_sum /
+ * counts, M <= 0, H <= 0, C < 2, rate outside [0, 1) when training, dfc1 without dW2 and db2, misaligned fc1 /
+ * keep_mask, and in the _step form a NULL dfc1 or accumulator; CONV3P_ERR_UNSUPPORTED unless M <= 128, H % 8 == 0,
+ * H <= 1024, C <= 128 (C need not be a multiple of 8); CONV3P_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+size_t conv3p_cls_tail_workspace_bytes(int M, int H, int C);
+int conv3p_cls_tail_f32(const float *fc1, const float *W2, const float *b2, const int32_t *labels, int M, int H, int C,
+                        int training, double rate, const float *keep_mask, uint64_t seed, uint64_t step, float grad_scale,
+                        float *logits, int32_t *pred, float *dfc1, float *dW2, float *db2, uint8_t *keep_out,
+                        double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_cls_tail_step_f32(const float *fc1, float *W2, float *b2, const int32_t *labels, int M, int H, int C,
+                             int training, double rate, const float *keep_mask, uint64_t seed, uint64_t step,
+                             float grad_scale, float *logits, int32_t *pred, float *dfc1, float *accum_W2, float *accum_b2,
+                             float lr, float momentum, uint8_t *keep_out, double *loss_sum, int64_t *counts,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* Kernel-level timing with HIP events recorded on the caller's stream (bench.py uses it
  * to derive the roofline of the dominant kernel).  Off by default; when enabled every
  * kernel launch of this library is bracketed by an event pair.  read() synchronises the

@@ -20,9 +20,11 @@
 #include "conv3p_head.hpp"
 #include "conv3p_seg_head.hpp"
 #include "conv3p_optim.hpp"
+#include "conv3p_cls_tail.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2831,6 +2833,69 @@ int momentum_step_impl(int n, T *const *params, const T *const *grads, T *const 
 }
 }  // namespace
 
+// ----------------------------------------------------------------------------- the classification tail
+namespace {
+struct ClsPlan { size_t drop, dz, loss, pred, total; };
+bool cls_plan(int M, int H, int C, ClsPlan &p)
+{
+    if (M < 1 || M > kClsMaxRows || H < 8 || H % 8 != 0 || H > kClsMaxHidden || C < 2 || C > kClsMaxClass) return false;
+    p.drop = 0;
+    p.dz = p.drop + up((size_t)M * H * 4);
+    p.loss = p.dz + up((size_t)M * C * 4);
+    p.pred = p.loss + up((size_t)M * 8);
+    p.total = p.pred + up((size_t)M * 4);
+    return true;
+}
+
+// Every status first; then cls_tail_row_kernel and cls_tail_dw_kernel, outside the profile bracket (the table of
+// kinds is pinned), as momentum_step_kernel.  accum_W2 != NULL: the _step entry point.
+int cls_tail_impl(const float *fc1, float *W2, float *b2, const int32_t *labels, int M, int H, int C, int training,
+                  double rate, const float *keep_mask, uint64_t seed, uint64_t step, float grad_scale, float *logits,
+                  int32_t *pred, float *dfc1, float *dW2, float *db2, float *accum_W2, float *accum_b2, float lr,
+                  float momentum, uint8_t *keep_out, double *loss_sum, int64_t *counts, void *workspace,
+                  size_t workspace_bytes, void *stream)
+{
+    if (!fc1 || !W2 || !b2 || !labels || !logits || !loss_sum || !counts || M <= 0 || H <= 0 || C < 2)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (training && !(rate >= 0.0 && rate < 1.0)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (dfc1 && !accum_W2 && (!dW2 || !db2)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (((reinterpret_cast<uintptr_t>(fc1) | reinterpret_cast<uintptr_t>(keep_mask)) & 15) != 0)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    ClsPlan pl;
+    if (!cls_plan(M, H, C, pl)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, pl.total));
+    char *ws = static_cast<char *>(workspace);
+    ClsTailArgs a;
+    a.fc1 = fc1; a.W2 = W2; a.b2 = b2; a.labels = labels; a.keep_mask = keep_mask;
+    a.M = M; a.H = H; a.C = C;
+    a.dropout = training && rate > 0.0;
+    a.need_grad = dfc1 != nullptr;
+    // selu.py:36-61 in double, as head.dropout_selu_constants
+    const double alpha = -1.7580993408473766, keep = 1.0 - rate;
+    const double ca = a.dropout ? std::sqrt(1.0 / (keep * ((1.0 - keep) * alpha * alpha + 1.0))) : 1.0;
+    a.keep_prob = (float)keep;
+    a.a = (float)ca;
+    a.b = a.dropout ? (float)(0.0 - ca * ((1.0 - keep) * alpha)) : 0.0f;
+    a.alpha = (float)alpha;
+    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
+    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
+    a.grad_scale = grad_scale;
+    a.logits = logits; a.pred = pred; a.dfc1 = dfc1; a.keep_out = keep_out;
+    a.drop = reinterpret_cast<float *>(ws + pl.drop);
+    a.dz = reinterpret_cast<float *>(ws + pl.dz);
+    a.row_loss = reinterpret_cast<double *>(ws + pl.loss);
+    a.row_pred = reinterpret_cast<int32_t *>(ws + pl.pred);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(cls_tail_row_kernel, dim3((unsigned)M), dim3(kClsRowThreads), 0, s, a);
+    TRY(hip_ok());
+    const unsigned wgs = a.need_grad ? (unsigned)((H * C + kClsDwThreads - 1) / kClsDwThreads) : 0u;
+    hipLaunchKernelGGL(cls_tail_dw_kernel, dim3(wgs + 1), dim3(kClsDwThreads), 0, s, a.drop, a.dz, a.row_loss, a.row_pred,
+                       labels, M, H, C, a.need_grad, W2, b2, accum_W2, accum_b2, lr, momentum, dW2, db2, loss_sum,
+                       reinterpret_cast<long long *>(counts));
+    return hip_ok();
+}
+}  // namespace
+
 extern "C" {
 
 size_t conv3p_workspace_bytes(int pass, int elem_bytes, int B, int N, int Cin, int Cout, int fz, int fy,
@@ -3307,6 +3372,32 @@ int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float 
         else launch(fc_dw_step_kernel<64>, 64);
     }
     return hip_ok();
+}
+
+size_t conv3p_cls_tail_workspace_bytes(int M, int H, int C)
+{
+    ClsPlan p;
+    return cls_plan(M, H, C, p) ? p.total : 0;
+}
+int conv3p_cls_tail_f32(const float *fc1, const float *W2, const float *b2, const int32_t *labels, int M, int H, int C,
+                        int training, double rate, const float *keep_mask, uint64_t seed, uint64_t step, float grad_scale,
+                        float *logits, int32_t *pred, float *dfc1, float *dW2, float *db2, uint8_t *keep_out,
+                        double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return cls_tail_impl(fc1, const_cast<float *>(W2), const_cast<float *>(b2), labels, M, H, C, training, rate, keep_mask,
+                         seed, step, grad_scale, logits, pred, dfc1, dW2, db2, nullptr, nullptr, 0.0f, 0.0f, keep_out,
+                         loss_sum, counts, workspace, workspace_bytes, stream);
+}
+int conv3p_cls_tail_step_f32(const float *fc1, float *W2, float *b2, const int32_t *labels, int M, int H, int C,
+                             int training, double rate, const float *keep_mask, uint64_t seed, uint64_t step,
+                             float grad_scale, float *logits, int32_t *pred, float *dfc1, float *accum_W2, float *accum_b2,
+                             float lr, float momentum, uint8_t *keep_out, double *loss_sum, int64_t *counts,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!accum_W2 || !accum_b2 || !dfc1) return CONV3P_ERR_INVALID_ARGUMENT;
+    return cls_tail_impl(fc1, W2, b2, labels, M, H, C, training, rate, keep_mask, seed, step, grad_scale, logits, pred, dfc1,
+                         nullptr, nullptr, accum_W2, accum_b2, lr, momentum, keep_out, loss_sum, counts, workspace,
+                         workspace_bytes, stream);
 }
 
 int conv3p_profile_enable(int on)
