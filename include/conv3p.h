@@ -391,6 +391,40 @@ int conv3p_sort_xyz_order_f32(const float *data, int B, int N, int row_floats, i
 int conv3p_gather_rows(const void *src, const int32_t *order, int B, int N, int row_bytes, void *dst, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One batch of the reference's data providers as ONE launch (pointwise_amd/csrc/conv3p_provider.hpp): what
+ * DataConsumer.get_batch_point_cloud does per batch and load_current_data / next_epoch per file or epoch
+ * (modelnet_provider.py:171-219, scene_seg/s3dis_provider.py:80-118, scene_seg/scenenn_provider.py:67-105) with the
+ * sort of util.py:55-109, from a data set resident on the device.
+ *
+ *   data    float (S, Nsrc, K), K >= 3, xyz first; the first N <= Nsrc rows of a sample are used
+ *   labels  label_bytes = 1 / 4 / 8 (uint8 / int32 / int64) each; (S) or, labels_per_point != 0, (S, Nsrc).  NULL
+ *           together with labels_out: no labels
+ *   perm    int32[perm_len] or NULL (identity); cloud b of the batch is sample s = perm[start + b]
+ *   flags   CONV3P_PROVIDER_ROTATE | _JITTER | _SORT;  sigma >= 0, clip > 0 (looked at with JITTER)
+ *   cos_sin double (B, 2), noise double (B, N, 3): conv3p_augment_f32's, used with ROTATE / JITTER; NULL: drawn with
+ *           Philox4x32-10 as a function of (seed, step, s, source row) -- the recipe is in conv3p_provider.hpp
+ *
+ *   points (B, N, 3); input (B, N, K) = the sample's rows with xyz replaced by the augmented xyz; labels_out int32 (B) or
+ *   (B, N).  Optional (NULL: not written): cos_sin_out (B, 2), noise_out (B, N, 3) in source-row order, order_out int32
+ *   (B, N): the source row of every output row.  With SORT, rows and per-point labels are in the order of
+ *   conv3p_sort_xyz_order_f32 applied to the augmented xyz; N <= 8192 (CONV3P_ERR_UNSUPPORTED beyond, before any launch).
+ *   A sample index outside [0, S) is not read: the cloud's rows are 0, its labels -1, and bad_index[0] (int32, written
+ *   by every call that launches) counts such clouds.  B * N == 0: CONV3P_OK, nothing launched, nothing written.
+ *   Scratch from conv3p_provider_workspace_bytes (0 without SORT).  Bitwise reproducible; no output depends on a
+ *   cloud's position in the batch.
+ * ------------------------------------------------------------------------------------------- */
+#define CONV3P_PROVIDER_ROTATE 1
+#define CONV3P_PROVIDER_JITTER 2
+#define CONV3P_PROVIDER_SORT 4
+size_t conv3p_provider_workspace_bytes(int B, int N, int flags);
+int conv3p_provider_batch_f32(const float *data, const void *labels, int S, int Nsrc, int K, int label_bytes,
+                              int labels_per_point, const int32_t *perm, int64_t perm_len, int64_t start, int B, int N,
+                              int flags, double sigma, double clip, uint64_t seed, uint64_t step, const double *cos_sin,
+                              const double *noise, float *points, float *input, int32_t *labels_out, double *cos_sin_out,
+                              double *noise_out, int32_t *order_out, int32_t *bad_index, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:
  * view (B, N*36) -> fully_connected 512, selu -> dropout_selu -> fully_connected num_class, selu).
  * tf.contrib.layers.fully_connected is y = activation(x . W + b) with W of shape (K, N).

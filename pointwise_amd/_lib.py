@@ -30,6 +30,7 @@ CACHE_MATMUL_BF16 = 64            # matrix-core path: filter contractions in bf1
 ABI_VERSION = 5                # CONV3P_ABI_VERSION of include/conv3p.h
 STACK_MAX_LAYERS = 8
 OPT_MAX_TENSORS = 16             # CONV3P_OPT_MAX_TENSORS
+PROVIDER_ROTATE, PROVIDER_JITTER, PROVIDER_SORT = 1, 2, 4   # CONV3P_PROVIDER_*
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -90,6 +91,10 @@ SYMBOLS = {
     "conv3p_cls_tail_step_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, ctypes.c_uint64,
                                       ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
                                       ctypes.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_provider_workspace_bytes": (_sz, [_i, _i, _i]),
+    "conv3p_provider_batch_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

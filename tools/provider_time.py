@@ -1,0 +1,131 @@
+"""developer: time the fused batch provider (provider.assemble_batch: conv3p_provider_batch_f32, one launch) against
+the composition it replaces -- index the resident set with torch, draw B angles with numpy on the host and upload
+cos / sin, draw B x N x 3 float64 normals with torch.randn, prestep.rotate_and_jitter, prestep.sort_order_xyz and the
+gathers, the [:, :, 0:3] slice, the label cast -- at
+    32 x 2048 x 3    rotate + jitter + sort     (the classification model's batch)
+    128 x 4096 x 9   sort only                  (param.json's segmentation batch)
+    16 x 8192 x 12   sort only
+    32 x 2048 x 3    rotate + jitter, no sort
+
+Both in one process, alternated: 5 rounds x 20 calls each, us per call INCLUDING Python, a round timed with one pair
+of HIP events; every size is warmed up first; nothing synchronises inside a round.  Then the C entry point alone,
+200 back-to-back calls between one event pair.  For the two large sizes also the achieved bytes per second of
+(4 K + 12 + label bytes) * 2 per point (rows, points and labels, read and written), from the C call alone.
+Output: profiles/provider_time.txt (--out).
+
+    python tools/provider_time.py [--out profiles/provider_time.txt]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np
+import torch
+
+from pointwise_amd import _lib, prestep, provider
+
+# B, N, K, augment, sort, labels per point, samples in the resident set, what
+SIZES = ((32, 2048, 3, True, True, False, 256, "rotate + jitter + sort"),
+         (128, 4096, 9, False, True, True, 256, "sort only: param.json's segmentation batch"),
+         (16, 8192, 12, False, True, True, 64, "sort only"),
+         (32, 2048, 3, True, False, False, 256, "rotate + jitter, no sort"))
+ROUNDS, CALLS, BARE = 5, 20, 200
+
+
+def composition(data, labels, perm, start, B, augment, sort):
+    """What a user of prestep.py does per batch on the parent commit."""
+    idx = perm[start:start + B].long()
+    rows = data[idx]
+    lab = labels[idx]
+    xyz = rows if rows.shape[2] == 3 else rows[:, :, 0:3].contiguous()
+    if augment:
+        xyz = prestep.rotate_and_jitter(xyz)              # numpy angles + upload, torch.randn float64, one launch
+        rows = xyz if rows.shape[2] == 3 else torch.cat([xyz, rows[:, :, 3:]], dim=2)
+    if sort:
+        order = prestep.sort_order_xyz(rows)
+        rows = prestep._gather(rows, order)
+        if lab.dim() == 2:
+            lab = prestep._gather(lab, order)
+    return rows[:, :, 0:3].contiguous(), rows, lab.to(torch.int32)
+
+
+def timed(fn, calls=CALLS):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / calls      # us per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                                  "provider_time.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("provider_time: needs a HIP device")
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    lines = ["fused batch provider (one launch) vs the composition it replaces, %s" % torch.cuda.get_device_name(dev),
+             "us per call including Python; %d rounds x %d calls, alternated, HIP events; ratio = composition / fused per round"
+             % (ROUNDS, CALLS)]
+    for B, N, K, augment, sort, per_point, S, what in SIZES:
+        g = torch.Generator(device="cpu").manual_seed(B + N + K)
+        data = torch.rand(S, N, K, generator=g).to(dev)
+        labels = torch.randint(0, 13, (S, N) if per_point else (S,), generator=g).to(torch.uint8).to(dev)
+        perm = torch.from_numpy(np.random.default_rng(1).permutation(S).astype(np.int32)).to(dev)
+        bufs = [provider.BatchBuffers(B, N, K, per_point, dev, sort) for _ in range(2)]
+        step = [0]
+
+        def fused():
+            step[0] += 1
+            return provider.assemble_batch(data, labels, B, perm=perm, start=(step[0] * B) % (S - B + 1), rotate=augment,
+                                           jitter=augment, sort_cloud=sort, seed=1, step=step[0], out=bufs[step[0] & 1])
+
+        def comp():
+            step[0] += 1
+            return composition(data, labels, perm, (step[0] * B) % (S - B + 1), B, augment, sort)
+        for _ in range(5):
+            fused(), comp()
+        torch.cuda.synchronize()
+        tf, tc = [], []
+        for _ in range(ROUNDS):
+            tf.append(timed(fused))
+            tc.append(timed(comp))
+        # the C entry point alone
+        o = bufs[0]
+        flags = (3 if augment else 0) | (4 if sort else 0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = o.workspace
+        a = (data.data_ptr(), labels.data_ptr(), S, N, K, 1, int(per_point), perm.data_ptr(), S, 0, B, N, flags, 0.01, 0.05,
+             1, 7, None, None, o.points.data_ptr(), o.input.data_ptr(), o.labels.data_ptr(), None, None, None,
+             o.bad_index.data_ptr(), ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+
+        def bare():
+            if lib.conv3p_provider_batch_f32(*a) != _lib.OK:
+                raise SystemExit("provider_time: conv3p_provider_batch_f32 failed")
+        bare()
+        torch.cuda.synchronize()
+        tb = [timed(bare, BARE) for _ in range(3)]
+        lines.append("")
+        lines.append("B x N x K = %d x %d x %d  (%s)" % (B, N, K, what))
+        lines.append("  fused  (1 launch)          " + "  ".join("%8.1f" % v for v in tf))
+        lines.append("  composition                " + "  ".join("%8.1f" % v for v in tc))
+        lines.append("  ratio composition / fused  " + "  ".join("%8.2f" % (c / f) for f, c in zip(tf, tc)))
+        lines.append("  the C call alone, %d back to back, 3 rounds: " % BARE + "  ".join("%.1f" % v for v in tb) + " us")
+        if B * N >= 16 * 8192:
+            nbytes = (4 * K + 12 + (1 if per_point else 0)) * 2 * B * N
+            lines.append("  (4 K + 12 + label bytes) * 2 per point = %.2f MB: " % (nbytes / 1e6)
+                         + "  ".join("%.0f" % (nbytes / (v * 1e-6) / 1e9) for v in tb) + " GB/s")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
