@@ -475,6 +475,65 @@ int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, i
                         size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same head with the other arguments of the call it replaces,
+ * tf.losses.softmax_cross_entropy(onehot_labels, logits, weights, label_smoothing, reduction)
+ * (scene_seg/pointcnn_scene_seg_acsd.py:66-67), and the confusion matrix of an evaluation.  Kernels and the exact
+ * arithmetic: csrc/conv3p_seg_head_weighted.hpp.
+ *
+ * Row weight  w_r = [label in [0, num_class)] * class_weight[label] * point_weight[r]; class_weight (num_class) and
+ * point_weight (rows) are device arrays of the element type, either may be NULL (= 1).  Weights are NOT validated: a
+ * negative, infinite or NaN weight propagates to the total, *loss_sum and that row's gradient.
+ *
+ * conv3p_seg_weight_total_f32 / _f64   (pointcnn_scene_seg_acsd.py:66-67: the denominator of the `reduction`)
+ *   total = double[2] (device): {sum_r w_r, number of rows with w_r != 0}; reads labels and the weights only.  Two
+ *   launches, fixed summation order: equal inputs give equal bits.  total[0] is the denominator of torch's weighted
+ *   mean, total[1] that of TensorFlow's SUM_BY_NONZERO_WEIGHTS; a data-parallel caller all-reduces `total` first.
+ *
+ * conv3p_seg_head_weighted_f32 / _f64  (pointcnn_scene_seg_acsd.py:66-67: the loss itself)
+ *   conv3p_seg_head_* with, per valid row and ls = label_smoothing in [0, 1):
+ *     target q_c     = (1 - ls) [c == label] + ls / num_class       (TensorFlow's rule, not torch's class-weighted one)
+ *     row loss       = w_r * (logsumexp(act[r]) - (1 - ls) act[r][label] - (ls / num_class) sum_c act[r][c])
+ *     grad_act[r][c] = w_r * (softmax(act[r])_c - q_c) * scale
+ *     scale          = grad_scale, or with denominator != NULL (a device double, e.g. total + 0 or total + 1)
+ *                      grad_scale / *denominator, and 0 when *denominator == 0 (gradient all +0)
+ *     *loss_sum      = sum of the row losses (double, device), NOT scaled
+ *   A row with w_r == 0 has no loss and a +0 gradient row but still counts in seen / correct_class / predicted.  A
+ *   label outside [0, num_class) is an ignored row as in conv3p_seg_head_* (TensorFlow would charge such a row the
+ *   uniform part of a smoothed target; here it stays ignored).  pred, counts, the NaN / inf behaviour and the
+ *   reproducibility are those of conv3p_seg_head_*; with class_weight == point_weight == denominator == NULL and
+ *   label_smoothing == 0 every output is bit-equal to it.  No host synchronisation: the denominator is read on the
+ *   device.
+ *
+ * conv3p_seg_confusion                 (the evaluation of a model trained with pointcnn_scene_seg_acsd.py:66-67)
+ *   confusion = int64[num_class][num_class] (device): confusion[label][pred] over the rows whose label and pred are
+ *   both in [0, num_class); exact.  Two launches.
+ *
+ * Scratch: conv3p_seg_head_weighted_workspace_bytes covers conv3p_seg_weight_total_* and conv3p_seg_head_weighted_*
+ * (one buffer may serve both calls on one stream), conv3p_seg_confusion_workspace_bytes the matrix; 0 for a refused
+ * shape.  Status, decided before any launch: CONV3P_ERR_INVALID_ARGUMENT for rows == 0, num_class < 2, a NULL act /
+ * labels / loss_sum / counts (total; pred / confusion), label_smoothing outside [0, 1) or NaN; CONV3P_ERR_UNSUPPORTED
+ * above the class limit of conv3p_seg_head_* (fp32 and the confusion matrix 128, fp64 79); CONV3P_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+size_t conv3p_seg_head_weighted_workspace_bytes(size_t rows, int num_class);
+int conv3p_seg_weight_total_f32(const int32_t *labels, size_t rows, int num_class, const float *class_weight,
+                                const float *point_weight, double *total, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int conv3p_seg_weight_total_f64(const int32_t *labels, size_t rows, int num_class, const double *class_weight,
+                                const double *point_weight, double *total, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int conv3p_seg_head_weighted_f32(const float *act, const int32_t *labels, size_t rows, int num_class,
+                                 const float *class_weight, const float *point_weight, double label_smoothing,
+                                 float grad_scale, const double *denominator, float *grad_act, int32_t *pred,
+                                 double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_seg_head_weighted_f64(const double *act, const int32_t *labels, size_t rows, int num_class,
+                                 const double *class_weight, const double *point_weight, double label_smoothing,
+                                 double grad_scale, const double *denominator, double *grad_act, int32_t *pred,
+                                 double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+size_t conv3p_seg_confusion_workspace_bytes(size_t rows, int num_class);
+int conv3p_seg_confusion(const int32_t *labels, const int32_t *pred, size_t rows, int num_class, int64_t *confusion,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The optimizer step of all three training drivers: tf.train.MomentumOptimizer(learning_rate, momentum)
  * (train_modelnet40_acsd.py:81, scene_seg/train_scene_seg_s3dis.py:83, train_scene_seg_scenenn.py:86),
  * i.e. TensorFlow's non-Nesterov ApplyMomentum, in place, per element:

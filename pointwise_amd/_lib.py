@@ -81,6 +81,15 @@ SYMBOLS = {
     "conv3p_seg_head_workspace_bytes": (_sz, [_sz, _i]),
     "conv3p_seg_head_f32": (_i, [_vp, _vp, _sz, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_seg_head_f64": (_i, [_vp, _vp, _sz, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_seg_head_weighted_workspace_bytes": (_sz, [_sz, _i]),
+    "conv3p_seg_weight_total_f32": (_i, [_vp, _sz, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_seg_weight_total_f64": (_i, [_vp, _sz, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_seg_head_weighted_f32": (_i, [_vp, _vp, _sz, _i, _vp, _vp, ctypes.c_double, ctypes.c_float, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "conv3p_seg_head_weighted_f64": (_i, [_vp, _vp, _sz, _i, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "conv3p_seg_confusion_workspace_bytes": (_sz, [_sz, _i]),
+    "conv3p_seg_confusion": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
     "conv3p_momentum_step_f32": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp]),
     "conv3p_momentum_step_f64": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
     "conv3p_fc_backward_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float,

@@ -19,6 +19,7 @@
 #include "conv3p_prestep.hpp"
 #include "conv3p_head.hpp"
 #include "conv3p_seg_head.hpp"
+#include "conv3p_seg_head_weighted.hpp"
 #include "conv3p_optim.hpp"
 #include "conv3p_cls_tail.hpp"
 #include "conv3p_provider.hpp"
@@ -2795,6 +2796,69 @@ int seg_head_impl(const T *act, const int32_t *labels, size_t rows, int C, T gra
     return hip_ok();
 }
 
+// ----------------------------------------------------------------------------- the weighted segmentation head
+// (conv3p_seg_head_weighted.hpp).  All launches are accounted under K_SEG_HEAD.
+inline unsigned seg_total_grid(size_t rows)
+{
+    const size_t wgs = (rows + kSegTotalRowsPerWg - 1) / kSegTotalRowsPerWg;
+    return (unsigned)(wgs < (size_t)kSegTotalMaxGrid ? wgs : (size_t)kSegTotalMaxGrid);
+}
+inline unsigned seg_conf_grid(size_t rows)
+{
+    const size_t wgs = (rows + kSegConfRowsPerWg - 1) / kSegConfRowsPerWg;
+    return (unsigned)(wgs < (size_t)kSegConfMaxGrid ? wgs : (size_t)kSegConfMaxGrid);
+}
+inline size_t seg_total_bytes(size_t rows) { return up((size_t)seg_total_grid(rows) * sizeof(SegTotalRecord)); }
+
+template <typename T>
+int seg_weight_total_impl(const int32_t *labels, size_t rows, int C, const T *class_weight, const T *point_weight,
+                          double *total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (rows == 0 || C < 2 || !labels || !total) return CONV3P_ERR_INVALID_ARGUMENT;
+    SegPlan p;
+    if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, seg_total_bytes(rows)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SegTotalRecord *part = static_cast<SegTotalRecord *>(workspace);
+    const unsigned grid = seg_total_grid(rows);
+    {
+        Scope sc(K_SEG_HEAD, s);
+        hipLaunchKernelGGL(seg_weight_total_kernel<T>, dim3(grid), dim3(kSegTotalThreads), 0, s, labels, rows, C,
+                           class_weight, point_weight, part);
+        hipLaunchKernelGGL(seg_weight_total_finish_kernel, dim3(1), dim3(64), 0, s, part, (int)grid, total);
+    }
+    return hip_ok();
+}
+
+template <typename T>
+int seg_head_weighted_impl(const T *act, const int32_t *labels, size_t rows, int C, const T *class_weight,
+                           const T *point_weight, double smoothing, T grad_scale, const double *denominator, T *grad_act,
+                           int32_t *pred, double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes,
+                           void *stream)
+{
+    if (rows == 0 || C < 2 || !act || !labels || !loss_sum || !counts) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!(smoothing >= 0.0 && smoothing < 1.0)) return CONV3P_ERR_INVALID_ARGUMENT;   // also rejects NaN
+    const T ls = (T)smoothing;                                                         // what the kernel smooths with
+    if (!class_weight && !point_weight && ls == T(0) && !denominator)                  // the plain head, bit for bit
+        return seg_head_impl<T>(act, labels, rows, C, grad_scale, grad_act, pred, loss_sum, counts, workspace,
+                                workspace_bytes, stream);
+    SegPlan p;
+    if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, p.part_bytes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char *part = static_cast<char *>(workspace);
+    {
+        Scope sc(K_SEG_HEAD, s);
+        auto kern = ls != T(0) ? seg_head_weighted_kernel<T, true> : seg_head_weighted_kernel<T, false>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), p.lds, s, act, labels, rows, C, class_weight,
+                           point_weight, ls, grad_scale, denominator, grad_act, pred, part);
+        hipLaunchKernelGGL(seg_head_finish_kernel, dim3(1), dim3(kSegFinishThreads), 0, s, part, (int)p.grid, C, loss_sum,
+                           reinterpret_cast<long long *>(counts));
+    }
+    return hip_ok();
+}
+
 }  // namespace
 
 namespace {
@@ -3367,6 +3431,73 @@ int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, i
 {
     return seg_head_impl<double>(act, labels, rows, num_class, grad_scale, grad_act, pred, loss_sum, counts, workspace,
                                  workspace_bytes, stream);
+}
+
+size_t conv3p_seg_head_weighted_workspace_bytes(size_t rows, int num_class)
+{
+    const size_t head = conv3p_seg_head_workspace_bytes(rows, num_class);
+    if (head == 0) return 0;
+    const size_t total = seg_total_bytes(rows);
+    return head > total ? head : total;
+}
+int conv3p_seg_weight_total_f32(const int32_t *labels, size_t rows, int num_class, const float *class_weight,
+                                const float *point_weight, double *total, void *workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    return seg_weight_total_impl<float>(labels, rows, num_class, class_weight, point_weight, total, workspace,
+                                        workspace_bytes, stream);
+}
+int conv3p_seg_weight_total_f64(const int32_t *labels, size_t rows, int num_class, const double *class_weight,
+                                const double *point_weight, double *total, void *workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    return seg_weight_total_impl<double>(labels, rows, num_class, class_weight, point_weight, total, workspace,
+                                         workspace_bytes, stream);
+}
+int conv3p_seg_head_weighted_f32(const float *act, const int32_t *labels, size_t rows, int num_class,
+                                 const float *class_weight, const float *point_weight, double label_smoothing,
+                                 float grad_scale, const double *denominator, float *grad_act, int32_t *pred,
+                                 double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return seg_head_weighted_impl<float>(act, labels, rows, num_class, class_weight, point_weight, label_smoothing,
+                                         grad_scale, denominator, grad_act, pred, loss_sum, counts, workspace,
+                                         workspace_bytes, stream);
+}
+int conv3p_seg_head_weighted_f64(const double *act, const int32_t *labels, size_t rows, int num_class,
+                                 const double *class_weight, const double *point_weight, double label_smoothing,
+                                 double grad_scale, const double *denominator, double *grad_act, int32_t *pred,
+                                 double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return seg_head_weighted_impl<double>(act, labels, rows, num_class, class_weight, point_weight, label_smoothing,
+                                          grad_scale, denominator, grad_act, pred, loss_sum, counts, workspace,
+                                          workspace_bytes, stream);
+}
+
+size_t conv3p_seg_confusion_workspace_bytes(size_t rows, int num_class)
+{
+    if (rows == 0 || num_class < 2 || num_class > kSegMaxClass) return 0;
+    return up((size_t)seg_conf_grid(rows) * num_class * num_class * sizeof(int));
+}
+int conv3p_seg_confusion(const int32_t *labels, const int32_t *pred, size_t rows, int num_class, int64_t *confusion,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (rows == 0 || num_class < 2 || !labels || !pred || !confusion) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (num_class > kSegMaxClass || rows > ((size_t)1 << 36)) return CONV3P_ERR_UNSUPPORTED;   // (int32 partial counters)
+    TRY(buf_check(workspace, workspace_bytes, conv3p_seg_confusion_workspace_bytes(rows, num_class)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int *part = static_cast<int *>(workspace);
+    const unsigned grid = seg_conf_grid(rows);
+    const int cells = num_class * num_class;
+    const size_t lds = (size_t)cells * sizeof(int);
+    {
+        Scope sc(K_SEG_HEAD, s);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(seg_confusion_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(seg_confusion_kernel, dim3(grid), dim3(kSegConfThreads), lds, s, labels, pred, rows, num_class,
+                           part);
+        hipLaunchKernelGGL(seg_confusion_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, part,
+                           (int)grid, cells, reinterpret_cast<long long *>(confusion));
+    }
+    return hip_ok();
 }
 
 int conv3p_momentum_step_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
