@@ -571,6 +571,55 @@ int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float 
                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same step with the rest of the call it replaces: the use_nesterov argument of tf.train.MomentumOptimizer, the
+ * tf.clip_by_global_norm a TF1 driver puts between compute_gradients and apply_gradients, and a step that is not
+ * taken when a gradient holds a NaN or an Inf.  The norm is found on the device and used on the device: no host
+ * synchronisation.  Kernels and the exact arithmetic: csrc/conv3p_optim_guarded.hpp.
+ *
+ * conv3p_grad_norm_f32 / _f64   stats = double[2] (device): {sum over all elements of grad^2, number of elements that
+ *   are NaN or +-Inf}.  grads and numels are HOST arrays of n_tensors <= CONV3P_OPT_MAX_TENSORS entries as in
+ *   conv3p_momentum_step_*; a tensor of 0 elements is legal and its pointer may be NULL.  Squares and sums are double
+ *   (an fp32 square is exact), a non-finite element contributes 0 to stats[0] and 1 to stats[1]; when stats[0] itself
+ *   is not finite (fp64 squares can overflow) stats[1] is one larger, so stats[1] > 0 whenever stats[0] is unusable.
+ *   accumulate != 0 adds to what stats holds: more than 16 tensors, both element types or several calls chain in
+ *   stream order, e.g. f32(.., accumulate 0), f64(.., accumulate 1).  Two launches, no memset, no atomic, a grid that
+ *   depends on the element counts alone: equal arguments give equal bits (the result does depend on how tensors are
+ *   grouped into calls and on their alignment, within the rounding of a double sum of non-negative terms).
+ *   Nothing to read (n_tensors == 0 or all counts zero): accumulate == 0 writes {0, 0} (one launch), accumulate != 0
+ *   launches nothing.  Scratch: conv3p_grad_norm_workspace_bytes(), needed only when there is something to read.
+ *   Status, decided before any launch: n_tensors out of range, NULL stats, a NULL array (n_tensors > 0), a NULL or
+ *   misaligned entry with a non-zero count -> CONV3P_ERR_INVALID_ARGUMENT; CONV3P_ERR_WORKSPACE.
+ *
+ * conv3p_momentum_step_guarded_f32 / _f64   conv3p_momentum_step_* with, uniformly over the call:
+ *   skip   skip_nonfinite != 0 and stats[1] > 0: nothing is read or written, params and accums keep their bits
+ *   clip   clip_norm > 0: grad' = grad * scale (one rounded multiply), scale = (T)(clip_norm / max(sqrt(stats[0]),
+ *          clip_norm)) with sqrt and division correctly rounded in double and one rounding to the element type;
+ *          exactly 1 (the step is bit-equal to the unclipped one) when the norm is at most clip_norm, 0 when stats[0]
+ *          is not finite.  clip_norm <= 0: no clipping
+ *   rule   nesterov == 0: the rule above.  nesterov != 0: TensorFlow's ApplyMomentum with use_nesterov,
+ *            accum = accum * momentum + grad'
+ *            param = param - (grad' * lr + (accum * momentum) * lr)
+ *          every product and sum separately rounded: bit-equal to numpy evaluating these statements in the element type
+ *   stats is the device double[2] of conv3p_grad_norm_* (or those of all ranks, summed); it is read only when clipping
+ *   or skipping is asked for and may be NULL otherwise.  With nesterov == 0, clip_norm <= 0 and skip_nonfinite == 0 the
+ *   call is conv3p_momentum_step_*: the same kernel, the same bits.  Without skipping, a NaN or Inf in grad reaches
+ *   its element as before (it is not part of the norm).  One launch.
+ *   Status, decided before any launch: those of conv3p_momentum_step_*; a NaN or infinite clip_norm, or stats == NULL
+ *   with clip_norm > 0 or skip_nonfinite != 0 -> CONV3P_ERR_INVALID_ARGUMENT.
+ * ------------------------------------------------------------------------------------------- */
+size_t conv3p_grad_norm_workspace_bytes(void);
+int conv3p_grad_norm_f32(int n_tensors, const float *const *grads, const size_t *numels, double *stats, int accumulate,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_grad_norm_f64(int n_tensors, const double *const *grads, const size_t *numels, double *stats, int accumulate,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_momentum_step_guarded_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
+                                     const size_t *numels, float lr, float momentum, int nesterov, float clip_norm,
+                                     int skip_nonfinite, const double *stats, void *stream);
+int conv3p_momentum_step_guarded_f64(int n_tensors, double *const *params, const double *const *grads,
+                                     double *const *accums, const size_t *numels, double lr, double momentum, int nesterov,
+                                     double clip_norm, int skip_nonfinite, const double *stats, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The tail of the classification model's training step as two launches: everything between fc1's output and fc1's
  * backward (/root/reference/pointcnn2_acsd.py:73-90: dropout_selu, fully_connected num_class selu, mean sparse softmax
  * cross-entropy; /root/reference/selu.py:35-70), the statistics of /root/reference/train_modelnet40_acsd.py:136-146

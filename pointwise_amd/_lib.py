@@ -94,6 +94,13 @@ SYMBOLS = {
     "conv3p_momentum_step_f64": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
     "conv3p_fc_backward_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float,
                                          _vp, _sz, _vp]),
+    "conv3p_grad_norm_workspace_bytes": (_sz, []),
+    "conv3p_grad_norm_f32": (_i, [_i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "conv3p_grad_norm_f64": (_i, [_i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "conv3p_momentum_step_guarded_f32": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, ctypes.c_float,
+                                              _i, _vp, _vp]),
+    "conv3p_momentum_step_guarded_f64": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i,
+                                              ctypes.c_double, _i, _vp, _vp]),
     "conv3p_cls_tail_workspace_bytes": (_sz, [_i, _i, _i]),
     "conv3p_cls_tail_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, ctypes.c_uint64, ctypes.c_uint64,
                                  ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -21,6 +21,7 @@
 #include "conv3p_seg_head.hpp"
 #include "conv3p_seg_head_weighted.hpp"
 #include "conv3p_optim.hpp"
+#include "conv3p_optim_guarded.hpp"
 #include "conv3p_cls_tail.hpp"
 #include "conv3p_provider.hpp"
 
@@ -2864,15 +2865,11 @@ int seg_head_weighted_impl(const T *act, const int32_t *labels, size_t rows, int
 namespace {
 static_assert(kOptMaxTensors == CONV3P_OPT_MAX_TENSORS, "conv3p_optim.hpp and conv3p.h disagree");
 
-// status first, then (only if there is anything to do) the table by value and one launch
+// The table of a launch from the host arrays: CONV3P_ERR_INVALID_ARGUMENT for a NULL or misaligned entry with a non-zero
+// count; tab.chunks == 0 when there is nothing to do.
 template <typename T>
-int momentum_step_impl(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, T lr,
-                       T momentum, void *stream)
+int opt_table(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, OptTable<T> &tab)
 {
-    if (n < 0 || n > kOptMaxTensors) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (n == 0) return CONV3P_OK;
-    if (!params || !grads || !accums || !numels) return CONV3P_ERR_INVALID_ARGUMENT;
-    OptTable<T> tab;
     size_t chunks = 0;
     for (int i = 0; i < kOptMaxTensors; ++i) {
         const size_t ne = i < n ? numels[i] : 0;
@@ -2889,11 +2886,79 @@ int momentum_step_impl(int n, T *const *params, const T *const *grads, T *const 
         chunks += (ne + kOptChunk - 1) / kOptChunk;
         tab.chunk_end[i] = chunks;
     }
-    if (chunks == 0) return CONV3P_OK;
     tab.chunks = chunks;
-    const unsigned grid = (unsigned)(chunks < (size_t)kOptMaxGrid ? chunks : (size_t)kOptMaxGrid);
-    hipLaunchKernelGGL(momentum_step_kernel<T>, dim3(grid), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream), tab, lr,
-                       momentum);
+    return CONV3P_OK;
+}
+inline unsigned opt_grid(size_t chunks) { return (unsigned)(chunks < (size_t)kOptMaxGrid ? chunks : (size_t)kOptMaxGrid); }
+
+// status first, then (only if there is anything to do) the table by value and one launch
+template <typename T>
+int momentum_step_impl(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, T lr,
+                       T momentum, void *stream)
+{
+    if (n < 0 || n > kOptMaxTensors) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (n == 0) return CONV3P_OK;
+    if (!params || !grads || !accums || !numels) return CONV3P_ERR_INVALID_ARGUMENT;
+    OptTable<T> tab;
+    TRY(opt_table<T>(n, params, grads, accums, numels, tab));
+    if (tab.chunks == 0) return CONV3P_OK;
+    hipLaunchKernelGGL(momentum_step_kernel<T>, dim3(opt_grid(tab.chunks)), dim3(kOptThreads), 0,
+                       static_cast<hipStream_t>(stream), tab, lr, momentum);
+    return hip_ok();
+}
+
+// The guarded step.  Without Nesterov and without a use for stats this IS momentum_step_impl: the same instantiation
+// of momentum_step_kernel, so the defaults cost and compute what they did.
+template <typename T>
+int momentum_step_guarded_impl(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, T lr,
+                               T momentum, int nesterov, T clip_norm, int skip_nonfinite, const double *stats, void *stream)
+{
+    if (n < 0 || n > kOptMaxTensors) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite((double)clip_norm)) return CONV3P_ERR_INVALID_ARGUMENT;
+    const bool clip = clip_norm > T(0), guarded = clip || skip_nonfinite != 0;
+    if (guarded && !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!nesterov && !guarded) return momentum_step_impl<T>(n, params, grads, accums, numels, lr, momentum, stream);
+    if (n == 0) return CONV3P_OK;
+    if (!params || !grads || !accums || !numels) return CONV3P_ERR_INVALID_ARGUMENT;
+    OptTable<T> tab;
+    TRY(opt_table<T>(n, params, grads, accums, numels, tab));
+    if (tab.chunks == 0) return CONV3P_OK;
+    auto kern = nesterov ? momentum_step_guarded_kernel<T, true> : momentum_step_guarded_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(opt_grid(tab.chunks)), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream), tab, lr,
+                       momentum, guarded ? stats : nullptr, clip ? clip_norm : T(0), skip_nonfinite ? 1 : 0);
+    return hip_ok();
+}
+
+// grad_sumsq_kernel + grad_sumsq_finish_kernel; with nothing to read only the finish runs (stats = 0), and with
+// accumulate nothing at all.  Outside the profile bracket, as momentum_step_kernel.
+inline size_t grad_norm_bytes() { return up((size_t)kOptMaxGrid * sizeof(GradNormRecord)); }
+
+template <typename T>
+int grad_norm_impl(int n, const T *const *grads, const size_t *numels, double *stats, int accumulate, void *workspace,
+                   size_t workspace_bytes, void *stream)
+{
+    if (n < 0 || n > kOptMaxTensors || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (n > 0 && (!grads || !numels)) return CONV3P_ERR_INVALID_ARGUMENT;
+    GradTable<T> tab;
+    size_t chunks = 0;
+    for (int i = 0; i < kOptMaxTensors; ++i) {
+        const size_t ne = i < n ? numels[i] : 0;
+        if (ne != 0 && (!grads[i] || (reinterpret_cast<size_t>(grads[i]) & (sizeof(T) - 1)) != 0))
+            return CONV3P_ERR_INVALID_ARGUMENT;
+        tab.grad[i] = ne ? grads[i] : nullptr;
+        tab.numel[i] = ne;
+        chunks += (ne + kOptChunk - 1) / kOptChunk;
+        tab.chunk_end[i] = chunks;
+    }
+    tab.chunks = chunks;
+    if (chunks == 0 && accumulate) return CONV3P_OK;
+    if (chunks != 0) TRY(buf_check(workspace, workspace_bytes, grad_norm_bytes()));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GradNormRecord *part = static_cast<GradNormRecord *>(workspace);
+    const unsigned grid = opt_grid(chunks);
+    if (grid != 0) hipLaunchKernelGGL(grad_sumsq_kernel<T>, dim3(grid), dim3(kOptThreads), 0, s, tab, part);
+    hipLaunchKernelGGL(grad_sumsq_finish_kernel, dim3(1), dim3(kGradFinishThreads), 0, s, part, (int)grid,
+                       accumulate ? 1 : 0, stats);
     return hip_ok();
 }
 }  // namespace
@@ -3511,6 +3576,31 @@ int conv3p_momentum_step_f64(int n_tensors, double *const *params, const double 
     return momentum_step_impl<double>(n_tensors, params, grads, accums, numels, lr, momentum, stream);
 }
 
+size_t conv3p_grad_norm_workspace_bytes(void) { return grad_norm_bytes(); }
+int conv3p_grad_norm_f32(int n_tensors, const float *const *grads, const size_t *numels, double *stats, int accumulate,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grad_norm_impl<float>(n_tensors, grads, numels, stats, accumulate, workspace, workspace_bytes, stream);
+}
+int conv3p_grad_norm_f64(int n_tensors, const double *const *grads, const size_t *numels, double *stats, int accumulate,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grad_norm_impl<double>(n_tensors, grads, numels, stats, accumulate, workspace, workspace_bytes, stream);
+}
+int conv3p_momentum_step_guarded_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
+                                     const size_t *numels, float lr, float momentum, int nesterov, float clip_norm,
+                                     int skip_nonfinite, const double *stats, void *stream)
+{
+    return momentum_step_guarded_impl<float>(n_tensors, params, grads, accums, numels, lr, momentum, nesterov, clip_norm,
+                                             skip_nonfinite, stats, stream);
+}
+int conv3p_momentum_step_guarded_f64(int n_tensors, double *const *params, const double *const *grads,
+                                     double *const *accums, const size_t *numels, double lr, double momentum, int nesterov,
+                                     double clip_norm, int skip_nonfinite, const double *stats, void *stream)
+{
+    return momentum_step_guarded_impl<double>(n_tensors, params, grads, accums, numels, lr, momentum, nesterov, clip_norm,
+                                              skip_nonfinite, stats, stream);
+}
 int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float *y, const float *dy, int M, int K, int N,
                                 int act, float *dx, float *accum_W, float *accum_b, float lr, float momentum,
                                 void *workspace, size_t workspace_bytes, void *stream)

@@ -254,7 +254,9 @@ class ClassificationHead:
         optimizer (an optim.MomentumOptimizer that owns W1 and b1; single-GPU runs): fc1's gradient pass applies the
         update itself (optimizer.fused_fc_step) -- W1 and b1 are stepped on return, dW1 / db1 are NOT written and
         gradients() reports None for them; W2, b2 and everything else are the caller's optimizer.step().  Data-parallel
-        runs keep the default: the gradient has to cross ranks before anything is updated."""
+        runs keep the default: the gradient has to cross ranks before anything is updated.  So does an optimizer that
+        is not `fusable` (use_nesterov, clip_norm, skip_nonfinite: its step needs every gradient first): dW1 / db1 are
+        written and optimizer.step(gradients) updates everything."""
         view, fc1, drop, mask, fc2, shape = self._saved
         ddrop, _, _ = fully_connected_grad(drop, self.W2, fc2, dlogits, selu=True, dW_out=self.dW2, db_out=self.db2)
         if mask is not None:
@@ -266,7 +268,7 @@ class ClassificationHead:
         return self._fc1_backward(view, fc1, dfc1, optimizer).reshape(shape)
 
     def _fc1_backward(self, view, fc1, dfc1, optimizer):
-        self._fc1_stepped = optimizer is not None and optimizer.owns(self.W1, self.b1)
+        self._fc1_stepped = optimizer is not None and optimizer.fusable and optimizer.owns(self.W1, self.b1)
         if self._fc1_stepped:
             return optimizer.fused_fc_step(view.contiguous(), self.W1, self.b1, fc1, dfc1.contiguous(), selu=True)
         dview, _, _ = fully_connected_grad(view, self.W1, fc1, dfc1, selu=True, dW_out=self.dW1, db_out=self.db1)
@@ -290,7 +292,8 @@ class ClassificationHead:
         device from (seed, step): seed defaults to the constructor's, step to the number of forward_backward() calls
         before this one that were not given a step.  Gradients land in dW1, db1, dW2, db2 -- except what `optimizer` (an
         optim.MomentumOptimizer) owns: W1 / b1 are stepped by fc1's gradient pass as in backward(), W2 / b2 by the
-        tail's second launch, and gradients() reports None for them.  The global step is the caller's
+        tail's second launch, and gradients() reports None for them (an optimizer that is not `fusable` owns nothing in
+        this sense: all four gradients are written for its step()).  The global step is the caller's
         optimizer.step(gradients...) to advance.  counts() / accumulate() / summary() refer to this call; its logits
         and predictions stay in .logits / .pred."""
         self._check_batch(feat, labels)
@@ -301,7 +304,7 @@ class ClassificationHead:
             self._calls += 1
         view = feat.reshape(B, -1)
         fc1 = fully_connected(view, self.W1, self.b1, selu=True)
-        own2 = optimizer is not None and optimizer.owns(self.W2, self.b2)
+        own2 = optimizer is not None and optimizer.fusable and optimizer.owns(self.W2, self.b2)
         kw = {}
         if own2:
             _require(optimizer.accums[optimizer._index(self.W2, "W2")].numel() == self.W2.numel(),
