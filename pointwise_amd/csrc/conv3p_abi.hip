@@ -403,6 +403,8 @@ template <typename T> struct Call {
     const T *addend = nullptr;
     RowLd ld{0, 0, 0, 0, 0};       // row strides of the feature tensors; filled with the dense values by set_ld()
     bool strided = false;          // some tensor is a column block of a wider buffer (register-path shapes only)
+    ReduceJob<T> rider{};          // stack backward, register kernels: partials of the layer above, summed by workgroups
+                                   // appended to this call's first backward launch (reduce_rider); nslots == 0: none
 };
 
 template <typename T> void set_ld(Call<T> &c, const RowLd *ld, int Cin, int Cout)
@@ -817,6 +819,17 @@ template <typename T> Stencil<T> undilated_stencil(const Dims &d)
     return make_stencil<T>(d, one, (T)1);
 }
 
+// workgroups a launch appends for its reduction rider (reduce_rider, conv3p_kernels.hpp)
+template <typename T> inline unsigned rider_grid(const ReduceJob<T> &rider)
+{
+    return rider.nslots > 0 ? rider_blocks(rider.nw) : 0u;
+}
+// the first backward launch of a Register route can carry a rider: its dynamic LDS holds the rider's [16][kRiderW] sums
+template <typename T> inline bool rider_fits(const Route &r)
+{
+    return (r.cap > 0 ? r.sparse_lds : r.lds) >= (size_t)16 * kRiderW * sizeof(T);
+}
+
 // The populated-rows kernel: narrow dilated layers when the pair lists are short, layers of >= 16 inputs always (their
 // dense G plus the transposed filter take 151 KiB of LDS, one workgroup per CU; the populated rows fit two), and filters
 // whose dense G does not fit LDS at all.  regime: launched for the short-lists case only -- the dense-G kernel follows and
@@ -834,11 +847,11 @@ int launch_backward_sparse(const Call<T> &c, const Route &r, const T *grad_out, 
         Scope sc(K_BACKWARD, c.s);
         auto go = [&](auto kern) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.sparse_lds);
-            hipLaunchKernelGGL(kern, dim3(grid_of(bm)), dim3(256), r.sparse_lds, c.s, c.L.pts, c.L.boxes,
+            hipLaunchKernelGGL(kern, dim3(grid_of(bm) + rider_grid(c.rider)), dim3(256), r.sparse_lds, c.s, c.L.pts, c.L.boxes,
                                S.count, S.pairs, S.segs, S.qsegs, S.qbm, S.qbm_hi, grad_out, input, filter, st, d.N, d.ntiles, c.L.ngroups,
                                bm, grad_input, partials, (c.act ? 1 : 0) | (c.accum ? 2 : 0), c.addend,
                                st.window ? c.L.cmin : nullptr, c.ld, r.cap, sched_of(S),
-                               r.regime ? S.regime : static_cast<const uint32_t *>(nullptr));
+                               r.regime ? S.regime : static_cast<const uint32_t *>(nullptr), c.rider, grid_of(bm));
         };
         if constexpr (CI < 16) {
             if (st.ntap > 64) go(backward_sparse_kernel<T, CI, CO, 2>);        // 128-bit tap sets
@@ -856,7 +869,8 @@ int launch_backward_sparse(const Call<T> &c, const Route &r, const T *grad_out, 
 // The dense-G kernel (CI == 0: its generic form).  lds: the route's (plan_backward); regime: see launch_backward_sparse.
 template <typename T, int CI, int CO>
 int launch_backward(const Call<T> &c, size_t lds, const T *grad_out, const T *input, const T *filter, T *grad_input,
-                    T *partials, const uint8_t *only_flagged = nullptr, int gen_slots = 1, const uint32_t *regime = nullptr)
+                    T *partials, const uint8_t *only_flagged = nullptr, int gen_slots = 1, const uint32_t *regime = nullptr,
+                    const ReduceJob<T> &rider = ReduceJob<T>{})
 {
     const Dims &d = c.d;
     const Stencil<T> &st = c.st;
@@ -865,11 +879,11 @@ int launch_backward(const Call<T> &c, size_t lds, const T *grad_out, const T *in
     Scope sc(CI == 0 && only_flagged == nullptr ? K_GENERIC_BWD : K_BACKWARD, c.s);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(backward_kernel<T, CI, CO>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((backward_kernel<T, CI, CO>), dim3(grid_of(bm)), dim3(256), lds, c.s, c.L.pts, c.L.boxes,
+    hipLaunchKernelGGL((backward_kernel<T, CI, CO>), dim3(grid_of(bm) + rider_grid(rider)), dim3(256), lds, c.s, c.L.pts, c.L.boxes,
                        S.count, S.pairs, S.segs, S.qsegs, grad_out, input, filter, st, d.N, d.ntiles, c.L.ngroups,
                        d.Cin, d.Cout, bm, grad_input, partials, only_flagged,
                        ((CI > 0 && c.act) ? 1 : 0) | ((CI > 0 && c.accum) ? 2 : 0), c.addend, gen_slots,
-                       st.window ? c.L.cmin : nullptr, c.ld, sched_of(S), regime);
+                       st.window ? c.L.cmin : nullptr, c.ld, sched_of(S), regime, rider, grid_of(bm));
     return hip_ok();
 }
 
@@ -885,8 +899,9 @@ int register_backward(const Call<T> &c, const Route &r, const T *grad_out, const
 {
     if (r.cap > 0) TRY((launch_backward_sparse<T, CI, CO>(c, r, grad_out, input, filter, grad_input, partials)));
     if (r.cap > 0 && !r.regime) return CONV3P_OK;
+    // (a rider goes with the call's FIRST launch: the populated-rows kernel's when there is one)
     return launch_backward<T, CI, CO>(c, r.lds, grad_out, input, filter, grad_input, partials, nullptr, 1,
-                                      r.cap > 0 ? c.L.slot[c.slot].regime : nullptr);
+                                      r.cap > 0 ? c.L.slot[c.slot].regime : nullptr, r.cap > 0 ? ReduceJob<T>{} : c.rider);
 }
 template <typename T> struct RegisterShape {
     int cin, cout;
@@ -1809,11 +1824,13 @@ template <typename T> void note_companions_built(const Call<T> &c, const FusedJo
             if (sl != c.slot && h.tags[sl] == fj.job[k].cc.tag) h.built_gen[sl] = h.gen;
 }
 
-// Stack-level backward: a layer's grad_filter partials stay in the caller's region and are reduced later, together
-// with the other layers', by one reduce_multi_kernel launch.
+// Stack-level backward: a layer's grad_filter partials stay in the caller's region and are reduced later -- by the rider
+// workgroups of the next layer's launch, or by the stack's closing reduction.
 template <typename T> struct DeferredReduce {
     T *region = nullptr;      // in: where this layer's partials go (>= reduce_region_bytes)
     ReduceJob<T> job{};       // out: what to reduce (nslots == 0: the layer reduced its grad_filter itself)
+    ReduceJob<T> ride{};      // in: partials of the layer above, complete when this layer's launches start (nslots == 0: none)
+    bool rode = false;        // out: this layer's first launch sums `ride` (register kernels; else it stays the caller's)
 };
 
 template <typename T> int selu_impl(const T *x, T *y, size_t n, void *stream);
@@ -2056,6 +2073,10 @@ int backward_impl(const T *grad_out, const T *points, const T *input, const T *f
     TRY(run_prep<T>(points, c));
     TRY(run_cloud_min<T>(points, c));
     TRY(run_search<T>(c, c.L.slot[c.slot].count, true));
+    if (defer && defer->ride.nslots > 0 && r.family == Family::Register && rider_fits<T>(r)) {
+        c.rider = defer->ride;
+        defer->rode = true;
+    }
     // the register kernels leave per-workgroup grad_filter partials: in the stack's region when it reduces them later
     T *partials = defer && !r.self_reduces ? defer->region : c.L.partials;
     switch (r.family) {
@@ -2677,7 +2698,9 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
     T *ga = reinterpret_cast<T *>(sp);
     T *gb = reinterpret_cast<T *>(sp + up(rows * wide * sizeof(T)));
     T *dconcat = reinterpret_cast<T *>(sp + 2 * up(rows * wide * sizeof(T)));
-    // every layer leaves its grad_filter partials in its own region; ONE launch reduces them all at the end, so the
+    // every layer leaves its grad_filter partials in its own region.  The per-layer path: a layer's partials are summed by
+    // rider workgroups of the NEXT layer's launch (reduce_rider: stream order makes them complete and visible there), and
+    // one closing launch reduces what no launch carried -- the first layer's, and those of layers on other kernels; so the
     // chain of dependent backward kernels is not interleaved with reductions
     DeferredReduce<T> red[CONV3P_STACK_MAX_LAYERS + 1];
     {
@@ -2700,13 +2723,28 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
         if (nj == 0) return CONV3P_OK;
         hipStream_t s = static_cast<hipStream_t>(stream);
         Scope sc(K_REDUCE, s);
-        hipLaunchKernelGGL(reduce_multi_kernel<T>, dim3(gx, (unsigned)nj), dim3(1024), 0, s, jobs);
+        // one layer left (the riders took the others): 16 weights per workgroup -- a few MB are bound by the chain of
+        // dependent loads, which is a quarter as long there (same summation order, same bits: reduce_slots)
+        if (nj == 1)
+            hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3((jobs.job[0].nw + kReduceW - 1) / kReduceW), dim3(1024), 0, s,
+                               jobs.job[0].partials, jobs.job[0].nslots, (size_t)jobs.job[0].nw, jobs.job[0].grad_filter);
+        else
+            hipLaunchKernelGGL(reduce_multi_kernel<T>, dim3(gx, (unsigned)nj), dim3(1024), 0, s, jobs);
         return hip_ok();
     };
     auto where = [&]() {
         return persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
                           cfg->max_Cin, cfg->max_Cout,
                           CONV3P_CACHE_POINTS_UNCHANGED | (cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS)));
+    };
+    int pending = -1;   // the layer whose partials wait for a launch to ride in
+    auto ride = [&](int l) {
+        red[l].ride = pending >= 0 ? red[pending].job : ReduceJob<T>{};
+        red[l].rode = false;
+    };
+    auto rode = [&](int l) {
+        if (red[l].rode) red[pending].job.nslots = 0;   // (summed inside layer l's launch: nothing left for reduce_all)
+        pending = red[l].job.nslots > 0 ? l : -1;
     };
     // external gradient of the concat's column blocks: the caller's, the head's, or their sum
     const T *ext = grad_concat;
@@ -2717,6 +2755,7 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
         TRY(backward_impl<T>(ga, points, concat, filters[nh], sd->strides[nh], voxel, B, N, CW, sd->num_class, sd->fz,
                              sd->fy, sd->fx, dconcat, grad_filters[nh], where(), stream, false, nullptr, nullptr,
                              &red[nh]));
+        pending = red[nh].job.nslots > 0 ? nh : -1;
         ext = dconcat;
     }
     // the hidden layers nh-1 .. 1 as ONE launch (conv3p_stack_fused.hpp) where the stack, the cache and the device allow it
@@ -2744,13 +2783,17 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
         // grad wrt the argument of the SELU that produced act_{l-1}: (dX + ext_{l-1}) * selu'(act_{l-1})
         const RowLd ld{CW, 0, H, H, ld_ext};
         const int Cin = H;
+        ride(l);
         TRY(backward_impl<T>(g, points, concat + (size_t)H * (l - 1), filters[l], sd->strides[l], voxel, B, N, Cin, H,
                              sd->fz, sd->fy, sd->fx, gn, grad_filters[l], where(), stream, /*act=*/true,
                              ext + (size_t)H * (l - 1), &ld, &red[l]));
+        rode(l);
         T *t = g; g = gn; gn = t;
     }
+    ride(0);
     TRY(backward_impl<T>(g, points, input, filters[0], sd->strides[0], voxel, B, N, sd->in_channels, H, sd->fz, sd->fy,
                          sd->fx, grad_input, grad_filters[0], where(), stream, false, nullptr, nullptr, &red[0]));
+    rode(0);
     return reduce_all();
 }
 

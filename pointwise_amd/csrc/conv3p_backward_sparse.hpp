@@ -885,9 +885,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((!BIG && (C
     const T *__restrict__ filter, Stencil<T> st, int N, int ntiles, int ngroups, BlockMap bm, T *__restrict__ grad_input,
     T *__restrict__ partials, int act, const T *__restrict__ addend, const T *__restrict__ cmin, RowLd ld, int cap,
     const uint32_t *__restrict__ sched,   // launch order of the tiles (tile_sched_kernel) or nullptr
-    const uint32_t *__restrict__ regime)  // non-null: run only if the slot's lists are SHORT (*regime == 1, tile_sched_kernel);
+    const uint32_t *__restrict__ regime,  // non-null: run only if the slot's lists are SHORT (*regime == 1, tile_sched_kernel);
                                           // the host then launches backward_kernel too, which runs in the other case
+    ReduceJob<T> rider, unsigned ntile_blocks)   // rider.nslots > 0: the workgroups from ntile_blocks on are reduction riders
+                                                 // (reduce_rider, conv3p_kernels.hpp) -- whatever the regime word says
 {
+    if (blockIdx.x >= ntile_blocks) {   // (uniform)
+        extern __shared__ __attribute__((aligned(16))) char smem[];
+        reduce_rider<T>(rider, blockIdx.x - ntile_blocks, reinterpret_cast<T *>(smem));
+        return;
+    }
     if (regime != nullptr && *regime != 1u) return;   // (uniform)
     int b, qt;
     const bool live = block_to_tile(bm, sched, ntiles, b, qt);   // uniform for the workgroup

@@ -832,6 +832,58 @@ __device__ __forceinline__ bool block_to_tile(const BlockMap &m, const uint32_t 
     return true;
 }
 
+// One layer's grad_filter partials and where their sum goes (reduce_multi_kernel, reduce_rider).
+template <typename T> struct ReduceJob {
+    const T *partials;
+    T *grad_filter;
+    int nslots;
+    unsigned nw;
+};
+// One stripe (slot mod 64) of weight e, summed 64 slots apart into four interleaved accumulators: the summation order of
+// reduce_slots (below), shared with reduce_rider.
+template <typename T>
+__device__ __forceinline__ T reduce_stripe_sum(const T *__restrict__ partials, int nslots, size_t nw, size_t e, int stripe)
+{
+    T s0 = (T)0, s1 = (T)0, s2 = (T)0, s3 = (T)0;
+    int p = stripe;
+    for (; p + 192 < nslots; p += 256) {
+        s0 += partials[(size_t)p * nw + e];
+        s1 += partials[(size_t)(p + 64) * nw + e];
+        s2 += partials[(size_t)(p + 128) * nw + e];
+        s3 += partials[(size_t)(p + 192) * nw + e];
+    }
+    for (; p < nslots; p += 64) s0 += partials[(size_t)p * nw + e];
+    return (s0 + s1) + (s2 + s3);
+}
+// Reduction riders of the stack backward: workgroups appended AFTER the tile workgroups of a layer's backward launch sum
+// the partials the layer above left (complete and visible: that launch came earlier on the stream) -- they enter the
+// CUs as the first tiles leave and run in the launch's tail, instead of a launch of their own behind the last layer.
+// A rider workgroup (256 threads) serves kRiderW = 16 consecutive weights: thread = (weight, "wave" w of reduce_slots),
+// the thread runs the stripes 4w .. 4w + 3 itself, (t0 + t2) + (t1 + t3), the 16 w meet through LDS in ascending order:
+// reduce_slots' summation order, the same bits.  part: [16][kRiderW] values of LDS (the launch's dynamic LDS, which a
+// rider workgroup uses for nothing else).
+constexpr int kRiderW = 16;
+inline unsigned rider_blocks(unsigned nw) { return (nw + (unsigned)kRiderW - 1u) / (unsigned)kRiderW; }
+template <typename T> __device__ __forceinline__ void reduce_rider(const ReduceJob<T> &j, unsigned block, T *part)
+{
+    const int wl = threadIdx.x & (kRiderW - 1), w = threadIdx.x >> 4;
+    const size_t nw = (size_t)j.nw, e = (size_t)block * kRiderW + wl;
+    T s = (T)0;
+    if (e < nw) {
+        const T t0 = reduce_stripe_sum(j.partials, j.nslots, nw, e, w * 4), t1 = reduce_stripe_sum(j.partials, j.nslots, nw, e, w * 4 + 1),
+                t2 = reduce_stripe_sum(j.partials, j.nslots, nw, e, w * 4 + 2), t3 = reduce_stripe_sum(j.partials, j.nslots, nw, e, w * 4 + 3);
+        s = (t0 + t2) + (t1 + t3);
+    }
+    part[w * kRiderW + wl] = s;
+    __syncthreads();
+    if (w == 0 && e < nw) {
+        T t = part[wl];
+#pragma unroll
+        for (int v = 1; v < 16; ++v) t += part[v * kRiderW + wl];
+        j.grad_filter[e] = t;
+    }
+}
+
 // LDS layout of the forward kernel's filter copy (register path).  fp32: a tap's block is [Cin][Cout rounded up to
 // even], so that a lane reads two consecutive output channels' weights with ONE aligned 8-byte access (ds_read_b64:
 // 256 B / clk against 128 for 4-byte reads -- the walk's 81 weight reads per record were 80 % of the LDS's cycles and
@@ -1258,14 +1310,20 @@ __global__ __launch_bounds__(256) void backward_kernel(
                                              // spread their atomics over (slot = workgroup % gen_slots)
     const T *__restrict__ cmin,              // per-cloud grid origin (window-mode stencils, overflow path only)
     RowLd ld, const uint32_t *__restrict__ sched,   // sched: launch order of the tiles (tile_sched_kernel) or nullptr
-    const uint32_t *__restrict__ regime)            // non-null: run only if the slot's lists are LONG (*regime == 0); the
+    const uint32_t *__restrict__ regime,            // non-null: run only if the slot's lists are LONG (*regime == 0); the
                                                     // populated-rows kernel was launched for the other case
+    ReduceJob<T> rider, unsigned ntile_blocks)      // rider.nslots > 0: the workgroups from ntile_blocks on are reduction
+                                                    // riders (reduce_rider) -- whatever the regime word says
 {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (blockIdx.x >= ntile_blocks) {   // (uniform)
+        reduce_rider<T>(rider, blockIdx.x - ntile_blocks, reinterpret_cast<T *>(smem));
+        return;
+    }
     if (regime != nullptr && *regime != 0u) return;   // (uniform)
     constexpr bool kSmall = CIN > 0;
     const int cin = kSmall ? CIN : cin_rt;
     const int cout = kSmall ? COUT : cout_rt;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     int16_t *tapmap = reinterpret_cast<int16_t *>(smem);
     size_t off = align16((size_t)3 * st.maxfull * 2);
     const size_t nw = (size_t)st.ntap * cin * cout;
@@ -1748,18 +1806,7 @@ __device__ __forceinline__ void reduce_slots(const T *__restrict__ partials, int
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wl = lane & (W - 1);
     const size_t e = (size_t)block * W + wl;
-    auto stripe_sum = [&](int stripe) {
-        T s0 = (T)0, s1 = (T)0, s2 = (T)0, s3 = (T)0;
-        int p = stripe;
-        for (; p + 192 < nslots; p += 256) {
-            s0 += partials[(size_t)p * nw + e];
-            s1 += partials[(size_t)(p + 64) * nw + e];
-            s2 += partials[(size_t)(p + 128) * nw + e];
-            s3 += partials[(size_t)(p + 192) * nw + e];
-        }
-        for (; p < nslots; p += 64) s0 += partials[(size_t)p * nw + e];
-        return (s0 + s1) + (s2 + s3);
-    };
+    auto stripe_sum = [&](int stripe) { return reduce_stripe_sum(partials, nslots, nw, e, stripe); };
     T s = (T)0;
     if (W == 16) {
         if (e < nw) s = stripe_sum(wave * 4 + (lane >> 4));
@@ -1791,12 +1838,6 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(const T *__restri
 // The same for several layers in ONE launch (blockIdx.y = layer): the stack-level backward leaves every layer's
 // partials in its own region and reduces them all at the end, off the chain of dependent backward kernels.
 constexpr int kMaxReduceJobs = 9;
-template <typename T> struct ReduceJob {
-    const T *partials;
-    T *grad_filter;
-    int nslots;
-    unsigned nw;
-};
 template <typename T> struct ReduceJobs {
     ReduceJob<T> job[kMaxReduceJobs];
 };
