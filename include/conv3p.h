@@ -382,12 +382,26 @@ int conv3p_cache_fused_status(void *cache, unsigned *forward_launches, unsigned 
  * conv3p_sort_xyz_order_f32:  order[b][r] = index of the point that comes r-th in cloud b sorted by x, then y,
  *   then z (what util.py:66-68's three argsorts produce), remaining ties by original index.  data rows have
  *   row_floats floats starting with x, y, z.  N <= 8192 (CONV3P_ERR_UNSUPPORTED beyond).
+ * conv3p_sort_morton_order_f32:  the same arguments, status codes and limit; order[b][r] = index of the row that comes
+ *   r-th in cloud b by ascending Morton code (sort_method "morton", modelnet_provider.py:100-110 and
+ *   :202-208).  The reference computes its code with a third-party library; here the order is DEFINED, per cloud:
+ *     1. a row is finite if x, y and z are all finite;
+ *     2. lo[a], hi[a] = minimum and maximum of coordinate a over the finite rows, the float values converted to double;
+ *     3. e = max_a(hi[a] - lo[a]), subtracted in double;   4. s = 65536.0 / e, one IEEE double division;
+ *     5. q[a] = min(65535, floor((double(v[a]) - lo[a]) * s)): one double subtraction, then one double multiplication,
+ *        each rounded on its own;                          6. e == 0 (one row, or all finite rows equal): every q = 0;
+ *     7. code = the 48-bit interleave, x most significant in every triple: bit 3k+2 of code = bit k of q[x], bit 3k+1 =
+ *        bit k of q[y], bit 3k = bit k of q[z], k = 0..15;
+ *     8. a row that is not finite is left out of the box and gets code = 2^48 - 1, the code of the far corner cell;
+ *     9. ascending code, ties by ascending original index.
+ *   Sixteen bits an axis: code << 16 | index is one 64-bit key.  Reproducible bit for bit in numpy (tests/morton_ref.py).
  * conv3p_gather_rows:  dst[b][r] = src[b][order[b][r]] for rows of row_bytes bytes: applies one order to the
  *   points and to every per-point attribute / label array (sort_point_cloud_xyz2).  dst must not alias src.
  * ------------------------------------------------------------------------------------------- */
 int conv3p_augment_f32(const float *points_in, const double *cos_sin, const double *noise, double sigma, double clip,
                        int B, int N, float *points_out, void *stream);
 int conv3p_sort_xyz_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream);
+int conv3p_sort_morton_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream);
 int conv3p_gather_rows(const void *src, const int32_t *order, int B, int N, int row_bytes, void *dst, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -400,14 +414,16 @@ int conv3p_gather_rows(const void *src, const int32_t *order, int B, int N, int 
  *   labels  label_bytes = 1 / 4 / 8 (uint8 / int32 / int64) each; (S) or, labels_per_point != 0, (S, Nsrc).  NULL
  *           together with labels_out: no labels
  *   perm    int32[perm_len] or NULL (identity); cloud b of the batch is sample s = perm[start + b]
- *   flags   CONV3P_PROVIDER_ROTATE | _JITTER | _SORT;  sigma >= 0, clip > 0 (looked at with JITTER)
+ *   flags   CONV3P_PROVIDER_ROTATE | _JITTER | _SORT | _MORTON;  sigma >= 0, clip > 0 (looked at with JITTER).  _MORTON
+ *           qualifies _SORT (without it: CONV3P_ERR_INVALID_ARGUMENT): the order of conv3p_sort_morton_order_f32
  *   cos_sin double (B, 2), noise double (B, N, 3): conv3p_augment_f32's, used with ROTATE / JITTER; NULL: drawn with
  *           Philox4x32-10 as a function of (seed, step, s, source row) -- the recipe is in conv3p_provider.hpp
  *
  *   points (B, N, 3); input (B, N, K) = the sample's rows with xyz replaced by the augmented xyz; labels_out int32 (B) or
  *   (B, N).  Optional (NULL: not written): cos_sin_out (B, 2), noise_out (B, N, 3) in source-row order, order_out int32
  *   (B, N): the source row of every output row.  With SORT, rows and per-point labels are in the order of
- *   conv3p_sort_xyz_order_f32 applied to the augmented xyz; N <= 8192 (CONV3P_ERR_UNSUPPORTED beyond, before any launch).
+ *   conv3p_sort_xyz_order_f32 (with MORTON: conv3p_sort_morton_order_f32) applied to the augmented xyz -- the values
+ *   written to points; N <= 8192 (CONV3P_ERR_UNSUPPORTED beyond, before any launch).
  *   A sample index outside [0, S) is not read: the cloud's rows are 0, its labels -1, and bad_index[0] (int32, written
  *   by every call that launches) counts such clouds.  B * N == 0: CONV3P_OK, nothing launched, nothing written.
  *   Scratch from conv3p_provider_workspace_bytes (0 without SORT).  Bitwise reproducible; no output depends on a
@@ -416,6 +432,7 @@ int conv3p_gather_rows(const void *src, const int32_t *order, int B, int N, int 
 #define CONV3P_PROVIDER_ROTATE 1
 #define CONV3P_PROVIDER_JITTER 2
 #define CONV3P_PROVIDER_SORT 4
+#define CONV3P_PROVIDER_MORTON 8
 size_t conv3p_provider_workspace_bytes(int B, int N, int flags);
 int conv3p_provider_batch_f32(const float *data, const void *labels, int S, int Nsrc, int K, int label_bytes,
                               int labels_per_point, const int32_t *perm, int64_t perm_len, int64_t start, int B, int N,

@@ -30,7 +30,7 @@ CACHE_MATMUL_BF16 = 64            # matrix-core path: filter contractions in bf1
 ABI_VERSION = 5                # CONV3P_ABI_VERSION of include/conv3p.h
 STACK_MAX_LAYERS = 8
 OPT_MAX_TENSORS = 16             # CONV3P_OPT_MAX_TENSORS
-PROVIDER_ROTATE, PROVIDER_JITTER, PROVIDER_SORT = 1, 2, 4   # CONV3P_PROVIDER_*
+PROVIDER_ROTATE, PROVIDER_JITTER, PROVIDER_SORT, PROVIDER_MORTON = 1, 2, 4, 8   # CONV3P_PROVIDER_*
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -77,6 +77,7 @@ SYMBOLS = {
     "conv3p_fc_backward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_augment_f32": (_i, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i, _i, _vp, _vp]),
     "conv3p_sort_xyz_order_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "conv3p_sort_morton_order_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "conv3p_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "conv3p_seg_head_workspace_bytes": (_sz, [_sz, _i]),
     "conv3p_seg_head_f32": (_i, [_vp, _vp, _sz, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -3333,7 +3333,11 @@ int conv3p_augment_f32(const float *points_in, const double *cos_sin, const doub
     return hip_ok();
 }
 
-int conv3p_sort_xyz_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream)
+namespace {
+// Both orders of a cloud: one workgroup per cloud, npad keys of key_bytes in dynamic LDS.
+using SortOrderKernel = void (*)(const float *, int, int, int, int32_t *);
+int sort_order_launch(SortOrderKernel kernel, size_t key_bytes, const float *data, int B, int N, int row_floats,
+                      int32_t *order, void *stream)
 {
     if (B < 0 || N < 0 || row_floats < 3) return CONV3P_ERR_INVALID_ARGUMENT;
     if ((size_t)B * N == 0) return CONV3P_OK;
@@ -3341,13 +3345,23 @@ int conv3p_sort_xyz_order_f32(const float *data, int B, int N, int row_floats, i
     if (N > 8192) return CONV3P_ERR_UNSUPPORTED;
     int npad = 64;
     while (npad < N) npad <<= 1;
-    const size_t lds = (size_t)npad * 16;
+    const size_t lds = (size_t)npad * key_bytes;
     const int threads = npad / 2 < 1024 ? (npad / 2 < 64 ? 64 : npad / 2) : 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sort_xyz_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    hipLaunchKernelGGL(sort_xyz_kernel, dim3((unsigned)B), dim3(threads), lds, static_cast<hipStream_t>(stream), data, N,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, static_cast<hipStream_t>(stream), data, N,
                        row_floats, npad, order);
     return hip_ok();
+}
+}  // namespace
+
+int conv3p_sort_xyz_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream)
+{
+    return sort_order_launch(sort_xyz_kernel, sizeof(SortKey), data, B, N, row_floats, order, stream);
+}
+
+int conv3p_sort_morton_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream)
+{
+    return sort_order_launch(sort_morton_kernel, sizeof(uint64_t), data, B, N, row_floats, order, stream);
 }
 
 int conv3p_gather_rows(const void *src, const int32_t *order, int B, int N, int row_bytes, void *dst, void *stream)
@@ -3377,8 +3391,9 @@ int conv3p_provider_batch_f32(const float *data, const void *labels, int S, int 
                               double *noise_out, int32_t *order_out, int32_t *bad_index, void *workspace,
                               size_t workspace_bytes, void *stream)
 {
-    const int known = CONV3P_PROVIDER_ROTATE | CONV3P_PROVIDER_JITTER | CONV3P_PROVIDER_SORT;
+    const int known = CONV3P_PROVIDER_ROTATE | CONV3P_PROVIDER_JITTER | CONV3P_PROVIDER_SORT | CONV3P_PROVIDER_MORTON;
     if (B < 0 || N < 0 || S < 0 || K < 3 || Nsrc < N || start < 0 || (flags & ~known)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((flags & CONV3P_PROVIDER_MORTON) && !(flags & CONV3P_PROVIDER_SORT)) return CONV3P_ERR_INVALID_ARGUMENT;   // a qualifier
     if ((flags & CONV3P_PROVIDER_JITTER) && (!(clip > 0.0) || !(sigma >= 0.0))) return CONV3P_ERR_INVALID_ARGUMENT;
     if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
     if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
@@ -3411,11 +3426,12 @@ int conv3p_provider_batch_f32(const float *data, const void *labels, int S, int 
     }
     int npad = 64;
     while (npad < N) npad <<= 1;
-    const size_t lds = (size_t)npad * sizeof(SortKey);
+    const bool morton = (flags & CONV3P_PROVIDER_MORTON) != 0;
+    const size_t lds = (size_t)npad * (morton ? sizeof(uint64_t) : sizeof(SortKey));
     const int threads = npad / 2 < 1024 ? (npad / 2 < 64 ? 64 : npad / 2) : 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(provider_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    hipLaunchKernelGGL(provider_sort_kernel, dim3((unsigned)B), dim3(threads), lds, s, a, npad);
+    auto kernel = morton ? provider_sort_kernel<true> : provider_sort_kernel<false>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, s, a, npad);
     return hip_ok();
 }
 

@@ -3,6 +3,7 @@
 // The reference prepares every batch on the host with per-cloud Python loops:
 //   rotate_point_cloud / jitter_point_cloud   /root/reference/modelnet_provider.py:23-75   (training augmentation)
 //   sort_point_cloud_xyz / sort_point_cloud_xyz2   /root/reference/util.py:55-109          (optional cloud ordering)
+//   sort_point_cloud_morton                        /root/reference/modelnet_provider.py:100-110   (the other sort_method)
 // Once the op itself takes well under a millisecond per step these loops are the feed-side bottleneck, so the same
 // transformations are provided on the device, operating on the batch where it already lives.  Random numbers stay
 // the caller's (rotation angles on the host, Gaussian noise as a device tensor): the kernels are deterministic
@@ -93,17 +94,27 @@ __device__ __forceinline__ SortKey make_sort_key(float x, float y, float z, int 
 }
 
 // Bitonic network over keys[0 .. npad) in LDS (npad a power of two), by the whole workgroup; the keys were stored
-// before a barrier, and the last stage ends in one.
-__device__ __forceinline__ void bitonic_sort_keys(SortKey *keys, int npad, int tid, int nthr)
+// before a barrier, and the last stage ends in one.  Key: the element moved, Less: its strict order -- SortKey with
+// KeyLess (16 bytes, up to four compares) for the xyz order, uint64_t with MortonLess (8 bytes, one compare) for the
+// Morton order.
+struct KeyLess {
+    __device__ __forceinline__ bool operator()(const SortKey &a, const SortKey &b) const { return key_less(a, b); }
+};
+struct MortonLess {
+    __device__ __forceinline__ bool operator()(uint64_t a, uint64_t b) const { return a < b; }
+};
+template <typename Key, typename Less>
+__device__ __forceinline__ void bitonic_sort_keys(Key *keys, int npad, int tid, int nthr)
 {
+    const Less less;
     for (int k = 2; k <= npad; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = tid; t < (npad >> 1); t += nthr) {
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
                 const int l = i | j;
-                const SortKey a = keys[i], c = keys[l];
+                const Key a = keys[i], c = keys[l];
                 const bool up = (i & k) == 0;
-                if (key_less(c, a) == up) {
+                if (less(c, a) == up) {
                     keys[i] = c;
                     keys[l] = a;
                 }
@@ -129,8 +140,153 @@ __global__ __launch_bounds__(1024) void sort_xyz_kernel(const float *__restrict_
         keys[i] = k;
     }
     __syncthreads();
-    bitonic_sort_keys(keys, npad, tid, nthr);
+    bitonic_sort_keys<SortKey, KeyLess>(keys, npad, tid, nthr);
     for (int i = tid; i < N; i += nthr) order[(size_t)b * N + i] = (int32_t)keys[i].idx;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The Morton order of a cloud (sort_method "morton" of the reference's providers, modelnet_provider.py:100-110; the
+// reference calls a third-party library whose cell size is not documented, so the order is DEFINED here -- the same
+// words as include/conv3p.h and DESIGN.md section 5d):
+//   a row is finite if x, y and z are; lo[a], hi[a] = min, max of coordinate a over the finite rows, as double;
+//   e = max_a(hi[a] - lo[a]);  s = 65536.0 / e;  q[a] = min(65535, floor((double(v[a]) - lo[a]) * s)), every
+//   operation an IEEE double operation rounded on its own; e == 0: q = 0;
+//   code = the 48-bit interleave, bit 3k+2 = bit k of q[x], 3k+1 of q[y], 3k of q[z]; a row that is not finite:
+//   code = 2^48 - 1;  order by ascending code, ties by ascending original index.
+// Sixteen bits an axis, so that code << 16 | index is ONE 64-bit key for every N <= 65536.
+
+constexpr uint64_t kMortonPadKey = ~0ull;                     // sorts strictly last: index < N <= 8192 < 0xFFFF
+constexpr uint64_t kMortonFarCode = (1ull << 48) - 1;
+
+__device__ __forceinline__ bool morton_finite(float x, float y, float z)
+{
+    const uint32_t m = 0x7F800000u;
+    return (__builtin_bit_cast(uint32_t, x) & m) != m && (__builtin_bit_cast(uint32_t, y) & m) != m &&
+           (__builtin_bit_cast(uint32_t, z) & m) != m;
+}
+
+// The box of a cloud, as every lane of the workgroup holds it after morton_box_reduce: lo[a] and the one scale.
+struct MortonBox {
+    double lo[3];
+    double s;              // 65536 / e; 0 when e == 0 or no row is finite (every q is 0 then)
+};
+
+// bits 0..15 of q -> bits 0, 3, 6, .., 45
+__device__ __forceinline__ uint64_t morton_spread16(uint32_t q)
+{
+    uint64_t v = q & 0xFFFFu;
+    v = (v | (v << 16)) & 0x0000FF0000FFull;
+    v = (v | (v << 8)) & 0x00F00F00F00Full;
+    v = (v | (v << 4)) & 0x0C30C30C30C3ull;
+    v = (v | (v << 2)) & 0x249249249249ull;
+    return v;
+}
+
+__device__ __forceinline__ uint64_t morton_code(float x, float y, float z, const MortonBox &box)
+{
+    if (!morton_finite(x, y, z)) return kMortonFarCode;
+    const float v[3] = {x, y, z};
+    uint32_t q[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double c = floor(__dmul_rn(__dsub_rn((double)v[a], box.lo[a]), box.s));   // >= 0: v[a] >= lo[a]
+        q[a] = c < 65535.0 ? (uint32_t)c : 65535u;
+    }
+    return (morton_spread16(q[0]) << 2) | (morton_spread16(q[1]) << 1) | morton_spread16(q[2]);
+}
+
+__device__ __forceinline__ uint64_t make_morton_key(float x, float y, float z, int i, const MortonBox &box)
+{
+    return (morton_code(x, y, z, box) << 16) | (uint64_t)(uint32_t)i;
+}
+
+// A lane's running box: lo = +inf, hi = -inf before the first finite row.
+struct MortonRange {
+    float lo[3], hi[3];
+};
+__device__ __forceinline__ void morton_range_init(MortonRange &r)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        r.lo[a] = __builtin_inff();
+        r.hi[a] = -__builtin_inff();
+    }
+}
+__device__ __forceinline__ void morton_range_add(MortonRange &r, float x, float y, float z)
+{
+    if (!morton_finite(x, y, z)) return;
+    const float v[3] = {x, y, z};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        r.lo[a] = fminf(r.lo[a], v[a]);
+        r.hi[a] = fmaxf(r.hi[a], v[a]);
+    }
+}
+
+// The lanes' ranges -> the cloud's box, in every lane: a butterfly inside each wave, then across the (at most 16)
+// waves through LDS (box_s: 16 x 6 floats).  Min and max do not depend on the order they are taken in, so the box is
+// exact; nothing goes through global memory.  Every thread of the workgroup calls it; it ends behind a barrier.
+__device__ __forceinline__ MortonBox morton_box_reduce(MortonRange r, float *box_s, int tid, int nthr)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        for (int m = 32; m > 0; m >>= 1) {
+            r.lo[a] = fminf(r.lo[a], __shfl_xor(r.lo[a], m, 64));
+            r.hi[a] = fmaxf(r.hi[a], __shfl_xor(r.hi[a], m, 64));
+        }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            box_s[(tid >> 6) * 6 + a] = r.lo[a];
+            box_s[(tid >> 6) * 6 + 3 + a] = r.hi[a];
+        }
+    }
+    __syncthreads();
+    const int waves = (nthr + 63) >> 6;
+    MortonBox box;
+    double e = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float lo = box_s[a], hi = box_s[3 + a];
+        for (int w = 1; w < waves; ++w) {
+            lo = fminf(lo, box_s[w * 6 + a]);
+            hi = fmaxf(hi, box_s[w * 6 + 3 + a]);
+        }
+        box.lo[a] = (double)lo;
+        const double d = __dsub_rn((double)hi, (double)lo);     // -inf when no row is finite
+        e = d > e ? d : e;
+    }
+    box.s = e > 0.0 ? __ddiv_rn(65536.0, e) : 0.0;
+    return box;
+}
+
+// order[b][r] = index of the row of cloud b that comes r-th in the Morton order defined above.  One workgroup per
+// cloud, the structure of sort_xyz_kernel: the box pass, the key pass, the network on 8-byte keys in LDS (npad * 8
+// bytes, 64 KB at N = 8192), `order` last.  `data` rows have `ld` floats, the first three being x, y, z.
+__global__ __launch_bounds__(1024) void sort_morton_kernel(const float *__restrict__ data, int N, int ld, int npad,
+                                                           int32_t *__restrict__ order)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float box_s[16 * 6];
+    uint64_t *keys = reinterpret_cast<uint64_t *>(smem);
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const float *cloud = data + (size_t)b * N * ld;
+    MortonRange rg;
+    morton_range_init(rg);
+    for (int i = tid; i < N; i += nthr)
+        morton_range_add(rg, cloud[(size_t)i * ld + 0], cloud[(size_t)i * ld + 1], cloud[(size_t)i * ld + 2]);
+    const MortonBox box = morton_box_reduce(rg, box_s, tid, nthr);
+    for (int i = tid; i < npad; i += nthr) {
+        uint64_t k = kMortonPadKey;
+        if (i < N) {
+            const float *row = cloud + (size_t)i * ld;
+            k = make_morton_key(row[0], row[1], row[2], i, box);
+        }
+        keys[i] = k;
+    }
+    __syncthreads();
+    bitonic_sort_keys<uint64_t, MortonLess>(keys, npad, tid, nthr);
+    for (int i = tid; i < N; i += nthr) order[(size_t)b * N + i] = (int32_t)(keys[i] & 0xFFFFu);
 }
 
 // dst[b][r][:] = src[b][order[b][r]][:], rows of `row_bytes` bytes (any element type: points, labels, attributes)

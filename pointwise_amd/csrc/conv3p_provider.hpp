@@ -20,9 +20,13 @@
 //                                     workspace row keys[r].idx -- written by this workgroup before the barrier, so it is
 //                                     read back from L2 -- and the other channels and the label from the source.  The
 //                                     key is not inverted instead: it has lost -0.0's sign and a NaN's payload.
+//                                     provider_sort_kernel<true> is the Morton order (sort_method "morton",
+//                                     modelnet_provider.py:202-208): the same passes on make_morton_key's 8-byte keys
+//                                     (64 KB at N = 8192), after a pass of their own for the augmented rows' box.
 //
-// Rotation and jitter are augment_point (conv3p_prestep.hpp), the sort is make_sort_key / bitonic_sort_keys of the same
-// file.  No memset, no atomic on global memory: every output word is written once by a plain store.
+// Rotation and jitter are augment_point (conv3p_prestep.hpp), the sort is make_sort_key or make_morton_key and
+// bitonic_sort_keys of the same file.  No memset, no atomic on global memory: every output word is written once by a
+// plain store.
 //
 // Sample of cloud b: s = perm[start + b] (perm == NULL: start + b).  s outside [0, S) is never used as an index: the
 // cloud's rows are zero, its labels -1 (ignored by both heads), and workgroup 0 counts such clouds into bad_index[0].
@@ -37,6 +41,8 @@
 // Functions of (seed, step, s, i) only -- not of the cloud's place in the batch.  The dropout mask of
 // conv3p_cls_tail.hpp uses counters whose second word is 0; here it is s + 1 >= 1 (S <= 2^31) or 0xFFFFFFFF.
 #pragma once
+
+#include <type_traits>
 
 #include "conv3p_cls_tail.hpp"
 #include "conv3p_prestep.hpp"
@@ -192,12 +198,18 @@ __global__ __launch_bounds__(kProviderTile) void provider_flat_kernel(const Prov
     }
 }
 
+// MORTON: the keys are make_morton_key's (8 bytes a row) instead of make_sort_key's (16).  The box of the AUGMENTED
+// rows has to be known before the first key, so the pass that stages the rows reduces the box and a second pass, behind
+// the barrier, builds the keys from the staged rows -- a lane reads back the rows it wrote itself.  MORTON = false is
+// the kernel as it was: none of its statements depends on the parameter.
+template <bool MORTON>
 __global__ __launch_bounds__(1024) void provider_sort_kernel(const ProviderArgs p, int npad)
 {
+    using Key = typename std::conditional<MORTON, uint64_t, SortKey>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ double2 cs_s;
     __shared__ int bad_s;
-    SortKey *keys = reinterpret_cast<SortKey *>(smem);
+    Key *keys = reinterpret_cast<Key *>(smem);
     const int tid = threadIdx.x, nthr = blockDim.x, b = blockIdx.x, N = p.N, K = p.K;
     const long long s = provider_sample(p, b);
     const bool valid = s >= 0 && s < p.S;
@@ -209,35 +221,63 @@ __global__ __launch_bounds__(1024) void provider_sort_kernel(const ProviderArgs 
     if (b == 0) provider_count_bad(p, &bad_s, tid, nthr);
     float *stage = p.stage + (size_t)b * N * 3;
     const double2 t = cs_s;
-    for (int i = tid; i < npad; i += nthr) {
-        SortKey k{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};   // padding sorts last
-        if (i < N) {
+    if constexpr (MORTON) {
+        __shared__ float box_s[16 * 6];
+        MortonRange rg;
+        morton_range_init(rg);
+        for (int i = tid; i < N; i += nthr) {
             float r[3];
             provider_row(p, b, s, valid, i, t, r);
             stage[3 * i] = r[0];
             stage[3 * i + 1] = r[1];
             stage[3 * i + 2] = r[2];
-            k = make_sort_key(r[0], r[1], r[2], i);
+            morton_range_add(rg, r[0], r[1], r[2]);
         }
-        keys[i] = k;
+        __threadfence_block();           // for the epilogue's gather, which reads rows other lanes staged (the key pass
+                                         // below reads only the lane's own rows: both loops walk i = tid + k * nthr)
+        const MortonBox box = morton_box_reduce(rg, box_s, tid, nthr);
+        for (int i = tid; i < npad; i += nthr) {
+            uint64_t k = kMortonPadKey;
+            if (i < N) k = make_morton_key(stage[3 * i], stage[3 * i + 1], stage[3 * i + 2], i, box);
+            keys[i] = k;
+        }
+        __syncthreads();
+        bitonic_sort_keys<uint64_t, MortonLess>(keys, npad, tid, nthr);
+    } else {
+        for (int i = tid; i < npad; i += nthr) {
+            SortKey k{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};   // padding sorts last
+            if (i < N) {
+                float r[3];
+                provider_row(p, b, s, valid, i, t, r);
+                stage[3 * i] = r[0];
+                stage[3 * i + 1] = r[1];
+                stage[3 * i + 2] = r[2];
+                k = make_sort_key(r[0], r[1], r[2], i);
+            }
+            keys[i] = k;
+        }
+        __threadfence_block();               // the staged rows are read back below by other lanes of this workgroup
+        __syncthreads();
+        bitonic_sort_keys<SortKey, KeyLess>(keys, npad, tid, nthr);
     }
-    __threadfence_block();               // the staged rows are read back below by other lanes of this workgroup
-    __syncthreads();
-    bitonic_sort_keys(keys, npad, tid, nthr);
+    auto row_of = [&](int r) -> uint32_t {
+        if constexpr (MORTON) return (uint32_t)(keys[r] & 0xFFFFu);
+        else return keys[r].idx;
+    };
     float *pts = p.points + (size_t)b * N * 3;
     for (int e = tid; e < N * 3; e += nthr) {
         const int r = e / 3, c = e - r * 3;
-        pts[e] = stage[3 * (size_t)keys[r].idx + c];
+        pts[e] = stage[3 * (size_t)row_of(r) + c];
     }
     float *inp = p.input + (size_t)b * N * K;
     const float *src = valid ? p.data + (size_t)s * p.Nsrc * K : nullptr;
     for (int e = tid; e < N * K; e += nthr) {
         const int r = e / K, c = e - r * K;
-        const size_t i = keys[r].idx;
+        const size_t i = row_of(r);
         inp[e] = c < 3 ? stage[3 * i + c] : (valid ? src[i * K + c] : 0.0f);
     }
     for (int r = tid; r < N; r += nthr) {
-        const int i = (int)keys[r].idx;
+        const int i = (int)row_of(r);
         const size_t o = (size_t)b * N + r;
         if (p.labels_out && p.per_point) p.labels_out[o] = valid ? provider_label(p, (size_t)s * p.Nsrc + i) : -1;
         if (p.order_out) p.order_out[o] = i;

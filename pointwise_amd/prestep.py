@@ -3,12 +3,16 @@
 Names, argument meaning and results follow the reference functions
     rotate_point_cloud, rotate_point_cloud_by_angle, jitter_point_cloud    /root/reference/modelnet_provider.py:23-75
     sort_point_cloud_xyz, sort_point_cloud_xyz2                            /root/reference/util.py:55-109
+    sort_point_cloud_morton                                                /root/reference/modelnet_provider.py:100-110
 with torch tensors on a HIP device in place of numpy arrays: the per-cloud Python loops of the reference become one
-kernel launch per batch (include/conv3p.h: conv3p_augment_f32, conv3p_sort_xyz_order_f32, conv3p_gather_rows).
+kernel launch per batch (include/conv3p.h: conv3p_augment_f32, conv3p_sort_xyz_order_f32,
+conv3p_sort_morton_order_f32, conv3p_gather_rows).
 Random numbers are drawn by the caller's generator (numpy on the host for the B angles, exactly as the reference
 does; torch on the device for the B x N x 3 Gaussian noise) and can be passed in explicitly, which is how the tests
-compare with the reference functions.  sort_point_cloud_morton (modelnet_provider.py:100-109) needs the third-party
-`libpluie`, which is not part of the reference tree, and is not provided; the default sort_method is "xyz".
+compare with the reference functions.  The reference's sort_point_cloud_morton takes its codes from the third-party
+`libpluie`, which is not part of the reference tree and whose cell size is not documented: the Morton order here is the
+one include/conv3p.h defines (sixteen bits an axis over the cloud's own bounding cube, ties by original index), restated
+in numpy by tests/morton_ref.py.  The default sort_method of the providers is "xyz".
 """
 import ctypes
 import math
@@ -84,8 +88,7 @@ def rotate_and_jitter(batch_data, angles=None, sigma=0.01, clip=0.05, noise=None
     return _augment(batch_data, np.stack([np.cos(angles), np.sin(angles)], axis=1), noise, sigma, clip)
 
 
-def sort_order_xyz(batch_data):
-    """int32 (B, N): for every cloud the permutation that sorts its points by x, then y, then z."""
+def _sort_order(batch_data, symbol):
     lib = _lib.load()
     dev = _check_device(batch_data)
     if batch_data.dim() != 3 or batch_data.shape[2] < 3 or batch_data.dtype != torch.float32:
@@ -94,8 +97,19 @@ def sort_order_xyz(batch_data):
     x = batch_data.contiguous()
     order = torch.empty((B, N), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _call(lib.conv3p_sort_xyz_order_f32, x.data_ptr(), B, N, K, order.data_ptr(), _stream(dev))
+        _call(getattr(lib, symbol), x.data_ptr(), B, N, K, order.data_ptr(), _stream(dev))
     return order
+
+
+def sort_order_xyz(batch_data):
+    """int32 (B, N): for every cloud the permutation that sorts its points by x, then y, then z."""
+    return _sort_order(batch_data, "conv3p_sort_xyz_order_f32")
+
+
+def sort_order_morton(batch_data):
+    """int32 (B, N): for every cloud the permutation that puts its points in Morton order (include/conv3p.h:
+    conv3p_sort_morton_order_f32 -- 16 bits an axis over the cloud's bounding cube, ties by original index)."""
+    return _sort_order(batch_data, "conv3p_sort_morton_order_f32")
 
 
 def _gather(t, order):
@@ -120,4 +134,17 @@ def sort_point_cloud_xyz(batch_data):
 def sort_point_cloud_xyz2(batch_data, batch_attributes):
     """util.py:76-109: the same, the per-point attributes (any dtype, BxN or BxNxM) permuted accordingly."""
     order = sort_order_xyz(batch_data)
+    return _gather(batch_data, order), _gather(batch_attributes, order)
+
+
+def sort_point_cloud_morton(batch_data):
+    """modelnet_provider.py:100-110: every cloud in Morton order of the xyz in its first three columns (BxNxK); whole
+    rows are permuted."""
+    return _gather(batch_data, sort_order_morton(batch_data))
+
+
+def sort_point_cloud_morton2(batch_data, batch_attributes):
+    """The same, the per-point attributes (any dtype, BxN or BxNxM) permuted accordingly, as sort_point_cloud_xyz2: what
+    the scene providers need for their labels."""
+    order = sort_order_morton(batch_data)
     return _gather(batch_data, order), _gather(batch_attributes, order)

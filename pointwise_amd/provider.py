@@ -10,8 +10,9 @@ with numpy loops per cloud.  Here the data set -- arrays already in memory; read
 is uploaded once, and a batch is assembled from it by ONE kernel launch: index, slice, rotate, jitter, sort, the
 points / input split and the label cast.  The random draws are the device's (Philox4x32-10, a function of seed, step,
 sample and source row: pointwise_amd/csrc/conv3p_provider.hpp), so an epoch is reproducible from (seed, epoch) alone
-and does not depend on how the batch is sharded.  sort_point_cloud_morton (modelnet_provider.py:100-109) needs the
-third-party `libpluie` and is not provided.
+and does not depend on how the batch is sharded.  sort_method is the providers' own argument
+(modelnet_provider.py:202-208): "xyz" or "morton", the latter in the order include/conv3p.h defines (the reference takes
+its codes from the third-party `libpluie`, which nobody has).
 
     assemble_batch   the call, on tensors
     BatchProvider    the reference providers' interface (next_epoch, has_next_batch, next_batch,
@@ -24,19 +25,36 @@ from . import _lib
 from .conv3p_op import Conv3pInvalidArgument, _call, _require
 
 _LABEL_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+SORT_METHODS = ("xyz", "morton")
+
+
+def _check_sort_method(sort_method):
+    """The reference prints a message and feeds unsorted clouds when it does not know the method; here it is an error,
+    raised before anything touches the device."""
+    if sort_method not in SORT_METHODS:
+        raise ValueError("sort_method must be one of %s, not %r" % (", ".join(map(repr, SORT_METHODS)), sort_method))
+    return sort_method
+
+
+def _sort_flags(sort_cloud, sort_method):
+    """sort_method is inert while sort_cloud is false, as in the reference."""
+    if not sort_cloud:
+        return 0
+    return _lib.PROVIDER_SORT | (_lib.PROVIDER_MORTON if sort_method == "morton" else 0)
 
 
 class BatchBuffers:
     """The output tensors of one batch and the call's scratch: points (B, N, 3), input (B, N, K), labels int32 (B) or
     (B, N), bad_index int32 (), and -- with randoms -- cos_sin (B, 2), noise (B, N, 3) float64, order int32 (B, N)."""
 
-    def __init__(self, B, N, K, per_point, device, sort_cloud=False, randoms=False):
+    def __init__(self, B, N, K, per_point, device, sort_cloud=False, randoms=False, sort_method="xyz"):
         self.shape = (B, N, K, bool(per_point))
         self.points = torch.empty((B, N, 3), dtype=torch.float32, device=device)
         self.input = torch.empty((B, N, K), dtype=torch.float32, device=device)
         self.labels = torch.empty((B, N) if per_point else (B,), dtype=torch.int32, device=device)
         self.bad_index = torch.zeros((), dtype=torch.int32, device=device)
-        nbytes = _lib.load().conv3p_provider_workspace_bytes(B, N, _lib.PROVIDER_SORT if sort_cloud else 0)
+        flags = _sort_flags(sort_cloud, _check_sort_method(sort_method))
+        nbytes = _lib.load().conv3p_provider_workspace_bytes(B, N, flags)
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
         self.cos_sin = self.noise = self.order = None
         if randoms:
@@ -50,16 +68,19 @@ def _ptr(t):
 
 
 def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0, rotate=False, jitter=False, sigma=0.01,
-                   clip=0.05, sort_cloud=False, seed=0, step=0, cos_sin=None, noise=None, out=None, return_randoms=False):
+                   clip=0.05, sort_cloud=False, seed=0, step=0, cos_sin=None, noise=None, out=None, return_randoms=False,
+                   sort_method="xyz"):
     """One batch from a resident data set, in one launch.
 
     data float32 (S, Nsrc, K) with xyz first; labels uint8 / int32 / int64, (S,) or (S, Nsrc); cloud b is sample
     perm[start + b] (perm int32 on the device; None: start + b) cut to its first num_points rows (default Nsrc).
-    rotate / jitter / sort_cloud: modelnet_provider.py:196-204; cos_sin (B, 2) and noise (B, N, 3), float64 device
-    tensors, replace the draws of (seed, step).  out: a BatchBuffers to write into (default: fresh tensors).
+    rotate / jitter / sort_cloud / sort_method ("xyz" or "morton"; inert without sort_cloud; anything else: ValueError):
+    modelnet_provider.py:196-208; cos_sin (B, 2) and noise (B, N, 3), float64 device tensors, replace the draws of
+    (seed, step).  out: a BatchBuffers to write into (default: fresh tensors).
     -> (points (B, N, 3), input (B, N, K), labels int32, bad_index) and, with return_randoms, a dict of cos_sin, noise
     (source-row order) and order.  bad_index is an int32 device scalar: the number of clouds whose sample index was
     outside [0, S) -- their rows are 0 and their labels -1; it is not synchronised on here."""
+    _check_sort_method(sort_method)
     lib = _lib.load()
     _require(isinstance(data, torch.Tensor) and data.dim() == 3 and data.dtype == torch.float32 and data.shape[2] >= 3,
              "data must be a float32 (S, Nsrc, K >= 3) tensor, xyz first")
@@ -94,13 +115,13 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
                  and t.is_contiguous(), "%s must be a contiguous float64 %s tensor on the data's device" % (name, shape))
     _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
     if out is None:
-        out = BatchBuffers(B, N, K, per_point, dev, sort_cloud, return_randoms)
+        out = BatchBuffers(B, N, K, per_point, dev, sort_cloud, return_randoms, sort_method)
     else:
         _require(isinstance(out, BatchBuffers) and out.shape == (B, N, K, per_point) and out.points.device == dev,
                  "out was made for another batch shape")
         _require(not return_randoms or out.noise is not None, "out has no buffers for the randoms")
     flags = ((_lib.PROVIDER_ROTATE if rotate else 0) | (_lib.PROVIDER_JITTER if jitter else 0)
-             | (_lib.PROVIDER_SORT if sort_cloud else 0))
+             | _sort_flags(sort_cloud, sort_method))
     need = lib.conv3p_provider_workspace_bytes(B, N, flags)
     ws = out.workspace
     if need and (ws is None or ws.numel() < need):
@@ -136,10 +157,12 @@ class BatchProvider:
     epoch `epoch` are those of step = epoch * num_batches + cur_batch.
 
     get_batch_point_cloud() -> (points, input, labels int32); the tensors alternate between two buffer sets, so a batch
-    stays valid while the next one is assembled.  bad_index (int32 device scalar) belongs to the last batch."""
+    stays valid while the next one is assembled.  bad_index (int32 device scalar) belongs to the last batch.
+    sort_method ("xyz" or "morton") is a constructor setting like sort_cloud, not state: state_dict does not carry it."""
 
     def __init__(self, data, labels, batch_size, num_points=None, training=True, rotate=None, jitter=None,
-                 sort_cloud=False, seed=0, device="cuda:0"):
+                 sort_cloud=False, seed=0, device="cuda:0", sort_method="xyz"):
+        self.sort_method = _check_sort_method(sort_method)
         self.device = torch.device(device)
         as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, order="C"))   # a copy: uploaded once
         data, labels = as_t(data), as_t(labels)
@@ -165,8 +188,8 @@ class BatchProvider:
         self.seed = int(seed)
         self.sigma, self.clip = 0.01, 0.05                                       # jitter_point_cloud's defaults, :64
         per_point = self.labels.dim() == 2
-        self._buffers = [BatchBuffers(self.batch_size, self.num_points, K, per_point, self.device, self.sort_cloud)
-                         for _ in range(2)]
+        self._buffers = [BatchBuffers(self.batch_size, self.num_points, K, per_point, self.device, self.sort_cloud,
+                                      sort_method=self.sort_method) for _ in range(2)]
         self._turn = 0
         self.bad_index = self._buffers[0].bad_index
         self.epoch = -1
@@ -199,12 +222,14 @@ class BatchProvider:
         if return_randoms and buf.noise is None:
             B, N, K, per_point = buf.shape
             for i in range(2):
-                self._buffers[i] = BatchBuffers(B, N, K, per_point, self.device, self.sort_cloud, randoms=True)
+                self._buffers[i] = BatchBuffers(B, N, K, per_point, self.device, self.sort_cloud, randoms=True,
+                                                sort_method=self.sort_method)
             buf = self._buffers[self._turn]
         self._turn ^= 1
         res = assemble_batch(self.data, self.labels, self.batch_size, self.num_points, self.permutation,
                              self.cur_batch * self.batch_size, self.rotate, self.jitter, self.sigma, self.clip,
-                             self.sort_cloud, self.seed, self.step, out=buf, return_randoms=return_randoms)
+                             self.sort_cloud, self.seed, self.step, out=buf, return_randoms=return_randoms,
+                             sort_method=self.sort_method)
         self.bad_index = res[3]
         return res[:3] + res[4:]
 

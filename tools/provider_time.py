@@ -13,7 +13,13 @@ of HIP events; every size is warmed up first; nothing synchronises inside a roun
 (4 K + 12 + label bytes) * 2 per point (rows, points and labels, read and written), from the C call alone.
 Output: profiles/provider_time.txt (--out).
 
+--morton: the three sorted shapes with sort_method="morton" instead.  Per shape and round, alternated: the xyz fused call
+(the yardstick: its kernel is the one timed above), the Morton fused call, and the composition with
+prestep.sort_order_morton in place of sort_order_xyz; then the C call alone with CONV3P_PROVIDER_MORTON.
+Output: profiles/provider_morton_time.txt.
+
     python tools/provider_time.py [--out profiles/provider_time.txt]
+    python tools/provider_time.py --morton [--out profiles/provider_morton_time.txt]
 """
 import argparse
 import os
@@ -33,8 +39,8 @@ SIZES = ((32, 2048, 3, True, True, False, 256, "rotate + jitter + sort"),
 ROUNDS, CALLS, BARE = 5, 20, 200
 
 
-def composition(data, labels, perm, start, B, augment, sort):
-    """What a user of prestep.py does per batch on the parent commit."""
+def composition(data, labels, perm, start, B, augment, sort, sort_order=prestep.sort_order_xyz):
+    """What a user of prestep.py does per batch without the fused call."""
     idx = perm[start:start + B].long()
     rows = data[idx]
     lab = labels[idx]
@@ -43,7 +49,7 @@ def composition(data, labels, perm, start, B, augment, sort):
         xyz = prestep.rotate_and_jitter(xyz)              # numpy angles + upload, torch.randn float64, one launch
         rows = xyz if rows.shape[2] == 3 else torch.cat([xyz, rows[:, :, 3:]], dim=2)
     if sort:
-        order = prestep.sort_order_xyz(rows)
+        order = sort_order(rows)
         rows = prestep._gather(rows, order)
         if lab.dim() == 2:
             lab = prestep._gather(lab, order)
@@ -60,23 +66,101 @@ def timed(fn, calls=CALLS):
     return a.elapsed_time(b) * 1e3 / calls      # us per call
 
 
+def bare_call(lib, data, labels, perm, S, N, K, B, per_point, flags, o, stream):
+    """The C entry point alone: BARE back-to-back calls between one event pair, 3 rounds."""
+    ws = o.workspace
+    a = (data.data_ptr(), labels.data_ptr(), S, N, K, 1, int(per_point), perm.data_ptr(), S, 0, B, N, flags, 0.01, 0.05,
+         1, 7, None, None, o.points.data_ptr(), o.input.data_ptr(), o.labels.data_ptr(), None, None, None,
+         o.bad_index.data_ptr(), ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+
+    def bare():
+        if lib.conv3p_provider_batch_f32(*a) != _lib.OK:
+            raise SystemExit("provider_time: conv3p_provider_batch_f32 failed")
+    bare()
+    torch.cuda.synchronize()
+    return [timed(bare, BARE) for _ in range(3)]
+
+
+def resident_set(B, N, K, per_point, S, dev):
+    g = torch.Generator(device="cpu").manual_seed(B + N + K)
+    data = torch.rand(S, N, K, generator=g).to(dev)
+    labels = torch.randint(0, 13, (S, N) if per_point else (S,), generator=g).to(torch.uint8).to(dev)
+    perm = torch.from_numpy(np.random.default_rng(1).permutation(S).astype(np.int32)).to(dev)
+    return data, labels, perm
+
+
+def main_morton(out_path):
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    lines = ["fused batch provider, sort_method=\"morton\" against \"xyz\" (the yardstick) and against the composition, %s"
+             % torch.cuda.get_device_name(dev),
+             "us per call including Python; %d rounds x %d calls, alternated, HIP events" % (ROUNDS, CALLS)]
+    for B, N, K, augment, sort, per_point, S, what in SIZES:
+        if not sort:
+            continue
+        data, labels, perm = resident_set(B, N, K, per_point, S, dev)
+        bufs = {m: [provider.BatchBuffers(B, N, K, per_point, dev, True, sort_method=m) for _ in range(2)]
+                for m in provider.SORT_METHODS}
+        step = [0]
+
+        def fused(method):
+            step[0] += 1
+            return provider.assemble_batch(data, labels, B, perm=perm, start=(step[0] * B) % (S - B + 1), rotate=augment,
+                                           jitter=augment, sort_cloud=True, seed=1, step=step[0],
+                                           out=bufs[method][step[0] & 1], sort_method=method)
+
+        def comp():
+            step[0] += 1
+            return composition(data, labels, perm, (step[0] * B) % (S - B + 1), B, augment, True, prestep.sort_order_morton)
+        calls = (lambda: fused("xyz"), lambda: fused("morton"), comp)
+        for _ in range(5):
+            for fn in calls:
+                fn()
+        torch.cuda.synchronize()
+        t = [[], [], []]
+        for _ in range(ROUNDS):
+            for k, fn in enumerate(calls):
+                t[k].append(timed(fn))
+        flags = (3 if augment else 0) | _lib.PROVIDER_SORT
+        tx = bare_call(lib, data, labels, perm, S, N, K, B, per_point, flags, bufs["xyz"][0], stream)
+        tm = bare_call(lib, data, labels, perm, S, N, K, B, per_point, flags | _lib.PROVIDER_MORTON, bufs["morton"][0], stream)
+        row = lambda v, f="%8.1f": "  ".join(f % x for x in v)
+        lines.append("")
+        lines.append("B x N x K = %d x %d x %d  (%s)" % (B, N, K, what.replace("sort", "sort (morton)")))
+        lines.append("  fused xyz     (1 launch)        " + row(t[0]))
+        lines.append("  fused morton  (1 launch)        " + row(t[1]))
+        lines.append("  composition   (morton)          " + row(t[2]))
+        lines.append("  ratio xyz / morton              " + row([x / m for x, m in zip(t[0], t[1])], "%8.2f"))
+        lines.append("  ratio composition / morton      " + row([c / m for c, m in zip(t[2], t[1])], "%8.2f"))
+        lines.append("  the C call alone, %d back to back, 3 rounds: xyz " % BARE + "  ".join("%.1f" % v for v in tx)
+                     + " us;  morton " + "  ".join("%.1f" % v for v in tm) + " us")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
-                                                  "provider_time.txt"))
+    ap.add_argument("--morton", action="store_true", help="time sort_method=\"morton\" on the sorted shapes")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                "provider_morton_time.txt" if args.morton else "provider_time.txt")
     if not torch.cuda.is_available():
         raise SystemExit("provider_time: needs a HIP device")
+    if args.morton:
+        return main_morton(args.out)
     lib = _lib.load()
     dev = torch.device("cuda:0")
     lines = ["fused batch provider (one launch) vs the composition it replaces, %s" % torch.cuda.get_device_name(dev),
              "us per call including Python; %d rounds x %d calls, alternated, HIP events; ratio = composition / fused per round"
              % (ROUNDS, CALLS)]
     for B, N, K, augment, sort, per_point, S, what in SIZES:
-        g = torch.Generator(device="cpu").manual_seed(B + N + K)
-        data = torch.rand(S, N, K, generator=g).to(dev)
-        labels = torch.randint(0, 13, (S, N) if per_point else (S,), generator=g).to(torch.uint8).to(dev)
-        perm = torch.from_numpy(np.random.default_rng(1).permutation(S).astype(np.int32)).to(dev)
+        data, labels, perm = resident_set(B, N, K, per_point, S, dev)
         bufs = [provider.BatchBuffers(B, N, K, per_point, dev, sort) for _ in range(2)]
         step = [0]
 
@@ -95,21 +179,8 @@ def main():
         for _ in range(ROUNDS):
             tf.append(timed(fused))
             tc.append(timed(comp))
-        # the C entry point alone
-        o = bufs[0]
-        flags = (3 if augment else 0) | (4 if sort else 0)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = o.workspace
-        a = (data.data_ptr(), labels.data_ptr(), S, N, K, 1, int(per_point), perm.data_ptr(), S, 0, B, N, flags, 0.01, 0.05,
-             1, 7, None, None, o.points.data_ptr(), o.input.data_ptr(), o.labels.data_ptr(), None, None, None,
-             o.bad_index.data_ptr(), ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
-
-        def bare():
-            if lib.conv3p_provider_batch_f32(*a) != _lib.OK:
-                raise SystemExit("provider_time: conv3p_provider_batch_f32 failed")
-        bare()
-        torch.cuda.synchronize()
-        tb = [timed(bare, BARE) for _ in range(3)]
+        tb = bare_call(lib, data, labels, perm, S, N, K, B, per_point, (3 if augment else 0) | (4 if sort else 0), bufs[0],
+                       torch.cuda.current_stream(dev).cuda_stream)
         lines.append("")
         lines.append("B x N x K = %d x %d x %d  (%s)" % (B, N, K, what))
         lines.append("  fused  (1 launch)          " + "  ".join("%8.1f" % v for v in tf))
