@@ -442,6 +442,39 @@ int conv3p_provider_batch_f32(const float *data, const void *labels, int S, int 
                               size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Both orders for clouds of up to 65536 rows, a cloud spread over many workgroups
+ * (pointwise_amd/csrc/conv3p_sort_wide.hpp).  The entry points above keep a cloud's keys in one workgroup's LDS, hence
+ * their limit of 8192; these keep them in a workspace and sort them in several launches.  Additions: the entry points
+ * above, their limits and their results are what they were.
+ *
+ * conv3p_sort_order_f32:  method CONV3P_SORT_XYZ: the order of conv3p_sort_xyz_order_f32; CONV3P_SORT_MORTON: the order
+ *   of conv3p_sort_morton_order_f32 (the nine steps above) -- both strict total orders, so for N <= 8192 the result is
+ *   that of those entry points bit for bit.  1 <= N <= 65536; data, row_floats, order as there.  Status, in this
+ *   order: B < 0, N < 0, row_floats < 3 or an unknown method: CONV3P_ERR_INVALID_ARGUMENT; B * N == 0: CONV3P_OK, nothing
+ *   launched; data or order NULL: CONV3P_ERR_INVALID_ARGUMENT; N > 65536: CONV3P_ERR_UNSUPPORTED; workspace NULL or
+ *   shorter than conv3p_sort_order_workspace_bytes(B, N, method): CONV3P_ERR_WORKSPACE -- all before any launch.
+ *   The workspace need not be initialised and nothing is kept in it between calls.
+ * conv3p_provider_batch_wide_f32:  conv3p_provider_batch_f32's arguments, meaning, draws and status codes, with two
+ *   differences: _SORT is required (CONV3P_ERR_INVALID_ARGUMENT without it) and N <= 65536.  Scratch from
+ *   conv3p_provider_wide_workspace_bytes.  Several launches instead of one: the augmented rows into the workspace, the
+ *   sort, the gather.  Wherever conv3p_provider_batch_f32 accepts the same call, every output is bit-equal to its.
+ * The _bytes functions return a multiple of 256, and 0 for B <= 0, N <= 0, N > 65536, an unknown method, flags
+ *   without _SORT.  Bitwise reproducible; a cloud's order does not depend on B or on its place in the batch.
+ * ------------------------------------------------------------------------------------------- */
+#define CONV3P_SORT_XYZ 0
+#define CONV3P_SORT_MORTON 1
+size_t conv3p_sort_order_workspace_bytes(int B, int N, int method);
+int conv3p_sort_order_f32(const float *data, int B, int N, int row_floats, int method, int32_t *order, void *workspace,
+                          size_t workspace_bytes, void *stream);
+size_t conv3p_provider_wide_workspace_bytes(int B, int N, int flags);
+int conv3p_provider_batch_wide_f32(const float *data, const void *labels, int S, int Nsrc, int K, int label_bytes,
+                                   int labels_per_point, const int32_t *perm, int64_t perm_len, int64_t start, int B,
+                                   int N, int flags, double sigma, double clip, uint64_t seed, uint64_t step,
+                                   const double *cos_sin, const double *noise, float *points, float *input,
+                                   int32_t *labels_out, double *cos_sin_out, double *noise_out, int32_t *order_out,
+                                   int32_t *bad_index, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:
  * view (B, N*36) -> fully_connected 512, selu -> dropout_selu -> fully_connected num_class, selu).
  * tf.contrib.layers.fully_connected is y = activation(x . W + b) with W of shape (K, N).

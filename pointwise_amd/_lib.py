@@ -31,6 +31,8 @@ ABI_VERSION = 5                # CONV3P_ABI_VERSION of include/conv3p.h
 STACK_MAX_LAYERS = 8
 OPT_MAX_TENSORS = 16             # CONV3P_OPT_MAX_TENSORS
 PROVIDER_ROTATE, PROVIDER_JITTER, PROVIDER_SORT, PROVIDER_MORTON = 1, 2, 4, 8   # CONV3P_PROVIDER_*
+SORT_XYZ, SORT_MORTON = 0, 1      # CONV3P_SORT_*: the methods of conv3p_sort_order_f32
+WIDE_SORT_MAX_POINTS = 65536      # its limit, and conv3p_provider_batch_wide_f32's
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -112,6 +114,9 @@ SYMBOLS = {
     "conv3p_provider_batch_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_sort_order_workspace_bytes": (_sz, [_i, _i, _i]),
+    "conv3p_sort_order_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "conv3p_provider_wide_workspace_bytes": (_sz, [_i, _i, _i]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),
@@ -129,6 +134,8 @@ SYMBOLS = {
 for _sfx, _real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
     for _name, _s in _sig(_real).items():
         SYMBOLS["conv3p_%s_%s" % (_name, _sfx)] = _s
+
+SYMBOLS["conv3p_provider_batch_wide_f32"] = SYMBOLS["conv3p_provider_batch_f32"]   # the same parameter list
 
 _LIB = None
 

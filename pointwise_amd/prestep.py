@@ -6,7 +6,9 @@ Names, argument meaning and results follow the reference functions
     sort_point_cloud_morton                                                /root/reference/modelnet_provider.py:100-110
 with torch tensors on a HIP device in place of numpy arrays: the per-cloud Python loops of the reference become one
 kernel launch per batch (include/conv3p.h: conv3p_augment_f32, conv3p_sort_xyz_order_f32,
-conv3p_sort_morton_order_f32, conv3p_gather_rows).
+conv3p_sort_morton_order_f32, conv3p_gather_rows).  Those two sorts take clouds of up to 8192 points; sort_order,
+sort_point_cloud and sort_point_cloud2 give the same orders for up to 65536, a cloud spread over many workgroups
+(conv3p_sort_order_f32).
 Random numbers are drawn by the caller's generator (numpy on the host for the B angles, exactly as the reference
 does; torch on the device for the B x N x 3 Gaussian noise) and can be passed in explicitly, which is how the tests
 compare with the reference functions.  The reference's sort_point_cloud_morton takes its codes from the third-party
@@ -147,4 +149,48 @@ def sort_point_cloud_morton2(batch_data, batch_attributes):
     """The same, the per-point attributes (any dtype, BxN or BxNxM) permuted accordingly, as sort_point_cloud_xyz2: what
     the scene providers need for their labels."""
     order = sort_order_morton(batch_data)
+    return _gather(batch_data, order), _gather(batch_attributes, order)
+
+
+SORT_METHODS = {"xyz": _lib.SORT_XYZ, "morton": _lib.SORT_MORTON}
+
+
+def _check_sort_method(sort_method):
+    """An unknown method is an error raised before anything touches the device, as in the provider."""
+    if sort_method not in SORT_METHODS:
+        raise ValueError("sort_method must be one of %s, not %r" % (", ".join(map(repr, SORT_METHODS)), sort_method))
+    return SORT_METHODS[sort_method]
+
+
+def sort_order(batch_data, sort_method="xyz", workspace=None):
+    """int32 (B, N): sort_order_xyz's ("xyz") or sort_order_morton's ("morton") permutation, bit for bit, for clouds
+    of up to 65536 points (include/conv3p.h: conv3p_sort_order_f32).  workspace: a uint8 device tensor of at least
+    conv3p_sort_order_workspace_bytes bytes to sort in (default: a fresh one); its contents do not matter."""
+    method = _check_sort_method(sort_method)
+    lib = _lib.load()
+    dev = _check_device(batch_data)
+    if batch_data.dim() != 3 or batch_data.shape[2] < 3 or batch_data.dtype != torch.float32:
+        raise Conv3pInvalidArgument("expected a float32 BxNxK batch whose first three channels are XYZ")
+    B, N, K = batch_data.shape
+    x = batch_data.contiguous()
+    order = torch.empty((B, N), dtype=torch.int32, device=dev)
+    need = lib.conv3p_sort_order_workspace_bytes(B, N, method)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise Conv3pInvalidArgument("workspace must be a contiguous uint8 tensor on the batch's device")
+    with torch.cuda.device(dev):
+        _call(lib.conv3p_sort_order_f32, x.data_ptr(), B, N, K, method, order.data_ptr(),
+              workspace.data_ptr() if workspace.numel() else None, workspace.numel(), _stream(dev))
+    return order
+
+
+def sort_point_cloud(batch_data, sort_method="xyz"):
+    """sort_point_cloud_xyz / sort_point_cloud_morton for clouds of up to 65536 points."""
+    return _gather(batch_data, sort_order(batch_data, sort_method))
+
+
+def sort_point_cloud2(batch_data, batch_attributes, sort_method="xyz"):
+    """sort_point_cloud_xyz2 / sort_point_cloud_morton2 for clouds of up to 65536 points."""
+    order = sort_order(batch_data, sort_method)
     return _gather(batch_data, order), _gather(batch_attributes, order)

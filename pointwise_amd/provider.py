@@ -17,6 +17,10 @@ its codes from the third-party `libpluie`, which nobody has).
     assemble_batch   the call, on tensors
     BatchProvider    the reference providers' interface (next_epoch, has_next_batch, next_batch,
                      get_batch_point_cloud, num_batches, num_points, num_channels) over it
+
+A sorted batch is one launch for clouds of up to 8192 points.  wide_sort=True routes a sorted batch to
+conv3p_provider_batch_wide_f32 instead: several launches, a cloud spread over many workgroups, up to 65536 points, the
+same bits wherever both apply (pointwise_amd/csrc/conv3p_sort_wide.hpp).
 """
 import numpy as np
 import torch
@@ -43,18 +47,22 @@ def _sort_flags(sort_cloud, sort_method):
     return _lib.PROVIDER_SORT | (_lib.PROVIDER_MORTON if sort_method == "morton" else 0)
 
 
+def _workspace_bytes(lib, wide):
+    return lib.conv3p_provider_wide_workspace_bytes if wide else lib.conv3p_provider_workspace_bytes
+
+
 class BatchBuffers:
     """The output tensors of one batch and the call's scratch: points (B, N, 3), input (B, N, K), labels int32 (B) or
     (B, N), bad_index int32 (), and -- with randoms -- cos_sin (B, 2), noise (B, N, 3) float64, order int32 (B, N)."""
 
-    def __init__(self, B, N, K, per_point, device, sort_cloud=False, randoms=False, sort_method="xyz"):
+    def __init__(self, B, N, K, per_point, device, sort_cloud=False, randoms=False, sort_method="xyz", wide_sort=False):
         self.shape = (B, N, K, bool(per_point))
         self.points = torch.empty((B, N, 3), dtype=torch.float32, device=device)
         self.input = torch.empty((B, N, K), dtype=torch.float32, device=device)
         self.labels = torch.empty((B, N) if per_point else (B,), dtype=torch.int32, device=device)
         self.bad_index = torch.zeros((), dtype=torch.int32, device=device)
         flags = _sort_flags(sort_cloud, _check_sort_method(sort_method))
-        nbytes = _lib.load().conv3p_provider_workspace_bytes(B, N, flags)
+        nbytes = _workspace_bytes(_lib.load(), wide_sort and sort_cloud)(B, N, flags)
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
         self.cos_sin = self.noise = self.order = None
         if randoms:
@@ -69,7 +77,7 @@ def _ptr(t):
 
 def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0, rotate=False, jitter=False, sigma=0.01,
                    clip=0.05, sort_cloud=False, seed=0, step=0, cos_sin=None, noise=None, out=None, return_randoms=False,
-                   sort_method="xyz"):
+                   sort_method="xyz", wide_sort=False):
     """One batch from a resident data set, in one launch.
 
     data float32 (S, Nsrc, K) with xyz first; labels uint8 / int32 / int64, (S,) or (S, Nsrc); cloud b is sample
@@ -78,8 +86,10 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
     modelnet_provider.py:196-208; cos_sin (B, 2) and noise (B, N, 3), float64 device tensors, replace the draws of
     (seed, step).  out: a BatchBuffers to write into (default: fresh tensors).
     -> (points (B, N, 3), input (B, N, K), labels int32, bad_index) and, with return_randoms, a dict of cos_sin, noise
-    (source-row order) and order.  bad_index is an int32 device scalar: the number of clouds whose sample index was
-    outside [0, S) -- their rows are 0 and their labels -1; it is not synchronised on here."""
+    (source-row order) and order.  wide_sort (inert without sort_cloud): the sort spread over many workgroups, in several
+    launches, for num_points up to 65536 instead of 8192; the same bits.  bad_index is an int32 device scalar: the number
+    of clouds whose sample index was outside [0, S) -- their rows are 0 and their labels -1; it is not synchronised on
+    here."""
     _check_sort_method(sort_method)
     lib = _lib.load()
     _require(isinstance(data, torch.Tensor) and data.dim() == 3 and data.dtype == torch.float32 and data.shape[2] >= 3,
@@ -115,14 +125,15 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
                  and t.is_contiguous(), "%s must be a contiguous float64 %s tensor on the data's device" % (name, shape))
     _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
     if out is None:
-        out = BatchBuffers(B, N, K, per_point, dev, sort_cloud, return_randoms, sort_method)
+        out = BatchBuffers(B, N, K, per_point, dev, sort_cloud, return_randoms, sort_method, wide_sort)
     else:
         _require(isinstance(out, BatchBuffers) and out.shape == (B, N, K, per_point) and out.points.device == dev,
                  "out was made for another batch shape")
         _require(not return_randoms or out.noise is not None, "out has no buffers for the randoms")
     flags = ((_lib.PROVIDER_ROTATE if rotate else 0) | (_lib.PROVIDER_JITTER if jitter else 0)
              | _sort_flags(sort_cloud, sort_method))
-    need = lib.conv3p_provider_workspace_bytes(B, N, flags)
+    wide = bool(wide_sort and sort_cloud)
+    need = _workspace_bytes(lib, wide)(B, N, flags)
     ws = out.workspace
     if need and (ws is None or ws.numel() < need):
         ws = out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -133,7 +144,8 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
         res = (out.points, out.input, out.labels, out.bad_index)
         return res + ({"cos_sin": out.cos_sin, "noise": out.noise, "order": out.order},) if return_randoms else res
     with torch.cuda.device(dev):
-        _call(lib.conv3p_provider_batch_f32, _ptr(data), _ptr(labels), S, Nsrc, K, _LABEL_DTYPES[labels.dtype],
+        _call(lib.conv3p_provider_batch_wide_f32 if wide else lib.conv3p_provider_batch_f32,
+              _ptr(data), _ptr(labels), S, Nsrc, K, _LABEL_DTYPES[labels.dtype],
               int(per_point), perm.data_ptr() if perm is not None else None, perm.numel() if perm is not None else 0,
               start, B, N, flags, float(sigma), float(clip), int(seed), int(step), _ptr(cos_sin), _ptr(noise),
               _ptr(out.points), _ptr(out.input), _ptr(out.labels),
@@ -158,11 +170,13 @@ class BatchProvider:
 
     get_batch_point_cloud() -> (points, input, labels int32); the tensors alternate between two buffer sets, so a batch
     stays valid while the next one is assembled.  bad_index (int32 device scalar) belongs to the last batch.
-    sort_method ("xyz" or "morton") is a constructor setting like sort_cloud, not state: state_dict does not carry it."""
+    sort_method ("xyz" or "morton") is a constructor setting like sort_cloud, not state: state_dict does not carry it.
+    Neither is wide_sort (assemble_batch's: sorted batches of clouds of up to 65536 points; inert without sort_cloud)."""
 
     def __init__(self, data, labels, batch_size, num_points=None, training=True, rotate=None, jitter=None,
-                 sort_cloud=False, seed=0, device="cuda:0", sort_method="xyz"):
+                 sort_cloud=False, seed=0, device="cuda:0", sort_method="xyz", wide_sort=False):
         self.sort_method = _check_sort_method(sort_method)
+        self.wide_sort = bool(wide_sort)
         self.device = torch.device(device)
         as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, order="C"))   # a copy: uploaded once
         data, labels = as_t(data), as_t(labels)
@@ -189,7 +203,7 @@ class BatchProvider:
         self.sigma, self.clip = 0.01, 0.05                                       # jitter_point_cloud's defaults, :64
         per_point = self.labels.dim() == 2
         self._buffers = [BatchBuffers(self.batch_size, self.num_points, K, per_point, self.device, self.sort_cloud,
-                                      sort_method=self.sort_method) for _ in range(2)]
+                                      sort_method=self.sort_method, wide_sort=self.wide_sort) for _ in range(2)]
         self._turn = 0
         self.bad_index = self._buffers[0].bad_index
         self.epoch = -1
@@ -223,13 +237,13 @@ class BatchProvider:
             B, N, K, per_point = buf.shape
             for i in range(2):
                 self._buffers[i] = BatchBuffers(B, N, K, per_point, self.device, self.sort_cloud, randoms=True,
-                                                sort_method=self.sort_method)
+                                                sort_method=self.sort_method, wide_sort=self.wide_sort)
             buf = self._buffers[self._turn]
         self._turn ^= 1
         res = assemble_batch(self.data, self.labels, self.batch_size, self.num_points, self.permutation,
                              self.cur_batch * self.batch_size, self.rotate, self.jitter, self.sigma, self.clip,
                              self.sort_cloud, self.seed, self.step, out=buf, return_randoms=return_randoms,
-                             sort_method=self.sort_method)
+                             sort_method=self.sort_method, wide_sort=self.wide_sort)
         self.bad_index = res[3]
         return res[:3] + res[4:]
 
