@@ -475,6 +475,71 @@ int conv3p_provider_batch_wide_f32(const float *data, const void *labels, int S,
                                    int32_t *bad_index, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A room to model-sized blocks and block predictions back to a label per room row
+ * (pointwise_amd/csrc/conv3p_scene.hpp).  The segmentation model takes (B, 4096, 9) blocks
+ * (scene_seg/s3dis_provider.py:9, :62-63); the partition that made those files is PointNet's
+ * room2blocks_plus_normalized (indoor3d_util), which is not in the reference tree, so it is DEFINED here
+ * (tests/scene_ref.py restates it in numpy).  One room per call; rows are float32, xyz first, z up.
+ *
+ * conv3p_scene_blocks_f32:  data (N, K), K >= 3; labels (N) of label_bytes = 1 / 4 / 8 (uint8 / int32 / int64), NULL
+ *   together with labels_out: no labels.  P = num_point.
+ *    1. A row is finite if x, y and z are finite.  Other rows belong to no cell and are counted in stats[4].
+ *    2. lo[a] = minimum of coordinate a over the finite rows; s[a] = v[a] - lo[a], one float32 subtraction, a = x, y,
+ *       z; lim[a] = maximum of s[a] over the finite rows.
+ *    3. nbx = max(1, (int)ceil((double(lim_x) - double(block)) / double(stride)) + 1), nby alike (PointNet's count with
+ *       a floor of one; each held at 2^30).  With no finite row nbx = nby = 0.
+ *    4. Cell (i, j) has id c = i * nby + j, edges xbeg = float(i) * stride (one float32 product), xend = xbeg + block
+ *       (one float32 sum), y alike.  A finite row is a member iff xbeg <= s_x <= xend and ybeg <= s_y <= yend: both
+ *       ends inclusive, so a row on an edge, or under overlapping strides, belongs to several cells.
+ *    5. count[c] = number of members.  A cell is kept iff count[c] >= max(1, min_points).  Kept cells get block numbers
+ *       in ascending c; blocks numbered >= max_blocks are not emitted.
+ *    6. A cell's member list is in ascending room row.
+ *    7. Block b of cell c, n = count[c], has P slots.  Slot t takes member t when n <= P and t < n.  Every other slot
+ *       (every slot when n > P) is a draw, with replacement as PointNet's sample_data:
+ *       w = philox4x32_10(counter (t, 0x80000000 | c, step low, step high), key (seed low, seed high)).w[0],
+ *       member (uint64(w) * n) >> 32.  The counter's second word is disjoint from the provider's and the dropout's.
+ *    8. index_out[b][t] = the slot's room row; labels_out = that row's label cast to int32.  With bmin_x, bmin_y the
+ *       minima of s_x, s_y over the block's P emitted rows and h = block * 0.5f, the output row is
+ *       {s_x - (bmin_x + h), s_y - (bmin_y + h), s_z, channels 3..K-1 copied, s_x / lim_x, s_y / lim_y, s_z / lim_z},
+ *       each operation a single float32 one; a division by lim == 0 gives 0.
+ *    9. Blocks nb..max_blocks-1 (nb = emitted blocks) get data 0, labels -1, index -1, block_cell -1, block_count 0:
+ *       both heads and the vote ignore them.  block_cell[b] = c and block_count[b] = n otherwise.
+ *   10. stats = {emitted blocks, kept cells, nbx, nby, non-finite rows, cells with 0 < count < min_points, 0, error}.
+ *       nbx * nby > CONV3P_SCENE_MAX_CELLS: nothing is emitted (all blocks are step 9's) and stats[7] = 1 -- known
+ *       on the device only, so not a status code.
+ *   Status, in this order, all before any launch: N < 0, K < 3, num_point < 1, max_blocks < 0, block or stride not
+ *   finite or <= 0, labels given without labels_out or the reverse, labels with label_bytes not 1 / 4 / 8:
+ *   CONV3P_ERR_INVALID_ARGUMENT; N == 0 or max_blocks == 0: CONV3P_OK, nothing launched, nothing written; data,
+ *   blocks_out, index_out, block_cell, block_count or stats NULL: CONV3P_ERR_INVALID_ARGUMENT; N > 2^24, num_point >
+ *   65536, K > 65536 or block outside [stride, 2 stride]: CONV3P_ERR_UNSUPPORTED; workspace NULL, misaligned or shorter
+ *   than conv3p_scene_blocks_workspace_bytes: CONV3P_ERR_WORKSPACE.  That size is a host-side upper bound from its five
+ *   arguments (the cell counts, and member lists of at most N * (ceil(block / stride) + 1)^2 entries), a multiple of
+ *   256, 0 for arguments the call refuses or does nothing for; never a data-dependent failure.  The workspace need not
+ *   be initialised and nothing is kept in it between calls.  Seven launches; no float atomics; every output word is
+ *   written once by a plain store; bitwise reproducible.
+ *
+ * conv3p_scene_vote:  every row r with 0 <= index[r] < N and 0 <= pred[r] < num_class adds 1 to
+ *   votes[index[r]][pred[r]] (int32 (N, num_class), ACCUMULATED into: the caller zeroes it, so several passes -- other
+ *   steps, overlapping strides -- add up).  Each emitted row votes, so a room row drawn twice votes twice.  Integer
+ *   atomics: exact.  Status: N < 0 or num_class < 1: CONV3P_ERR_INVALID_ARGUMENT; rows == 0 or N == 0: CONV3P_OK,
+ *   nothing launched; a NULL pointer: CONV3P_ERR_INVALID_ARGUMENT; N > 2^31 - 1: CONV3P_ERR_UNSUPPORTED.
+ * conv3p_scene_vote_labels:  label_out[i] = the class with the most votes of room row i, the lowest class on a tie, -1
+ *   for a row without votes; stats = int64 {voted rows, unvoted rows}.  Status as above (N == 0: CONV3P_OK, nothing
+ *   written), then CONV3P_ERR_WORKSPACE against conv3p_scene_vote_labels_workspace_bytes.  Two launches.
+ * ------------------------------------------------------------------------------------------- */
+#define CONV3P_SCENE_MAX_CELLS 65536
+size_t conv3p_scene_blocks_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride);
+int conv3p_scene_blocks_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float block,
+                            float stride, int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step,
+                            float *blocks_out, int32_t *labels_out, int32_t *index_out, int32_t *block_cell,
+                            int32_t *block_count, int32_t *stats, void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_scene_vote(const int32_t *pred, const int32_t *index, size_t rows, int64_t N, int num_class, int32_t *votes,
+                      void *stream);
+size_t conv3p_scene_vote_labels_workspace_bytes(int64_t N, int num_class);
+int conv3p_scene_vote_labels(const int32_t *votes, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:
  * view (B, N*36) -> fully_connected 512, selu -> dropout_selu -> fully_connected num_class, selu).
  * tf.contrib.layers.fully_connected is y = activation(x . W + b) with W of shape (K, N).

@@ -4,13 +4,15 @@ Only what the path needs: csrc/ (hand-written gfx950 HIP kernels + the C ABI of 
 conv3p_op (host mirror of the reference's operator interface), stack (the models' conv3p layer stacks),
 head, seg_head (the two models' heads), optim (the training drivers' momentum optimizer), distributed (batch sharding + RCCL all-reduce of the weight gradients),
 provider (the reference providers' per-batch work as one launch over a resident data set),
+scene (a room to model-sized blocks, block predictions voted back to the room's rows),
 synth (synthetic clouds).
 """
 from .conv3p_op import (Conv3pFunction, Conv3pInvalidArgument, Conv3pRuntimeError, conv3p, conv3p_autograd,
                         conv3p_grad, conv3p_layer, conv3p_layer_grad, neighbor_count, selu, selu_grad)
 from .optim import MomentumOptimizer, exponential_decay, momentum_step
 from .provider import BatchBuffers, BatchProvider, assemble_batch
+from .scene import SceneBlocks, SceneVotes, default_max_blocks, scene_blocks
 from .seg_head import SegmentationHead, class_weights_from_counts
 
-__all__ = ["BatchProvider", "BatchBuffers", "assemble_batch", "SegmentationHead", "class_weights_from_counts", "MomentumOptimizer", "exponential_decay", "momentum_step", "conv3p", "conv3p_grad", "conv3p_layer", "conv3p_layer_grad", "conv3p_autograd", "Conv3pFunction", "neighbor_count", "selu", "selu_grad",
+__all__ = ["scene_blocks", "SceneBlocks", "SceneVotes", "default_max_blocks","BatchProvider", "BatchBuffers", "assemble_batch", "SegmentationHead", "class_weights_from_counts", "MomentumOptimizer", "exponential_decay", "momentum_step", "conv3p", "conv3p_grad", "conv3p_layer", "conv3p_layer_grad", "conv3p_autograd", "Conv3pFunction", "neighbor_count", "selu", "selu_grad",
            "Conv3pInvalidArgument", "Conv3pRuntimeError"]

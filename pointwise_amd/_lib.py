@@ -33,6 +33,9 @@ OPT_MAX_TENSORS = 16             # CONV3P_OPT_MAX_TENSORS
 PROVIDER_ROTATE, PROVIDER_JITTER, PROVIDER_SORT, PROVIDER_MORTON = 1, 2, 4, 8   # CONV3P_PROVIDER_*
 SORT_XYZ, SORT_MORTON = 0, 1      # CONV3P_SORT_*: the methods of conv3p_sort_order_f32
 WIDE_SORT_MAX_POINTS = 65536      # its limit, and conv3p_provider_batch_wide_f32's
+SCENE_MAX_CELLS = 65536           # CONV3P_SCENE_MAX_CELLS
+SCENE_MAX_ROWS = 1 << 24          # conv3p_scene_blocks_f32's limits: room rows, rows of a block
+SCENE_MAX_NUM_POINT = 65536
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -117,6 +120,12 @@ SYMBOLS = {
     "conv3p_sort_order_workspace_bytes": (_sz, [_i, _i, _i]),
     "conv3p_sort_order_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "conv3p_provider_wide_workspace_bytes": (_sz, [_i, _i, _i]),
+    "conv3p_scene_blocks_workspace_bytes": (_sz, [ctypes.c_int64, _i, _i, ctypes.c_float, ctypes.c_float]),
+    "conv3p_scene_blocks_f32": (_i, [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_float, ctypes.c_float, _i, _i, _i,
+                                     ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_scene_vote": (_i, [_vp, _vp, _sz, ctypes.c_int64, _i, _vp, _vp]),
+    "conv3p_scene_vote_labels_workspace_bytes": (_sz, [ctypes.c_int64, _i]),
+    "conv3p_scene_vote_labels": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

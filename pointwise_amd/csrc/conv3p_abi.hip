@@ -25,6 +25,7 @@
 #include "conv3p_cls_tail.hpp"
 #include "conv3p_provider.hpp"
 #include "conv3p_sort_wide.hpp"
+#include "conv3p_scene.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3569,6 +3570,129 @@ int conv3p_provider_batch_f32(PROVIDER_PARAMS) { return provider_impl(false, PRO
 int conv3p_provider_batch_wide_f32(PROVIDER_PARAMS) { return provider_impl(true, PROVIDER_ARGS); }
 #undef PROVIDER_PARAMS
 #undef PROVIDER_ARGS
+
+namespace {
+// The workspace of conv3p_scene_blocks_f32 (conv3p_scene.hpp): a host-side upper bound from the five arguments.
+struct ScenePlan { int records, chunk_rows, chunks, blocks; size_t hdr, rec, count, blk, chunk_count, members, total; };
+bool scene_plan(int64_t N, int num_point, int max_blocks, float block, float stride, ScenePlan &w)
+{
+    if (N <= 0 || N > kSceneMaxN || num_point < 1 || num_point > kSceneMaxP || max_blocks <= 0) return false;
+    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return false;
+    if (block < stride || block > 2.0f * stride) return false;
+    const size_t tiles = ((size_t)N + kSceneThreads - 1) / kSceneThreads;
+    w.records = (int)(tiles < (size_t)kSceneMaxRecords ? tiles : (size_t)kSceneMaxRecords);
+    const size_t even = (((size_t)N + kSceneMaxChunks - 1) / kSceneMaxChunks + kSceneThreads - 1) / kSceneThreads * kSceneThreads;
+    w.chunk_rows = (int)(even > (size_t)kSceneMinChunk ? even : (size_t)kSceneMinChunk);
+    w.chunks = (int)(((size_t)N + w.chunk_rows - 1) / w.chunk_rows);
+    w.blocks = max_blocks < kSceneMaxCells ? max_blocks : kSceneMaxCells;
+    const size_t m = (size_t)std::ceil((double)block / (double)stride) + 1;          // cells a row can be in, an axis
+    w.hdr = up(sizeof(SceneHeader));
+    w.rec = up((size_t)kSceneMaxRecords * 8 * sizeof(float));
+    w.count = up((size_t)kSceneMaxCells * sizeof(int));
+    w.blk = up((size_t)w.blocks * sizeof(int));
+    w.chunk_count = up((size_t)w.blocks * kSceneMaxChunks * sizeof(int));
+    w.members = up((size_t)N * m * m * sizeof(int));
+    w.total = w.hdr + w.rec + w.count + 3 * w.blk + w.chunk_count + w.members;
+    return true;
+}
+inline unsigned scene_grid(size_t work)
+{
+    const size_t g = (work + kSceneThreads - 1) / kSceneThreads;
+    return (unsigned)(g < (size_t)kSceneMaxRecords ? (g ? g : 1) : (size_t)kSceneMaxRecords);
+}
+}  // namespace
+
+size_t conv3p_scene_blocks_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride)
+{
+    ScenePlan w;
+    return scene_plan(N, num_point, max_blocks, block, stride, w) ? w.total : 0;
+}
+
+// Every status first, in the order include/conv3p.h gives; then the seven launches, outside the profile bracket (the
+// table of kinds is pinned), as provider_impl.
+int conv3p_scene_blocks_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float block,
+                            float stride, int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step,
+                            float *blocks_out, int32_t *labels_out, int32_t *index_out, int32_t *block_cell,
+                            int32_t *block_count, int32_t *stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || K < 3 || num_point < 1 || max_blocks < 0) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N == 0 || max_blocks == 0) return CONV3P_OK;
+    if (!data || !blocks_out || !index_out || !block_cell || !block_count || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > kSceneMaxN || num_point > kSceneMaxP || K > 65536 || block < stride || block > 2.0f * stride)
+        return CONV3P_ERR_UNSUPPORTED;
+    ScenePlan w;
+    if (!scene_plan(N, num_point, max_blocks, block, stride, w)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, w.total));
+    SceneArgs a;
+    a.data = data; a.labels = labels;
+    a.N = (int)N; a.K = K; a.label_bytes = label_bytes; a.P = num_point; a.min_points = min_points; a.max_blocks = max_blocks;
+    a.block = block; a.stride = stride;
+    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
+    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
+    a.blocks_out = blocks_out; a.labels_out = labels_out; a.index_out = index_out;
+    a.block_cell = block_cell; a.block_count = block_count; a.stats = stats;
+    char *ws = static_cast<char *>(workspace);
+    a.hdr = reinterpret_cast<SceneHeader *>(ws); ws += w.hdr;
+    a.records = reinterpret_cast<float *>(ws); ws += w.rec;
+    a.count = reinterpret_cast<int *>(ws); ws += w.count;
+    a.blk_cell = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.blk_count = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.blk_off = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.chunk_count = reinterpret_cast<int *>(ws); ws += w.chunk_count;
+    a.members = reinterpret_cast<int *>(ws);
+    a.records_n = w.records; a.chunk_rows = w.chunk_rows; a.chunks = w.chunks;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t items = (size_t)w.blocks * w.chunks;
+    const unsigned igrid = (unsigned)(items < (size_t)kSceneMaxGrid ? items : (size_t)kSceneMaxGrid);
+    const unsigned egrid = (unsigned)(max_blocks < kSceneMaxGrid ? max_blocks : kSceneMaxGrid);
+    hipLaunchKernelGGL(scene_bounds_kernel, dim3((unsigned)w.records), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(scene_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, a);
+    hipLaunchKernelGGL(scene_count_kernel, dim3((unsigned)w.records), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(scene_plan_kernel, dim3(1), dim3(kScenePlanThreads), 0, s, a);
+    hipLaunchKernelGGL(scene_fill_count_kernel, dim3(igrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(scene_fill_kernel, dim3(igrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(scene_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
+    return hip_ok();
+}
+
+int conv3p_scene_vote(const int32_t *pred, const int32_t *index, size_t rows, int64_t N, int num_class, int32_t *votes,
+                      void *stream)
+{
+    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (rows == 0 || N == 0) return CONV3P_OK;
+    if (!pred || !index || !votes) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;              // index is int32
+    hipLaunchKernelGGL(scene_vote_kernel, dim3(scene_grid(rows)), dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream),
+                       pred, index, rows, (long long)N, num_class, votes);
+    return hip_ok();
+}
+
+size_t conv3p_scene_vote_labels_workspace_bytes(int64_t N, int num_class)
+{
+    if (N <= 0 || N > (int64_t)INT32_MAX || num_class < 1) return 0;
+    return up((size_t)kSceneMaxRecords * sizeof(long long));
+}
+
+int conv3p_scene_vote_labels(const int32_t *votes, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N == 0) return CONV3P_OK;
+    if (!votes || !label_out || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, conv3p_scene_vote_labels_workspace_bytes(N, num_class)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned grid = scene_grid((size_t)N);
+    long long *partial = static_cast<long long *>(workspace);
+    hipLaunchKernelGGL(scene_vote_labels_kernel, dim3(grid), dim3(kSceneThreads), 0, s, votes, (long long)N, num_class,
+                       label_out, partial);
+    hipLaunchKernelGGL(scene_vote_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, (const long long *)partial, (int)grid,
+                       (long long)N, reinterpret_cast<long long *>(stats));
+    return hip_ok();
+}
 
 namespace {
 struct FcPlan { int kc, chunks, mblocks, nblocks; size_t part_bytes, dz_bytes; };

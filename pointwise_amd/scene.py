@@ -1,0 +1,201 @@
+"""A room to model-sized blocks and block predictions back to a label per room point (include/conv3p.h:
+conv3p_scene_blocks_f32, conv3p_scene_vote, conv3p_scene_vote_labels; kernels in csrc/conv3p_scene.hpp).
+
+The segmentation model takes (B, 4096, 9) blocks (scene_seg/s3dis_provider.py:9, :62-63) and the reference only reads
+blocks that PointNet's indoor3d_util prepared (room2blocks_plus_normalized): shift the room to its minimum, tile x-y
+with block x block cells every stride, drop cells of fewer than 100 points, sample num_point rows a cell, centre x, y
+on the block, append the room-normalised xyz.  That partition is not in the reference tree; include/conv3p.h defines it
+bit for bit and tests/scene_ref.py restates it in numpy.  The evaluation loops count accuracy per block row
+(eval_and_log_scene_seg_s3dis.py:83-93); SceneVotes carries block predictions back to the room's own rows.
+
+    scene_blocks   one room (N, K) -> SceneBlocks: data (max_blocks, P, K + 3), labels, index (the room row of every
+                   emitted row), block_cell, block_count, stats
+    SceneVotes     votes (N, C) int32 accumulated from (pred, index) pairs -> labels(), counts()
+
+From a room to the model and back:
+
+    sb = scene_blocks(room, room_labels, num_point=4096, stride=0.5, step=epoch).trim()
+    pv = BatchProvider(sb.data, sb.index, batch_size, training=False, sort_cloud=True)   # index rides as the labels
+    votes = SceneVotes(room.shape[0], num_class, room.device)
+    per batch:  points, inp, rows = pv.get_batch_point_cloud()       # rows: the room row of every sorted point
+                pred = model(points, inp).argmax(-1)                  # e.g. SegmentationHead.evaluate(...)[0]
+                votes.add(pred, rows)
+    labels = votes.labels()                                          # (N) int32, -1 where no block covered the row
+
+The trimmed data / labels are what BatchProvider(data, labels, ...) takes for training; passing `index` as its
+per-point int32 "labels" instead carries the room rows through the provider's sort.  A room resampled with another
+`step` draws other rows for the slots that are draws: the scene providers' only augmentation.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .conv3p_op import _call, _require
+
+_LABEL_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def default_max_blocks(num_rows, block=1.0, stride=1.0, min_points=100):
+    """The bound scene_blocks uses for max_blocks=None, from the shape alone (no look at the data, no sync): a kept
+    cell has at least max(1, min_points) members and a row is a member of at most m x m cells, m = ceil(block /
+    stride) + 1, so there are at most num_rows m^2 // max(1, min_points) kept cells -- and never more than
+    SCENE_MAX_CELLS.  It is a loose bound (outputs are allocated for it): pass max_blocks when the room's extent is
+    known."""
+    m = int(math.ceil(float(block) / float(stride))) + 1
+    return max(1, min(_lib.SCENE_MAX_CELLS, int(num_rows) * m * m // max(1, int(min_points))))
+
+
+class SceneBlocks:
+    """The outputs of scene_blocks: data float32 (max_blocks, P, K + 3), points = data[..., 0:3] (a view), labels int32
+    (max_blocks, P) or None, index int32 (max_blocks, P), block_cell / block_count int32 (max_blocks), stats int32 (8) =
+    {emitted blocks, kept cells, nbx, nby, non-finite rows, cells with 0 < count < min_points, 0, error}.  Blocks past
+    the emitted ones hold data 0, labels -1, index -1, block_cell -1, block_count 0."""
+
+    def __init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes=0):
+        B, P = int(max_blocks), int(num_point)
+        self.shape = (B, P, int(K), bool(with_labels))
+        self.data = torch.empty((B, P, K + 3), dtype=torch.float32, device=device)
+        self.labels = torch.empty((B, P), dtype=torch.int32, device=device) if with_labels else None
+        self.index = torch.empty((B, P), dtype=torch.int32, device=device)
+        self.block_cell = torch.empty((B,), dtype=torch.int32, device=device)
+        self.block_count = torch.empty((B,), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((8,), dtype=torch.int32, device=device)
+        self.workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=device) if workspace_bytes else None
+
+    @property
+    def points(self):
+        return self.data[..., 0:3]
+
+    def num_blocks(self):
+        """The number of emitted blocks: the one host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def trim(self):
+        """Views of the first num_blocks() blocks, as a SceneBlocks (stats shared)."""
+        nb = self.num_blocks()
+        t = object.__new__(SceneBlocks)
+        t.shape = (nb,) + self.shape[1:]
+        t.data, t.index = self.data[:nb], self.index[:nb]
+        t.labels = self.labels[:nb] if self.labels is not None else None
+        t.block_cell, t.block_count = self.block_cell[:nb], self.block_count[:nb]
+        t.stats, t.workspace = self.stats, None
+        return t
+
+
+def _as_f32(x):
+    return float(np.float32(x))
+
+
+def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_points=100, max_blocks=None, seed=0,
+                 step=0, out=None):
+    """One room -> SceneBlocks, by the ten steps of include/conv3p.h (conv3p_scene_blocks_f32).
+
+    data float32 (N, K >= 3), xyz first, z up; labels (N) uint8 / int32 / int64 or None.  block and stride are taken
+    as float32, block in [stride, 2 stride].  max_blocks=None: default_max_blocks(N, block, stride, min_points), a
+    bound from the shape alone.  (seed, step) select the draws.  out: a SceneBlocks of an earlier call with the same
+    shapes, written into.  Nothing is synchronised on; stats[7] != 0 reports a tiling of more than SCENE_MAX_CELLS
+    cells (nothing emitted)."""
+    _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
+             "data must be a float32 (N, K >= 3) tensor, xyz first")
+    dev = data.device
+    N, K = data.shape
+    _require(data.is_contiguous(), "data must be contiguous")
+    if labels is not None:
+        _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
+        _require(labels.device == dev and tuple(labels.shape) == (N,) and labels.is_contiguous(),
+                 "labels must be a contiguous (N,) tensor on the data's device")
+    _require(isinstance(num_point, int) and 1 <= num_point <= _lib.SCENE_MAX_NUM_POINT,
+             "num_point must be an integer in [1, %d]" % _lib.SCENE_MAX_NUM_POINT)
+    for name, v in (("block", block), ("stride", stride)):
+        _require(isinstance(v, (int, float)) and math.isfinite(v) and _as_f32(v) > 0, "%s must be finite and positive" % name)
+    block, stride = _as_f32(block), _as_f32(stride)
+    _require(stride <= block <= _as_f32(np.float32(2) * np.float32(stride)), "block must lie in [stride, 2 stride]")
+    _require(N <= _lib.SCENE_MAX_ROWS, "at most 2^24 room rows")
+    _require(K <= 65536, "at most 65536 channels")
+    _require(isinstance(min_points, int) and -2 ** 31 <= min_points < 2 ** 31, "min_points must be an int32")
+    if max_blocks is None:
+        max_blocks = default_max_blocks(N, block, stride, min_points)
+    _require(isinstance(max_blocks, int) and 0 <= max_blocks < 2 ** 31, "max_blocks must be a non-negative integer")
+    _require(0 <= int(seed) < 2 ** 64 and 0 <= int(step) < 2 ** 64, "seed and step must fit 64 unsigned bits")
+    if out is not None:
+        _require(isinstance(out, SceneBlocks) and out.shape == (max_blocks, num_point, K, labels is not None)
+                 and out.data.device == dev, "out was made for another shape")
+    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
+    lib = _lib.load()
+    need = lib.conv3p_scene_blocks_workspace_bytes(N, num_point, max_blocks, block, stride)
+    if out is None:
+        out = SceneBlocks(max_blocks, num_point, K, labels is not None, dev, need)
+    elif need and (out.workspace is None or out.workspace.numel() < need):
+        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if N == 0 or max_blocks == 0:            # nothing is launched, so nothing is written
+        out.data.zero_()
+        out.index.fill_(-1)
+        out.block_cell.fill_(-1)
+        out.block_count.zero_()
+        out.stats.zero_()
+        if out.labels is not None:
+            out.labels.fill_(-1)
+        return out
+    ws = out.workspace
+    with torch.cuda.device(dev):
+        _call(lib.conv3p_scene_blocks_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None, N, K,
+              _LABEL_DTYPES[labels.dtype] if labels is not None else 0, block, stride, num_point, min_points, max_blocks,
+              int(seed), int(step), out.data.data_ptr(), out.labels.data_ptr() if labels is not None else None,
+              out.index.data_ptr(), out.block_cell.data_ptr(), out.block_count.data_ptr(), out.stats.data_ptr(),
+              ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+class SceneVotes:
+    """Votes of block predictions for the rows of one room: votes int32 (num_rows, num_class) on the device.
+
+    add(pred, index): every element with 0 <= index < num_rows and 0 <= pred < num_class adds one vote -- each emitted
+    row votes, so a room row drawn twice votes twice; index -1 (filler blocks) and out-of-range predictions are
+    ignored.  Votes accumulate over calls (other steps, overlapping strides) until reset().  labels() -> (num_rows)
+    int32, the class with the most votes, the lowest on a tie, -1 without votes; counts() -> int64 device tensor
+    {voted rows, unvoted rows} of the last labels() (computed if there was none)."""
+
+    def __init__(self, num_rows, num_class, device="cuda:0"):
+        _require(isinstance(num_rows, int) and 0 <= num_rows < 2 ** 31, "num_rows must be an integer in [0, 2^31)")
+        _require(isinstance(num_class, int) and num_class >= 1, "num_class must be a positive integer")
+        self.device = torch.device(device)
+        _require(self.device.type == "cuda", "votes live on a HIP device (there is no CPU path)")
+        self.num_rows, self.num_class = num_rows, num_class
+        self.votes = torch.zeros((num_rows, num_class), dtype=torch.int32, device=self.device)
+        self._labels = torch.empty((num_rows,), dtype=torch.int32, device=self.device)
+        self._counts = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        nbytes = _lib.load().conv3p_scene_vote_labels_workspace_bytes(num_rows, num_class)
+        self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if nbytes else None
+        self._fresh = False
+
+    def reset(self):
+        self.votes.zero_()
+        self._fresh = False
+
+    def add(self, pred, index):
+        for name, t in (("pred", pred), ("index", index)):
+            _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == self.device
+                     and t.is_contiguous(), "%s must be a contiguous int32 tensor on the votes' device" % name)
+        _require(pred.numel() == index.numel(), "pred and index must have as many elements")
+        self._fresh = False
+        if pred.numel() == 0 or self.num_rows == 0:
+            return
+        with torch.cuda.device(self.device):
+            _call(_lib.load().conv3p_scene_vote, pred.data_ptr(), index.data_ptr(), pred.numel(), self.num_rows,
+                  self.num_class, self.votes.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+
+    def labels(self):
+        if self.num_rows and not self._fresh:
+            ws = self._workspace
+            with torch.cuda.device(self.device):
+                _call(_lib.load().conv3p_scene_vote_labels, self.votes.data_ptr(), self.num_rows, self.num_class,
+                      self._labels.data_ptr(), self._counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                      torch.cuda.current_stream(self.device).cuda_stream)
+            self._fresh = True
+        return self._labels
+
+    def counts(self):
+        self.labels()
+        return self._counts
