@@ -526,6 +526,42 @@ int conv3p_provider_batch_wide_f32(const float *data, const void *labels, int S,
  * conv3p_scene_vote_labels:  label_out[i] = the class with the most votes of room row i, the lowest class on a tie, -1
  *   for a row without votes; stats = int64 {voted rows, unvoted rows}.  Status as above (N == 0: CONV3P_OK, nothing
  *   written), then CONV3P_ERR_WORKSPACE against conv3p_scene_vote_labels_workspace_bytes.  Two launches.
+ *
+ * conv3p_scene_blocks_cover_f32:  the COVERING mode of the partition, for evaluation: a crowded cell is not sampled but
+ *   split, so every finite row of a kept cell is emitted (pointwise_amd/csrc/conv3p_scene_cover.hpp;
+ *   tests/scene_cover_ref.py restates it).  The argument list, the statuses and their order are
+ *   conv3p_scene_blocks_f32's, the workspace size is conv3p_scene_blocks_cover_workspace_bytes (the same five arguments,
+ *   the same properties).  Steps 1-4, 6, 8 and 9 are as above; the others:
+ *    5'. A kept cell c with n = count[c] members gives q = ceil(n / P) blocks, its parts j = 0..q-1 (q = 1 when
+ *        n <= P).  Blocks are numbered in ascending (c, j); blocks numbered >= max_blocks are not emitted, so a cell
+ *        may be cut between two parts.
+ *    7'. Part j holds the members of rank [a_j, a_{j+1}) of the cell's ascending list, a_j = floor(j * n / q) in 64-bit
+ *        integers; so n_j = a_{j+1} - a_j <= P, and n_j >= floor(P / 2) whenever q > 1.  Slot t < n_j takes member
+ *        a_j + t.  Every other slot is a draw among the part's own members: member a_j + ((uint64(w) * n_j) >> 32),
+ *        w = philox4x32_10(counter (j * P + t, 0x80000000 | c, step low, step high), key (seed low, seed high)).w[0];
+ *        j * P + t < 2^25.  For j = 0 this is step 7's counter: a cell with n <= P comes out bit for bit as in the
+ *        plain mode.
+ *    9'. block_cell[b] = c and block_count[b] = n_j: the first block_count[b] slots of a block are distinct members,
+ *        the rest are draws; the parts of a cell are consecutive blocks with equal block_cell.
+ *   10'. stats[6] = the blocks the room needs (the sum of q over the kept cells); stats[0] < stats[6] tells that
+ *        max_blocks cut the room.  The other words keep their meaning (the plain call writes stats[6] = 0).
+ *   When nothing is cut, the slots t < block_count[b] over the blocks of a cell are the cell's member list, each row
+ *   exactly once, in ascending order.  Eight launches; no float atomics; every output word is written once by a plain
+ *   store; bitwise reproducible.
+ *
+ * conv3p_scene_vote_scores_f32:  votes by summed class probabilities.  logits (rows, num_class) float32, the model's
+ *   last activations.  A row r votes iff 0 <= index[r] < N and all its num_class logits are finite; it computes, each
+ *   step a single float32 operation and the sum in ascending class, m = max_c x_c, e_c = expf(x_c - m), S = sum_c e_c,
+ *   p_c = e_c / S, v_c = llrintf(p_c * 2^30), and adds v_c to scores[index[r]][c] (int64 (N, num_class), ACCUMULATED
+ *   into: the caller zeroes it) with a 64-bit integer atomic: fixed point, so exact and independent of the order of
+ *   the rows and of the launch geometry.  stats (int64 (2)) is accumulated into as well: stats[0] += rows that voted,
+ *   stats[1] += rows with a valid index and a non-finite logit.  Status: N < 0 or num_class < 1:
+ *   CONV3P_ERR_INVALID_ARGUMENT; rows == 0 or N == 0: CONV3P_OK, nothing launched; a NULL pointer:
+ *   CONV3P_ERR_INVALID_ARGUMENT; N > 2^31 - 1 or num_class > 128: CONV3P_ERR_UNSUPPORTED.  One launch.
+ * conv3p_scene_score_labels:  label_out[i] = the class with the largest score of room row i, the lowest class on a
+ *   tie, -1 where all scores are 0; stats = int64 {voted rows, unvoted rows}.  Status as conv3p_scene_vote_labels
+ *   (num_class > 128: CONV3P_ERR_UNSUPPORTED), then CONV3P_ERR_WORKSPACE against
+ *   conv3p_scene_score_labels_workspace_bytes.  Two launches.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_SCENE_MAX_CELLS 65536
 size_t conv3p_scene_blocks_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride);
@@ -538,6 +574,17 @@ int conv3p_scene_vote(const int32_t *pred, const int32_t *index, size_t rows, in
 size_t conv3p_scene_vote_labels_workspace_bytes(int64_t N, int num_class);
 int conv3p_scene_vote_labels(const int32_t *votes, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
                              void *workspace, size_t workspace_bytes, void *stream);
+size_t conv3p_scene_blocks_cover_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride);
+int conv3p_scene_blocks_cover_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float block,
+                                  float stride, int num_point, int min_points, int max_blocks, uint64_t seed,
+                                  uint64_t step, float *blocks_out, int32_t *labels_out, int32_t *index_out,
+                                  int32_t *block_cell, int32_t *block_count, int32_t *stats, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int conv3p_scene_vote_scores_f32(const float *logits, const int32_t *index, size_t rows, int64_t N, int num_class,
+                                 int64_t *scores, int64_t *stats, void *stream);
+size_t conv3p_scene_score_labels_workspace_bytes(int64_t N, int num_class);
+int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

@@ -126,6 +126,12 @@ SYMBOLS = {
     "conv3p_scene_vote": (_i, [_vp, _vp, _sz, ctypes.c_int64, _i, _vp, _vp]),
     "conv3p_scene_vote_labels_workspace_bytes": (_sz, [ctypes.c_int64, _i]),
     "conv3p_scene_vote_labels": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_scene_blocks_cover_workspace_bytes": (_sz, [ctypes.c_int64, _i, _i, ctypes.c_float, ctypes.c_float]),
+    "conv3p_scene_blocks_cover_f32": (_i, [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_float, ctypes.c_float, _i, _i, _i,
+                                           ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_scene_vote_scores_f32": (_i, [_vp, _vp, _sz, ctypes.c_int64, _i, _vp, _vp, _vp]),
+    "conv3p_scene_score_labels_workspace_bytes": (_sz, [ctypes.c_int64, _i]),
+    "conv3p_scene_score_labels": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

@@ -26,6 +26,7 @@
 #include "conv3p_provider.hpp"
 #include "conv3p_sort_wide.hpp"
 #include "conv3p_scene.hpp"
+#include "conv3p_scene_cover.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3608,12 +3609,25 @@ size_t conv3p_scene_blocks_workspace_bytes(int64_t N, int num_point, int max_blo
     return scene_plan(N, num_point, max_blocks, block, stride, w) ? w.total : 0;
 }
 
-// Every status first, in the order include/conv3p.h gives; then the seven launches, outside the profile bracket (the
-// table of kinds is pinned), as provider_impl.
-int conv3p_scene_blocks_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float block,
-                            float stride, int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step,
-                            float *blocks_out, int32_t *labels_out, int32_t *index_out, int32_t *block_cell,
-                            int32_t *block_count, int32_t *stats, void *workspace, size_t workspace_bytes, void *stream)
+namespace {
+// The workspace of conv3p_scene_blocks_cover_f32 (conv3p_scene_cover.hpp): the plain call's, with its three per-block
+// arrays and the chunk counts per LISTED cell (at most min(max_blocks, cells)), plus the listed cells' first block
+// numbers and the block table.
+struct SceneCoverPlan { ScenePlan s; size_t table, total; };
+bool scene_cover_plan(int64_t N, int num_point, int max_blocks, float block, float stride, SceneCoverPlan &w)
+{
+    if (!scene_plan(N, num_point, max_blocks, block, stride, w.s)) return false;
+    w.table = up((size_t)max_blocks * sizeof(int4));
+    w.total = w.s.total + w.s.blk + w.table;
+    return true;
+}
+
+// Both modes of the partition.  Every status first, in the order include/conv3p.h gives; then the seven launches (the
+// covering mode: eight), outside the profile bracket (the table of kinds is pinned), as provider_impl.
+int scene_blocks_impl(bool cover, const float *data, const void *labels, int64_t N, int K, int label_bytes, float block,
+                      float stride, int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step,
+                      float *blocks_out, int32_t *labels_out, int32_t *index_out, int32_t *block_cell,
+                      int32_t *block_count, int32_t *stats, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (N < 0 || K < 3 || num_point < 1 || max_blocks < 0) return CONV3P_ERR_INVALID_ARGUMENT;
     if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
@@ -3623,9 +3637,10 @@ int conv3p_scene_blocks_f32(const float *data, const void *labels, int64_t N, in
     if (!data || !blocks_out || !index_out || !block_cell || !block_count || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
     if (N > kSceneMaxN || num_point > kSceneMaxP || K > 65536 || block < stride || block > 2.0f * stride)
         return CONV3P_ERR_UNSUPPORTED;
-    ScenePlan w;
-    if (!scene_plan(N, num_point, max_blocks, block, stride, w)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, w.total));
+    SceneCoverPlan cw;
+    if (!scene_cover_plan(N, num_point, max_blocks, block, stride, cw)) return CONV3P_ERR_UNSUPPORTED;
+    const ScenePlan &w = cw.s;
+    TRY(buf_check(workspace, workspace_bytes, cover ? cw.total : w.total));
     SceneArgs a;
     a.data = data; a.labels = labels;
     a.N = (int)N; a.K = K; a.label_bytes = label_bytes; a.P = num_point; a.min_points = min_points; a.max_blocks = max_blocks;
@@ -3642,7 +3657,9 @@ int conv3p_scene_blocks_f32(const float *data, const void *labels, int64_t N, in
     a.blk_count = reinterpret_cast<int *>(ws); ws += w.blk;
     a.blk_off = reinterpret_cast<int *>(ws); ws += w.blk;
     a.chunk_count = reinterpret_cast<int *>(ws); ws += w.chunk_count;
-    a.members = reinterpret_cast<int *>(ws);
+    a.members = reinterpret_cast<int *>(ws); ws += w.members;
+    a.blk_first = cover ? reinterpret_cast<int *>(ws) : nullptr;                   // past the plain call's workspace
+    a.table = cover ? reinterpret_cast<int4 *>(ws + w.blk) : nullptr;
     a.records_n = w.records; a.chunk_rows = w.chunk_rows; a.chunks = w.chunks;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t items = (size_t)w.blocks * w.chunks;
@@ -3651,12 +3668,40 @@ int conv3p_scene_blocks_f32(const float *data, const void *labels, int64_t N, in
     hipLaunchKernelGGL(scene_bounds_kernel, dim3((unsigned)w.records), dim3(kSceneThreads), 0, s, a);
     hipLaunchKernelGGL(scene_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, a);
     hipLaunchKernelGGL(scene_count_kernel, dim3((unsigned)w.records), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(scene_plan_kernel, dim3(1), dim3(kScenePlanThreads), 0, s, a);
+    if (cover) {
+        hipLaunchKernelGGL(scene_cover_plan_kernel, dim3(1), dim3(kScenePlanThreads), 0, s, a);
+        hipLaunchKernelGGL(scene_cover_table_kernel, dim3(scene_grid((size_t)max_blocks)), dim3(kSceneThreads), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(scene_plan_kernel, dim3(1), dim3(kScenePlanThreads), 0, s, a);
+    }
     hipLaunchKernelGGL(scene_fill_count_kernel, dim3(igrid), dim3(kSceneThreads), 0, s, a);
     hipLaunchKernelGGL(scene_fill_kernel, dim3(igrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(scene_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
+    if (cover)
+        hipLaunchKernelGGL(scene_cover_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(scene_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
     return hip_ok();
 }
+}  // namespace
+
+size_t conv3p_scene_blocks_cover_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride)
+{
+    SceneCoverPlan w;
+    return scene_cover_plan(N, num_point, max_blocks, block, stride, w) ? w.total : 0;
+}
+
+#define SCENE_PARAMS                                                                                                 \
+    const float *data, const void *labels, int64_t N, int K, int label_bytes, float block, float stride,             \
+        int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step, float *blocks_out,              \
+        int32_t *labels_out, int32_t *index_out, int32_t *block_cell, int32_t *block_count, int32_t *stats,          \
+        void *workspace, size_t workspace_bytes, void *stream
+#define SCENE_ARGS                                                                                                   \
+    data, labels, N, K, label_bytes, block, stride, num_point, min_points, max_blocks, seed, step, blocks_out,       \
+        labels_out, index_out, block_cell, block_count, stats, workspace, workspace_bytes, stream
+int conv3p_scene_blocks_f32(SCENE_PARAMS) { return scene_blocks_impl(false, SCENE_ARGS); }
+int conv3p_scene_blocks_cover_f32(SCENE_PARAMS) { return scene_blocks_impl(true, SCENE_ARGS); }
+#undef SCENE_PARAMS
+#undef SCENE_ARGS
 
 int conv3p_scene_vote(const int32_t *pred, const int32_t *index, size_t rows, int64_t N, int num_class, int32_t *votes,
                       void *stream)
@@ -3689,6 +3734,49 @@ int conv3p_scene_vote_labels(const int32_t *votes, int64_t N, int num_class, int
     long long *partial = static_cast<long long *>(workspace);
     hipLaunchKernelGGL(scene_vote_labels_kernel, dim3(grid), dim3(kSceneThreads), 0, s, votes, (long long)N, num_class,
                        label_out, partial);
+    hipLaunchKernelGGL(scene_vote_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, (const long long *)partial, (int)grid,
+                       (long long)N, reinterpret_cast<long long *>(stats));
+    return hip_ok();
+}
+
+// Waves per workgroup of conv3p_scene_vote_scores_f32: four while their tiles fit 48 KB of LDS, then two, then one (128
+// classes: 33.6 KB a wave).
+int conv3p_scene_vote_scores_f32(const float *logits, const int32_t *index, size_t rows, int64_t N, int num_class,
+                                 int64_t *scores, int64_t *stats, void *stream)
+{
+    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (rows == 0 || N == 0) return CONV3P_OK;
+    if (!logits || !index || !scores || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX || num_class > kScoreMaxClass) return CONV3P_ERR_UNSUPPORTED;
+    const int nw = score_lds_bytes(4, num_class) <= 48 * 1024 ? 4 : score_lds_bytes(2, num_class) <= 48 * 1024 ? 2 : 1;
+    const size_t lds = score_lds_bytes(nw, num_class);
+    const size_t tiles = (rows + 63) / 64, wgs = (tiles + nw - 1) / nw;
+    const unsigned grid = (unsigned)(wgs < (size_t)kSceneMaxRecords ? wgs : (size_t)kSceneMaxRecords);
+    hipLaunchKernelGGL(scene_vote_scores_kernel, dim3(grid), dim3(64 * nw), lds, static_cast<hipStream_t>(stream), logits,
+                       index, rows, (long long)N, num_class, reinterpret_cast<long long *>(scores),
+                       reinterpret_cast<long long *>(stats));
+    return hip_ok();
+}
+
+size_t conv3p_scene_score_labels_workspace_bytes(int64_t N, int num_class)
+{
+    if (N <= 0 || N > (int64_t)INT32_MAX || num_class < 1 || num_class > kScoreMaxClass) return 0;
+    return up((size_t)kSceneMaxRecords * sizeof(long long));
+}
+
+int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N == 0) return CONV3P_OK;
+    if (!scores || !label_out || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX || num_class > kScoreMaxClass) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, conv3p_scene_score_labels_workspace_bytes(N, num_class)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned grid = scene_grid((size_t)N);
+    long long *partial = static_cast<long long *>(workspace);
+    hipLaunchKernelGGL(scene_score_labels_kernel, dim3(grid), dim3(kSceneThreads), 0, s,
+                       reinterpret_cast<const long long *>(scores), (long long)N, num_class, label_out, partial);
     hipLaunchKernelGGL(scene_vote_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, (const long long *)partial, (int)grid,
                        (long long)N, reinterpret_cast<long long *>(stats));
     return hip_ok();

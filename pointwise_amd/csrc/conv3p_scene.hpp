@@ -45,6 +45,7 @@ constexpr int kSceneMaxGrid = 65536;        // workgroups of the item loops, at 
 struct SceneHeader {
     float lo[3], lim[3];
     int nbx, nby, ncells, nonfinite, error, nb;
+    int ne;                            // the covering mode's emitted blocks (nb is then its listed cells)
 };
 
 struct SceneArgs {
@@ -65,6 +66,9 @@ struct SceneArgs {
     int *chunk_count;                  // (emitted blocks, chunks)
     int *members;                      // the member lists, block after block
     int records_n, chunk_rows, chunks;
+    // the covering mode only (conv3p_scene_cover.hpp): blk_* are per listed cell there
+    int *blk_first;                    // (listed cells): a cell's first block number
+    int4 *table;                       // (max_blocks): {cell, list start + a_j, n_j, j * P}
 };
 
 __device__ __forceinline__ bool scene_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
@@ -184,6 +188,7 @@ __global__ __launch_bounds__(kSceneMaxRecords) void scene_finish_kernel(const Sc
         h.ncells = h.error ? 0 : (int)cells;
         h.nonfinite = r.bad;
         h.nb = 0;
+        h.ne = 0;
         *p.hdr = h;
         ncells_s = h.ncells;
     }
@@ -412,7 +417,9 @@ __device__ __forceinline__ int32_t scene_label(const SceneArgs &p, size_t idx)
     return (int32_t) static_cast<const long long *>(p.labels)[idx];
 }
 
-__global__ __launch_bounds__(kSceneThreads) void scene_emit_kernel(const SceneArgs p)
+// The emit of both modes.  kCover: block b is part j of its cell, (cell, list start + a_j, n_j, j * P) from the table --
+// n_j <= P members, the draws among them, the counter's first word behind j * P.
+template <bool kCover> __device__ __forceinline__ void scene_emit_body(const SceneArgs &p)
 {
     __shared__ float xyz_s[kSceneThreads * 3], nrm_s[kSceneThreads * 3];
     __shared__ int row_s[kSceneThreads];
@@ -423,7 +430,7 @@ __global__ __launch_bounds__(kSceneThreads) void scene_emit_kernel(const SceneAr
         float *out = p.blocks_out + (size_t)b * P * K3;
         int32_t *idx = p.index_out + (size_t)b * P;
         int32_t *lab = p.labels_out ? p.labels_out + (size_t)b * P : nullptr;
-        if (b >= h.nb) {                                 // the filler
+        if (b >= (kCover ? h.ne : h.nb)) {               // the filler
             for (size_t e = tid; e < (size_t)P * K3; e += kSceneThreads) out[e] = 0.0f;
             for (int t = tid; t < P; t += kSceneThreads) {
                 idx[t] = -1;
@@ -435,8 +442,15 @@ __global__ __launch_bounds__(kSceneThreads) void scene_emit_kernel(const SceneAr
             }
             continue;
         }
-        const int c = p.blk_cell[b], n = p.blk_count[b];
-        const int *list = p.members + p.blk_off[b];
+        int c, n, off;
+        unsigned base = 0;
+        if constexpr (kCover) {
+            const int4 e = p.table[b];
+            c = e.x; off = e.y; n = e.z; base = (unsigned)e.w;
+        } else {
+            c = p.blk_cell[b]; n = p.blk_count[b]; off = p.blk_off[b];
+        }
+        const int *list = p.members + off;
         if (tid == 0) {
             p.block_cell[b] = c;
             p.block_count[b] = n;
@@ -444,8 +458,8 @@ __global__ __launch_bounds__(kSceneThreads) void scene_emit_kernel(const SceneAr
         float mnx = INFINITY, mny = INFINITY;
         for (int t = tid; t < P; t += kSceneThreads) {
             int m = t;
-            if (n > P || t >= n) {
-                const Philox4 w = philox4x32_10((unsigned)t, 0x80000000u | (unsigned)c, p.step_lo, p.step_hi, p.seed_lo,
+            if ((!kCover && n > P) || t >= n) {
+                const Philox4 w = philox4x32_10(base + (unsigned)t, 0x80000000u | (unsigned)c, p.step_lo, p.step_hi, p.seed_lo,
                                                 p.seed_hi);
                 m = (int)(((unsigned long long)w.w[0] * (unsigned long long)n) >> 32);
             }
@@ -498,6 +512,8 @@ __global__ __launch_bounds__(kSceneThreads) void scene_emit_kernel(const SceneAr
         }
     }
 }
+
+__global__ __launch_bounds__(kSceneThreads) void scene_emit_kernel(const SceneArgs p) { scene_emit_body<false>(p); }
 
 // ---------------------------------------------------------------------------------------------- the way back
 __global__ __launch_bounds__(kSceneThreads) void scene_vote_kernel(const int32_t *pred, const int32_t *index, size_t rows,

@@ -1,5 +1,7 @@
 """A room to model-sized blocks and block predictions back to a label per room point (include/conv3p.h:
-conv3p_scene_blocks_f32, conv3p_scene_vote, conv3p_scene_vote_labels; kernels in csrc/conv3p_scene.hpp).
+conv3p_scene_blocks_f32, conv3p_scene_vote, conv3p_scene_vote_labels; kernels in csrc/conv3p_scene.hpp -- and the
+covering mode conv3p_scene_blocks_cover_f32 with the votes by summed probabilities conv3p_scene_vote_scores_f32,
+conv3p_scene_score_labels; kernels in csrc/conv3p_scene_cover.hpp).
 
 The segmentation model takes (B, 4096, 9) blocks (scene_seg/s3dis_provider.py:9, :62-63) and the reference only reads
 blocks that PointNet's indoor3d_util prepared (room2blocks_plus_normalized): shift the room to its minimum, tile x-y
@@ -11,6 +13,12 @@ bit for bit and tests/scene_ref.py restates it in numpy.  The evaluation loops c
     scene_blocks   one room (N, K) -> SceneBlocks: data (max_blocks, P, K + 3), labels, index (the room row of every
                    emitted row), block_cell, block_count, stats
     SceneVotes     votes (N, C) int32 accumulated from (pred, index) pairs -> labels(), counts()
+    SceneScores    scores (N, C) int64, the blocks' class probabilities summed in fixed point from (logits, index)
+                   pairs -> labels(), counts()
+
+For an evaluation, scene_blocks(..., cover=True) splits a crowded cell into parts instead of sampling it, so every row
+of a kept cell is emitted once (and min_points=1 keeps every cell), and SceneScores.add(acts[4], rows) takes the
+model's last activations where SceneVotes.add takes their argmax.
 
 From a room to the model and back:
 
@@ -37,21 +45,26 @@ from .conv3p_op import _call, _require
 _LABEL_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
 
 
-def default_max_blocks(num_rows, block=1.0, stride=1.0, min_points=100):
+def default_max_blocks(num_rows, block=1.0, stride=1.0, min_points=100, num_point=None):
     """The bound scene_blocks uses for max_blocks=None, from the shape alone (no look at the data, no sync): a kept
     cell has at least max(1, min_points) members and a row is a member of at most m x m cells, m = ceil(block /
     stride) + 1, so there are at most num_rows m^2 // max(1, min_points) kept cells -- and never more than
     SCENE_MAX_CELLS.  It is a loose bound (outputs are allocated for it): pass max_blocks when the room's extent is
-    known."""
+    known.  With num_point given it is the covering mode's bound: the sum of ceil(n_c / P) over the kept cells is at
+    most their number plus (the sum of n_c) // P, and the counts sum to at most num_rows m^2."""
     m = int(math.ceil(float(block) / float(stride))) + 1
-    return max(1, min(_lib.SCENE_MAX_CELLS, int(num_rows) * m * m // max(1, int(min_points))))
+    if num_point is None:
+        return max(1, min(_lib.SCENE_MAX_CELLS, int(num_rows) * m * m // max(1, int(min_points))))
+    return max(1, min(_lib.SCENE_MAX_CELLS, int(num_rows) * m * m // max(1, int(min_points)))
+               + int(num_rows) * m * m // int(num_point))
 
 
 class SceneBlocks:
     """The outputs of scene_blocks: data float32 (max_blocks, P, K + 3), points = data[..., 0:3] (a view), labels int32
     (max_blocks, P) or None, index int32 (max_blocks, P), block_cell / block_count int32 (max_blocks), stats int32 (8) =
     {emitted blocks, kept cells, nbx, nby, non-finite rows, cells with 0 < count < min_points, 0, error}.  Blocks past
-    the emitted ones hold data 0, labels -1, index -1, block_cell -1, block_count 0."""
+    the emitted ones hold data 0, labels -1, index -1, block_cell -1, block_count 0.  In the covering mode a block is a
+    part of its cell, block_count its distinct members (the first slots) and stats[6] the blocks the room needs."""
 
     def __init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes=0):
         B, P = int(max_blocks), int(num_point)
@@ -72,6 +85,11 @@ class SceneBlocks:
         """The number of emitted blocks: the one host read (a synchronisation)."""
         return int(self.stats[0])
 
+    def blocks_needed(self):
+        """The covering mode's stats[6], the blocks the room needs (a host read): more than num_blocks() when max_blocks
+        cut the room.  0 from the plain mode."""
+        return int(self.stats[6])
+
     def trim(self):
         """Views of the first num_blocks() blocks, as a SceneBlocks (stats shared)."""
         nb = self.num_blocks()
@@ -89,8 +107,10 @@ def _as_f32(x):
 
 
 def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_points=100, max_blocks=None, seed=0,
-                 step=0, out=None):
-    """One room -> SceneBlocks, by the ten steps of include/conv3p.h (conv3p_scene_blocks_f32).
+                 step=0, out=None, cover=False):
+    """One room -> SceneBlocks, by the ten steps of include/conv3p.h (conv3p_scene_blocks_f32), or with cover=True by
+    the covering mode's (conv3p_scene_blocks_cover_f32: a cell of n > num_point members becomes ceil(n / num_point)
+    blocks that hold each of its rows once; max_blocks=None is then default_max_blocks(..., num_point)).
 
     data float32 (N, K >= 3), xyz first, z up; labels (N) uint8 / int32 / int64 or None.  block and stride are taken
     as float32, block in [stride, 2 stride].  max_blocks=None: default_max_blocks(N, block, stride, min_points), a
@@ -115,8 +135,9 @@ def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_p
     _require(N <= _lib.SCENE_MAX_ROWS, "at most 2^24 room rows")
     _require(K <= 65536, "at most 65536 channels")
     _require(isinstance(min_points, int) and -2 ** 31 <= min_points < 2 ** 31, "min_points must be an int32")
+    _require(isinstance(cover, bool), "cover must be a bool")
     if max_blocks is None:
-        max_blocks = default_max_blocks(N, block, stride, min_points)
+        max_blocks = default_max_blocks(N, block, stride, min_points, num_point if cover else None)
     _require(isinstance(max_blocks, int) and 0 <= max_blocks < 2 ** 31, "max_blocks must be a non-negative integer")
     _require(0 <= int(seed) < 2 ** 64 and 0 <= int(step) < 2 ** 64, "seed and step must fit 64 unsigned bits")
     if out is not None:
@@ -124,7 +145,9 @@ def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_p
                  and out.data.device == dev, "out was made for another shape")
     _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
     lib = _lib.load()
-    need = lib.conv3p_scene_blocks_workspace_bytes(N, num_point, max_blocks, block, stride)
+    nbytes, call = ((lib.conv3p_scene_blocks_cover_workspace_bytes, lib.conv3p_scene_blocks_cover_f32) if cover else
+                    (lib.conv3p_scene_blocks_workspace_bytes, lib.conv3p_scene_blocks_f32))
+    need = nbytes(N, num_point, max_blocks, block, stride)
     if out is None:
         out = SceneBlocks(max_blocks, num_point, K, labels is not None, dev, need)
     elif need and (out.workspace is None or out.workspace.numel() < need):
@@ -140,7 +163,7 @@ def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_p
         return out
     ws = out.workspace
     with torch.cuda.device(dev):
-        _call(lib.conv3p_scene_blocks_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None, N, K,
+        _call(call, data.data_ptr(), labels.data_ptr() if labels is not None else None, N, K,
               _LABEL_DTYPES[labels.dtype] if labels is not None else 0, block, stride, num_point, min_points, max_blocks,
               int(seed), int(step), out.data.data_ptr(), out.labels.data_ptr() if labels is not None else None,
               out.index.data_ptr(), out.block_cell.data_ptr(), out.block_count.data_ptr(), out.stats.data_ptr(),
@@ -191,6 +214,69 @@ class SceneVotes:
             ws = self._workspace
             with torch.cuda.device(self.device):
                 _call(_lib.load().conv3p_scene_vote_labels, self.votes.data_ptr(), self.num_rows, self.num_class,
+                      self._labels.data_ptr(), self._counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                      torch.cuda.current_stream(self.device).cuda_stream)
+            self._fresh = True
+        return self._labels
+
+    def counts(self):
+        self.labels()
+        return self._counts
+
+
+class SceneScores:
+    """Summed class probabilities of block predictions for the rows of one room: scores int64 (num_rows, num_class) on
+    the device, in fixed point -- a vote adds llrintf(softmax(logits)[c] * SCALE) to its room row's class c, so the
+    sums are exact and do not depend on the order of the rows or of the calls.
+
+    add(logits, index): logits float32 (..., num_class), the model's last activations; index int32 with as many rows.
+    A row with 0 <= index < num_rows and finite logits votes; vote_stats int64 (2) accumulates {rows that voted, rows
+    with a valid index refused for a non-finite logit}.  Scores accumulate over calls until reset().  labels() ->
+    (num_rows) int32, the class with the largest score, the lowest on a tie, -1 where no row voted; counts() -> int64
+    device tensor {voted rows, unvoted rows} of the last labels() (computed if there was none).  scores / SCALE is the
+    sum of the probabilities."""
+
+    SCALE = 1 << 30
+
+    def __init__(self, num_rows, num_class, device="cuda:0"):
+        _require(isinstance(num_rows, int) and 0 <= num_rows < 2 ** 31, "num_rows must be an integer in [0, 2^31)")
+        _require(isinstance(num_class, int) and 1 <= num_class <= 128, "num_class must be an integer in [1, 128]")
+        self.device = torch.device(device)
+        _require(self.device.type == "cuda", "scores live on a HIP device (there is no CPU path)")
+        self.num_rows, self.num_class = num_rows, num_class
+        self.scores = torch.zeros((num_rows, num_class), dtype=torch.int64, device=self.device)
+        self.vote_stats = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        self._labels = torch.empty((num_rows,), dtype=torch.int32, device=self.device)
+        self._counts = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        nbytes = _lib.load().conv3p_scene_score_labels_workspace_bytes(num_rows, num_class)
+        self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if nbytes else None
+        self._fresh = False
+
+    def reset(self):
+        self.scores.zero_()
+        self.vote_stats.zero_()
+        self._fresh = False
+
+    def add(self, logits, index):
+        _require(isinstance(logits, torch.Tensor) and logits.dtype == torch.float32 and logits.device == self.device
+                 and logits.is_contiguous() and logits.dim() >= 1 and logits.shape[-1] == self.num_class,
+                 "logits must be a contiguous float32 (..., num_class) tensor on the scores' device")
+        _require(isinstance(index, torch.Tensor) and index.dtype == torch.int32 and index.device == self.device
+                 and index.is_contiguous(), "index must be a contiguous int32 tensor on the scores' device")
+        _require(logits.numel() == index.numel() * self.num_class, "logits and index must have as many rows")
+        self._fresh = False
+        if index.numel() == 0 or self.num_rows == 0:
+            return
+        with torch.cuda.device(self.device):
+            _call(_lib.load().conv3p_scene_vote_scores_f32, logits.data_ptr(), index.data_ptr(), index.numel(),
+                  self.num_rows, self.num_class, self.scores.data_ptr(), self.vote_stats.data_ptr(),
+                  torch.cuda.current_stream(self.device).cuda_stream)
+
+    def labels(self):
+        if self.num_rows and not self._fresh:
+            ws = self._workspace
+            with torch.cuda.device(self.device):
+                _call(_lib.load().conv3p_scene_score_labels, self.scores.data_ptr(), self.num_rows, self.num_class,
                       self._labels.data_ptr(), self._counts.data_ptr(), ws.data_ptr(), ws.numel(),
                       torch.cuda.current_stream(self.device).cuda_stream)
             self._fresh = True
