@@ -562,6 +562,49 @@ int conv3p_provider_batch_wide_f32(const float *data, const void *labels, int S,
  *   tie, -1 where all scores are 0; stats = int64 {voted rows, unvoted rows}.  Status as conv3p_scene_vote_labels
  *   (num_class > 128: CONV3P_ERR_UNSUPPORTED), then CONV3P_ERR_WORKSPACE against
  *   conv3p_scene_score_labels_workspace_bytes.  Two launches.
+ *
+ * conv3p_scene_blocks_rooms_f32:  MANY ROOMS in one call (pointwise_amd/csrc/conv3p_scene_rooms.hpp;
+ *   tests/scene_rooms_ref.py restates it on the single-room references).  data (N, K) holds the rooms' rows one room
+ *   after the other; room_start, int32 (R + 1) ON THE DEVICE, gives room r the rows [room_start[r], room_start[r+1]).
+ *   Rows before room_start[0] or from room_start[R] on belong to no room.  cover = 0 / 1 selects the plain or the
+ *   covering mode.  The result is the concatenation of the single-room calls:
+ *    a. Room r is tiled as by conv3p_scene_blocks_f32 (cover = 0) or conv3p_scene_blocks_cover_f32 (cover = 1) run on
+ *       the room's own rows with the same num_point, block, stride, min_points and step, and the Philox key
+ *       (seed + r) mod 2^64.  Every step above holds per room; lo, lim, nbx, nby are the room's own.  The minimum of
+ *       step 2 takes -0.0 as below +0.0 (IEEE 754-2019 minimum, the device's min instruction), in this call as in the
+ *       single-room ones, so lo does not depend on the order of the reduction.
+ *    b. Blocks are numbered room after room, within a room as the single call numbers them; first_r = the blocks the
+ *       rooms before r need (kept cells; covering: parts).  Blocks numbered >= max_blocks are not emitted: room r
+ *       behaves as its single call with max_blocks_r = max(0, max_blocks - first_r).  Blocks past the emitted ones get
+ *       step 9's filler and block_room -1.
+ *    c. index_out holds the GLOBAL row, room_start[r] + the room row; labels is (N), indexed by global row.  block_cell
+ *       is the cell id within the room, block_room (max_blocks) the room.
+ *    d. room_blocks int32 (R + 1): the prefix of the emitted blocks per room, room_blocks[R] = stats[0].
+ *       room_stats int32 (R, 8): the eight words the single call would write for room r with max_blocks_r -- words 1-7
+ *       also when max_blocks_r = 0 (word 0 is then 0); an empty room gives eight zeros.
+ *       stats int32 (8) = {emitted blocks, kept cells over all rooms, R, total cells (the sum of nbx nby over the rooms
+ *       without an error of their own, held at 2^31 - 1), non-finite rows, small cells, the blocks all rooms need
+ *       (covering; 0 plain), error bits}.
+ *    e. Errors known on the device only, stats[7]:  bit 0: some room's own tiling has more than CONV3P_SCENE_MAX_CELLS
+ *       cells; that room emits nothing and has room_stats[r][7] = 1, the others are unaffected.  bit 1: room_start is
+ *       malformed (room_start[0] < 0, a decrease, room_start[R] > N, a room of more than 2^24 rows): nothing is read
+ *       through it, nothing is emitted, room_blocks and room_stats are all 0.  bit 2: more than
+ *       CONV3P_SCENE_ROOMS_MAX_CELLS cells summed over the rooms without an error of their own: nothing is emitted,
+ *       room_blocks is all 0, room_stats keeps words 2, 3, 4 and 7 and has 0 elsewhere.  bit 3: the rows have more
+ *       member pairs than N (ceil(block / stride) + 1)^2, which the comparisons of step 4 do not allow -- an internal
+ *       error, reported rather than hidden: the pairs past the bound are dropped and the result is not to be used.
+ *   Status, in the single call's order: N < 0, R < 0, K < 3, num_point < 1, max_blocks < 0, cover not 0 / 1, block or
+ *   stride not finite or <= 0, labels without labels_out or the reverse, label_bytes not 1 / 4 / 8:
+ *   CONV3P_ERR_INVALID_ARGUMENT; R == 0, N == 0 or max_blocks == 0: CONV3P_OK, nothing launched, nothing written; a
+ *   NULL data, room_start or output: CONV3P_ERR_INVALID_ARGUMENT; N > 2^26 (the member pairs, at most 9 a row, stay
+ *   inside 31 bits), R > 65536, num_point > 65536, K > 65536 or block outside [stride, 2 stride]:
+ *   CONV3P_ERR_UNSUPPORTED; then CONV3P_ERR_WORKSPACE against conv3p_scene_blocks_rooms_workspace_bytes, a host-side
+ *   bound from its arguments (dominated by two buffers of N (ceil(block / stride) + 1)^2 pairs of 8 bytes: up to 144
+ *   bytes a row), a multiple of 256, 0 for arguments the call refuses or does nothing for; never a data-dependent
+ *   failure.  The workspace need not be initialised and nothing is kept in it.  The member lists are built by a stable
+ *   radix sort of (cell, row) pairs: work proportional to the pairs, not to cells x rows, and no limit on a list's
+ *   length.  21 launches whatever R, the cells and the blocks; no float atomics; every output word is written once by a
+ *   plain store; bitwise reproducible and independent of the launch geometry.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_SCENE_MAX_CELLS 65536
 size_t conv3p_scene_blocks_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride);
@@ -580,6 +623,15 @@ int conv3p_scene_blocks_cover_f32(const float *data, const void *labels, int64_t
                                   uint64_t step, float *blocks_out, int32_t *labels_out, int32_t *index_out,
                                   int32_t *block_cell, int32_t *block_count, int32_t *stats, void *workspace,
                                   size_t workspace_bytes, void *stream);
+#define CONV3P_SCENE_ROOMS_MAX_CELLS 1048576
+size_t conv3p_scene_blocks_rooms_workspace_bytes(int64_t N, int64_t R, int num_point, int max_blocks, float block,
+                                                 float stride, int cover);
+int conv3p_scene_blocks_rooms_f32(const float *data, const void *labels, const int32_t *room_start, int64_t N, int64_t R,
+                                  int K, int label_bytes, float block, float stride, int num_point, int min_points,
+                                  int max_blocks, int cover, uint64_t seed, uint64_t step, float *blocks_out,
+                                  int32_t *labels_out, int32_t *index_out, int32_t *block_cell, int32_t *block_count,
+                                  int32_t *block_room, int32_t *room_blocks, int32_t *room_stats, int32_t *stats,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 int conv3p_scene_vote_scores_f32(const float *logits, const int32_t *index, size_t rows, int64_t N, int num_class,
                                  int64_t *scores, int64_t *stats, void *stream);
 size_t conv3p_scene_score_labels_workspace_bytes(int64_t N, int num_class);

@@ -11,8 +11,9 @@ from .conv3p_op import (Conv3pFunction, Conv3pInvalidArgument, Conv3pRuntimeErro
                         conv3p_grad, conv3p_layer, conv3p_layer_grad, neighbor_count, selu, selu_grad)
 from .optim import MomentumOptimizer, exponential_decay, momentum_step
 from .provider import BatchBuffers, BatchProvider, assemble_batch
-from .scene import SceneBlocks, SceneScores, SceneVotes, default_max_blocks, scene_blocks
+from .scene import (SceneBlocks, SceneRoomBlocks, SceneScores, SceneVotes, default_max_blocks, default_max_blocks_rooms,
+                    scene_blocks, scene_blocks_rooms)
 from .seg_head import SegmentationHead, class_weights_from_counts
 
-__all__ = ["scene_blocks", "SceneBlocks", "SceneVotes", "SceneScores", "default_max_blocks","BatchProvider", "BatchBuffers", "assemble_batch", "SegmentationHead", "class_weights_from_counts", "MomentumOptimizer", "exponential_decay", "momentum_step", "conv3p", "conv3p_grad", "conv3p_layer", "conv3p_layer_grad", "conv3p_autograd", "Conv3pFunction", "neighbor_count", "selu", "selu_grad",
+__all__ = ["scene_blocks", "scene_blocks_rooms", "SceneRoomBlocks", "default_max_blocks_rooms", "SceneBlocks", "SceneVotes", "SceneScores", "default_max_blocks","BatchProvider", "BatchBuffers", "assemble_batch", "SegmentationHead", "class_weights_from_counts", "MomentumOptimizer", "exponential_decay", "momentum_step", "conv3p", "conv3p_grad", "conv3p_layer", "conv3p_layer_grad", "conv3p_autograd", "Conv3pFunction", "neighbor_count", "selu", "selu_grad",
            "Conv3pInvalidArgument", "Conv3pRuntimeError"]

@@ -36,6 +36,9 @@ WIDE_SORT_MAX_POINTS = 65536      # its limit, and conv3p_provider_batch_wide_f3
 SCENE_MAX_CELLS = 65536           # CONV3P_SCENE_MAX_CELLS
 SCENE_MAX_ROWS = 1 << 24          # conv3p_scene_blocks_f32's limits: room rows, rows of a block
 SCENE_MAX_NUM_POINT = 65536
+SCENE_ROOMS_MAX_CELLS = 1 << 20    # CONV3P_SCENE_ROOMS_MAX_CELLS; conv3p_scene_blocks_rooms_f32's limits: rooms, rows
+SCENE_ROOMS_MAX_ROOMS = 65536
+SCENE_ROOMS_MAX_ROWS = 1 << 26
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -129,6 +132,11 @@ SYMBOLS = {
     "conv3p_scene_blocks_cover_workspace_bytes": (_sz, [ctypes.c_int64, _i, _i, ctypes.c_float, ctypes.c_float]),
     "conv3p_scene_blocks_cover_f32": (_i, [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_float, ctypes.c_float, _i, _i, _i,
                                            ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_scene_blocks_rooms_workspace_bytes": (_sz, [ctypes.c_int64, ctypes.c_int64, _i, _i, ctypes.c_float,
+                                                        ctypes.c_float, _i]),
+    "conv3p_scene_blocks_rooms_f32": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, ctypes.c_float,
+                                           ctypes.c_float, _i, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_scene_vote_scores_f32": (_i, [_vp, _vp, _sz, ctypes.c_int64, _i, _vp, _vp, _vp]),
     "conv3p_scene_score_labels_workspace_bytes": (_sz, [ctypes.c_int64, _i]),
     "conv3p_scene_score_labels": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _sz, _vp]),

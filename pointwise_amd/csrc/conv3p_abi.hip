@@ -27,6 +27,7 @@
 #include "conv3p_sort_wide.hpp"
 #include "conv3p_scene.hpp"
 #include "conv3p_scene_cover.hpp"
+#include "conv3p_scene_rooms.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3702,6 +3703,131 @@ int conv3p_scene_blocks_f32(SCENE_PARAMS) { return scene_blocks_impl(false, SCEN
 int conv3p_scene_blocks_cover_f32(SCENE_PARAMS) { return scene_blocks_impl(true, SCENE_ARGS); }
 #undef SCENE_PARAMS
 #undef SCENE_ARGS
+
+namespace {
+// The workspace of conv3p_scene_blocks_rooms_f32 (conv3p_scene_rooms.hpp): a host-side upper bound from the arguments.
+// The two pair buffers dominate it: N * m^2 pairs of 8 bytes each, m = ceil(block / stride) + 1 the cells a row can be
+// in along an axis -- at m = 3 that is 144 bytes a row.
+struct RoomsPlan {
+    int row_tiles, listed_max, pairs_max, sort_tiles;
+    size_t hdr, room, base, pref, rec, tile, seg, blk, table, blk_room, hist, pairs, total;
+};
+bool rooms_plan(int64_t N, int64_t R, int num_point, int max_blocks, float block, float stride, RoomsPlan &w)
+{
+    if (N <= 0 || N > kRoomsMaxN || R <= 0 || R > kRoomsMaxRooms || num_point < 1 || num_point > kSceneMaxP || max_blocks <= 0)
+        return false;
+    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return false;
+    if (block < stride || block > 2.0f * stride) return false;
+    const size_t m = (size_t)std::ceil((double)block / (double)stride) + 1;
+    w.row_tiles = (int)((N + kRoomsRowTile - 1) / kRoomsRowTile);
+    w.listed_max = max_blocks < kRoomsMaxCells ? max_blocks : kRoomsMaxCells;
+    w.pairs_max = (int)((size_t)N * m * m);                                          // <= 9 * 2^26 < 2^31
+    w.sort_tiles = (w.pairs_max + kRoomsSortTile - 1) / kRoomsSortTile;
+    w.hdr = up(sizeof(RoomsHeader));
+    w.room = up((size_t)R * sizeof(RoomFrame));
+    w.base = up((size_t)(R + 1) * sizeof(int));
+    w.pref = up((size_t)(R + 1) * sizeof(int4));
+    w.rec = up(((size_t)w.row_tiles + (size_t)R) * 8 * sizeof(float));
+    w.tile = up((size_t)w.row_tiles * sizeof(int));
+    w.seg = up((size_t)kRoomsMaxCells * sizeof(int));
+    w.blk = up((size_t)w.listed_max * sizeof(int));
+    w.table = up((size_t)max_blocks * sizeof(int4));
+    w.blk_room = up((size_t)max_blocks * sizeof(int));
+    w.hist = up((size_t)w.sort_tiles * kRoomsDigits * sizeof(int));
+    w.pairs = up((size_t)w.pairs_max * sizeof(unsigned long long));
+    w.total = w.hdr + w.room + w.base + w.pref + w.rec + w.tile + 2 * w.seg + 4 * w.blk + w.table + w.blk_room + w.hist +
+              2 * w.pairs;
+    return true;
+}
+}  // namespace
+
+size_t conv3p_scene_blocks_rooms_workspace_bytes(int64_t N, int64_t R, int num_point, int max_blocks, float block,
+                                                 float stride, int cover)
+{
+    RoomsPlan w;
+    if (cover != 0 && cover != 1) return 0;
+    return rooms_plan(N, R, num_point, max_blocks, block, stride, w) ? w.total : 0;
+}
+
+// Every status first, in the order include/conv3p.h gives; then the launches, their number fixed, outside the profile
+// bracket as scene_blocks_impl's.
+int conv3p_scene_blocks_rooms_f32(const float *data, const void *labels, const int32_t *room_start, int64_t N, int64_t R,
+                                  int K, int label_bytes, float block, float stride, int num_point, int min_points,
+                                  int max_blocks, int cover, uint64_t seed, uint64_t step, float *blocks_out,
+                                  int32_t *labels_out, int32_t *index_out, int32_t *block_cell, int32_t *block_count,
+                                  int32_t *block_room, int32_t *room_blocks, int32_t *room_stats, int32_t *stats,
+                                  void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || R < 0 || K < 3 || num_point < 1 || max_blocks < 0 || (cover != 0 && cover != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (R == 0 || N == 0 || max_blocks == 0) return CONV3P_OK;
+    if (!data || !room_start || !blocks_out || !index_out || !block_cell || !block_count || !block_room || !room_blocks ||
+        !room_stats || !stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > kRoomsMaxN || R > kRoomsMaxRooms || num_point > kSceneMaxP || K > 65536 || block < stride || block > 2.0f * stride)
+        return CONV3P_ERR_UNSUPPORTED;
+    RoomsPlan w;
+    if (!rooms_plan(N, R, num_point, max_blocks, block, stride, w)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, w.total));
+    RoomsArgs a;
+    a.data = data; a.labels = labels; a.room_start = room_start;
+    a.N = (int)N; a.R = (int)R; a.K = K; a.label_bytes = label_bytes; a.P = num_point; a.min_points = min_points;
+    a.max_blocks = max_blocks; a.cover = cover;
+    a.block = block; a.stride = stride;
+    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
+    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
+    a.blocks_out = blocks_out; a.labels_out = labels_out; a.index_out = index_out;
+    a.block_cell = block_cell; a.block_count = block_count; a.block_room = block_room;
+    a.room_blocks = room_blocks; a.room_stats = room_stats; a.stats = stats;
+    char *ws = static_cast<char *>(workspace);
+    a.hdr = reinterpret_cast<RoomsHeader *>(ws); ws += w.hdr;
+    a.room = reinterpret_cast<RoomFrame *>(ws); ws += w.room;
+    a.cell_base = reinterpret_cast<int *>(ws); ws += w.base;
+    a.room_pref = reinterpret_cast<int4 *>(ws); ws += w.pref;
+    a.records = reinterpret_cast<float *>(ws); ws += w.rec;
+    a.tile_pairs = reinterpret_cast<int *>(ws); ws += w.tile;
+    a.seg_start = reinterpret_cast<int *>(ws); ws += w.seg;
+    a.seg_end = reinterpret_cast<int *>(ws); ws += w.seg;
+    a.blk_cell = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.blk_count = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.blk_off = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.blk_first = reinterpret_cast<int *>(ws); ws += w.blk;
+    a.table = reinterpret_cast<int4 *>(ws); ws += w.table;
+    a.blk_room = reinterpret_cast<int *>(ws); ws += w.blk_room;
+    a.hist = reinterpret_cast<int *>(ws); ws += w.hist;
+    a.pairs_a = reinterpret_cast<unsigned long long *>(ws); ws += w.pairs;
+    a.pairs_b = reinterpret_cast<unsigned long long *>(ws);
+    a.row_tiles = w.row_tiles; a.listed_max = w.listed_max; a.pairs_max = w.pairs_max;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned rgrid = (unsigned)(R < kSceneMaxRecords ? R : kSceneMaxRecords);
+    const unsigned sgrid = (unsigned)(w.sort_tiles < kSceneMaxGrid ? w.sort_tiles : kSceneMaxGrid);
+    const unsigned egrid = (unsigned)(max_blocks < kSceneMaxGrid ? max_blocks : kSceneMaxGrid);
+    hipLaunchKernelGGL(rooms_check_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_bounds_kernel, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_finish_kernel, dim3(rgrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_base_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_pairs_kernel<false>, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_tile_scan_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_pairs_kernel<true>, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
+    unsigned long long *src = a.pairs_a, *dst = a.pairs_b;
+    for (int pass = 0; pass < kRoomsPasses; ++pass) {
+        const int shift = pass * kRoomsDigitBits;
+        hipLaunchKernelGGL(rooms_sort_hist_kernel, dim3(sgrid), dim3(kSceneThreads), 0, s, a, (const unsigned long long *)src, shift);
+        hipLaunchKernelGGL(rooms_sort_scan_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
+        hipLaunchKernelGGL(rooms_sort_scatter_kernel, dim3(sgrid), dim3(64), 0, s, a, (const unsigned long long *)src, dst, shift);
+        std::swap(src, dst);
+    }
+    // an odd number of passes: the sorted pairs are in pairs_b (= src after the last swap), where the emit reads them
+    hipLaunchKernelGGL(rooms_segments_kernel, dim3(scene_grid((size_t)w.pairs_max)), dim3(kSceneThreads), 0, s, a,
+                       (const unsigned long long *)src);
+    hipLaunchKernelGGL(rooms_plan_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_table_kernel, dim3(scene_grid((size_t)max_blocks)), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_stats_kernel, dim3(scene_grid((size_t)R + 1)), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(rooms_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
+    return hip_ok();
+}
 
 int conv3p_scene_vote(const int32_t *pred, const int32_t *index, size_t rows, int64_t N, int num_class, int32_t *votes,
                       void *stream)

@@ -12,6 +12,8 @@ bit for bit and tests/scene_ref.py restates it in numpy.  The evaluation loops c
 
     scene_blocks   one room (N, K) -> SceneBlocks: data (max_blocks, P, K + 3), labels, index (the room row of every
                    emitted row), block_cell, block_count, stats
+    scene_blocks_rooms   many rooms (an area, a test split) in ONE call -> SceneRoomBlocks: the concatenation of the
+                   single-room results, index holding GLOBAL rows, plus block_room, room_blocks, room_stats
     SceneVotes     votes (N, C) int32 accumulated from (pred, index) pairs -> labels(), counts()
     SceneScores    scores (N, C) int64, the blocks' class probabilities summed in fixed point from (logits, index)
                    pairs -> labels(), counts()
@@ -29,6 +31,16 @@ From a room to the model and back:
                 pred = model(points, inp).argmax(-1)                  # e.g. SegmentationHead.evaluate(...)[0]
                 votes.add(pred, rows)
     labels = votes.labels()                                          # (N) int32, -1 where no block covered the row
+
+Many rooms at once -- an S3DIS area, SceneNN's test split -- with rows (N, K) the rooms one after the other and
+room_start their R + 1 boundaries; one call, one host read, no torch.cat, and one vote table over the N global rows:
+
+    sb = scene_blocks_rooms(rows, room_start, num_point=4096, stride=0.5, min_points=1, cover=True).trim()
+    pv = BatchProvider(sb.data, sb.index, batch_size, training=False, sort_cloud=True)
+    scores = SceneScores(rows.shape[0], num_class, rows.device)
+    per batch:  points, inp, idx = pv.get_batch_point_cloud();  scores.add(model(points, inp), idx)
+    labels = scores.labels()                                         # (N) int32 over the global rows of all rooms
+    conv3p_seg_confusion over (row_labels, labels): one confusion matrix of the N rows of all rooms
 
 The trimmed data / labels are what BatchProvider(data, labels, ...) takes for training; passing `index` as its
 per-point int32 "labels" instead carries the room rows through the provider's sort.  A room resampled with another
@@ -168,6 +180,171 @@ def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_p
               int(seed), int(step), out.data.data_ptr(), out.labels.data_ptr() if labels is not None else None,
               out.index.data_ptr(), out.block_cell.data_ptr(), out.block_count.data_ptr(), out.stats.data_ptr(),
               ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+class SceneRoomBlocks(SceneBlocks):
+    """The outputs of scene_blocks_rooms: SceneBlocks' fields over the blocks of all rooms, room after room -- index
+    holds GLOBAL rows, block_cell the cell within the block's room -- plus block_room int32 (max_blocks) (-1 past the
+    emitted blocks), room_blocks int32 (R + 1), the prefix of the emitted blocks per room, room_stats int32 (R, 8), the
+    single-room stats of every room, and room_start, the device tensor the call used.  stats int32 (8) = {emitted
+    blocks, kept cells, R, total cells, non-finite rows, small cells, blocks needed (covering), error bits: 1 a room of
+    too many cells, 2 room_start malformed, 4 too many cells in all, 8 an internal error (more member pairs than the
+    workspace bound: the result is not to be used)}."""
+
+    def __init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes=0, num_rooms=0):
+        SceneBlocks.__init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes)
+        R = int(num_rooms)
+        self.shape = self.shape + (R,)
+        self.block_room = torch.empty((int(max_blocks),), dtype=torch.int32, device=device)
+        self.room_blocks = torch.zeros((R + 1,), dtype=torch.int32, device=device)
+        self.room_stats = torch.zeros((R, 8), dtype=torch.int32, device=device)
+        self.room_start = None
+        self._room_blocks_host = None
+
+    def trim(self):
+        """Views of the first num_blocks() blocks, as a SceneRoomBlocks (stats and the per-room tensors shared)."""
+        nb = self.num_blocks()
+        t = object.__new__(SceneRoomBlocks)
+        t.shape = (nb,) + self.shape[1:]
+        t.data, t.index = self.data[:nb], self.index[:nb]
+        t.labels = self.labels[:nb] if self.labels is not None else None
+        t.block_cell, t.block_count, t.block_room = self.block_cell[:nb], self.block_count[:nb], self.block_room[:nb]
+        t.room_blocks, t.room_stats, t.room_start = self.room_blocks, self.room_stats, self.room_start
+        t.stats, t.workspace, t._room_blocks_host = self.stats, None, self._room_blocks_host
+        return t
+
+    def room(self, r):
+        """Views of room r's blocks, as a SceneBlocks whose stats is room_stats[r]; index stays global.  The first call
+        reads room_blocks to the host (a synchronisation), later ones reuse it."""
+        R = self.shape[4]
+        _require(isinstance(r, int) and 0 <= r < R, "room must be an integer in [0, %d)" % R)
+        if self._room_blocks_host is None:
+            self._room_blocks_host = self.room_blocks.tolist()
+        b0, b1 = self._room_blocks_host[r], self._room_blocks_host[r + 1]
+        t = object.__new__(SceneBlocks)
+        t.shape = (b1 - b0,) + self.shape[1:4]
+        t.data, t.index = self.data[b0:b1], self.index[b0:b1]
+        t.labels = self.labels[b0:b1] if self.labels is not None else None
+        t.block_cell, t.block_count = self.block_cell[b0:b1], self.block_count[b0:b1]
+        t.stats, t.workspace = self.room_stats[r], None
+        return t
+
+
+def default_max_blocks_rooms(room_rows, block=1.0, stride=1.0, min_points=100, num_point=None):
+    """default_max_blocks summed over rooms of room_rows[r] rows each: what scene_blocks_rooms uses for max_blocks=None
+    when the host knows room_start."""
+    return max(1, sum(default_max_blocks(n, block, stride, min_points, num_point) for n in room_rows if n > 0))
+
+
+def _rooms_bound(N, R, block, stride, min_points, num_point):
+    """The bound from N and R alone, for a room_start only the device knows: the sum over the rooms of min(65536, n_r m^2
+    // need) is at most min(R 65536, N m^2 // need) -- default_max_blocks(N, ...) with its min(65536, .) applied R times
+    over -- and the covering mode's sum of n_r m^2 // P is at most N m^2 // P; each room's max(1, .) adds at most R."""
+    m = int(math.ceil(float(block) / float(stride))) + 1
+    kept = min(R * _lib.SCENE_MAX_CELLS, N * m * m // max(1, int(min_points)))
+    return max(1, R + kept + (N * m * m // int(num_point) if num_point is not None else 0))
+
+
+def scene_blocks_rooms(data, room_start, labels=None, num_point=4096, block=1.0, stride=1.0, min_points=100,
+                       max_blocks=None, seed=0, step=0, out=None, cover=False):
+    """Many rooms -> SceneRoomBlocks in one call (conv3p_scene_blocks_rooms_f32): the concatenation of scene_blocks(room
+    r's rows, ..., seed=seed + r, cover=cover) over the rooms, cut at max_blocks, index holding global rows.
+
+    data float32 (N, K >= 3), the rooms' rows one room after the other; labels (N) or None.  room_start: the R + 1
+    boundaries.  A device int32 tensor is used as is (a malformed one is reported in stats[7], bit 1); a Python
+    sequence, numpy array or CPU tensor is checked here (ascending, inside [0, N], rooms of at most 2^24 rows) and copied
+    once.  max_blocks=None: default_max_blocks summed per room when the host knows room_start, otherwise a bound from N
+    and R alone; neither synchronises.  That second bound is very loose -- R + min(65536 R, N m^2 // min_points) + N m^2
+    // num_point blocks, and the outputs are allocated for it: 4 M rows at stride 0.5 ask for tens of GB -- so a caller
+    with a device room_start should pass max_blocks (from the rooms' extents, or from a first call with max_blocks=1
+    and blocks_needed()).  The other arguments are scene_blocks'.  Nothing is synchronised on."""
+    _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
+             "data must be a float32 (N, K >= 3) tensor, xyz first")
+    dev = data.device
+    N, K = data.shape
+    _require(data.is_contiguous(), "data must be contiguous")
+    host_rooms = None
+    if isinstance(room_start, torch.Tensor) and room_start.device.type != "cpu":
+        _require(room_start.dtype == torch.int32 and room_start.dim() == 1 and room_start.numel() >= 1
+                 and room_start.is_contiguous() and room_start.device == dev,
+                 "a device room_start must be a contiguous int32 (R + 1,) tensor on the data's device")
+        R = room_start.numel() - 1
+    else:
+        if isinstance(room_start, torch.Tensor):
+            _require(room_start.dtype in (torch.int32, torch.int64), "room_start must hold integers (int32 or int64)")
+            rs = room_start.numpy()
+        else:
+            try:
+                rs = np.asarray(room_start)
+            except Exception:
+                rs = None
+            _require(rs is not None and rs.dtype.kind in "iu", "room_start must hold integers")
+        _require(rs.ndim == 1 and rs.size >= 1, "room_start must have R + 1 >= 1 entries")
+        rs = rs.astype(np.int64)
+        _require(int(rs[0]) >= 0 and int(rs[-1]) <= N and bool(np.all(np.diff(rs) >= 0)),
+                 "room_start must ascend inside [0, N]")
+        _require(rs.size < 2 or int(np.diff(rs).max()) <= _lib.SCENE_MAX_ROWS, "at most 2^24 rows a room")
+        host_rooms = np.diff(rs).tolist()
+        R = rs.size - 1
+    _require(R <= _lib.SCENE_ROOMS_MAX_ROOMS, "at most 65536 rooms")
+    if labels is not None:
+        _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
+        _require(labels.device == dev and tuple(labels.shape) == (N,) and labels.is_contiguous(),
+                 "labels must be a contiguous (N,) tensor on the data's device")
+    _require(isinstance(num_point, int) and 1 <= num_point <= _lib.SCENE_MAX_NUM_POINT,
+             "num_point must be an integer in [1, %d]" % _lib.SCENE_MAX_NUM_POINT)
+    for name, v in (("block", block), ("stride", stride)):
+        _require(isinstance(v, (int, float)) and math.isfinite(v) and _as_f32(v) > 0, "%s must be finite and positive" % name)
+    block, stride = _as_f32(block), _as_f32(stride)
+    _require(stride <= block <= _as_f32(np.float32(2) * np.float32(stride)), "block must lie in [stride, 2 stride]")
+    _require(N <= _lib.SCENE_ROOMS_MAX_ROWS, "at most 2^26 rows")
+    _require(K <= 65536, "at most 65536 channels")
+    _require(isinstance(min_points, int) and -2 ** 31 <= min_points < 2 ** 31, "min_points must be an int32")
+    _require(isinstance(cover, bool), "cover must be a bool")
+    if max_blocks is None:
+        if host_rooms is not None:
+            max_blocks = default_max_blocks_rooms(host_rooms, block, stride, min_points, num_point if cover else None)
+        else:
+            max_blocks = _rooms_bound(N, R, block, stride, min_points, num_point if cover else None)
+    _require(isinstance(max_blocks, int) and 0 <= max_blocks < 2 ** 31, "max_blocks must be a non-negative integer")
+    _require(0 <= int(seed) < 2 ** 64 and 0 <= int(step) < 2 ** 64, "seed and step must fit 64 unsigned bits")
+    if out is not None:
+        _require(isinstance(out, SceneRoomBlocks) and out.shape == (max_blocks, num_point, K, labels is not None, R)
+                 and out.data.device == dev, "out was made for another shape")
+    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
+    lib = _lib.load()
+    need = lib.conv3p_scene_blocks_rooms_workspace_bytes(N, R, num_point, max_blocks, block, stride, int(cover))
+    if out is None:
+        out = SceneRoomBlocks(max_blocks, num_point, K, labels is not None, dev, need, R)
+    elif need and (out.workspace is None or out.workspace.numel() < need):
+        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    out._room_blocks_host = None
+    if host_rooms is not None:
+        out.room_start = torch.from_numpy(rs.astype(np.int32)).to(dev)
+    else:
+        out.room_start = room_start
+    if R == 0 or N == 0 or max_blocks == 0:  # nothing is launched, so nothing is written
+        out.data.zero_()
+        out.index.fill_(-1)
+        out.block_cell.fill_(-1)
+        out.block_count.zero_()
+        out.block_room.fill_(-1)
+        out.room_blocks.zero_()
+        out.room_stats.zero_()
+        out.stats.zero_()
+        if out.labels is not None:
+            out.labels.fill_(-1)
+        return out
+    ws = out.workspace
+    with torch.cuda.device(dev):
+        _call(lib.conv3p_scene_blocks_rooms_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None,
+              out.room_start.data_ptr(), N, R, K, _LABEL_DTYPES[labels.dtype] if labels is not None else 0, block, stride,
+              num_point, min_points, max_blocks, int(cover), int(seed), int(step), out.data.data_ptr(),
+              out.labels.data_ptr() if labels is not None else None, out.index.data_ptr(), out.block_cell.data_ptr(),
+              out.block_count.data_ptr(), out.block_room.data_ptr(), out.room_blocks.data_ptr(),
+              out.room_stats.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
+              torch.cuda.current_stream(dev).cuda_stream)
     return out
 
 
