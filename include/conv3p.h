@@ -639,6 +639,69 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Voxel-grid subsampling of a cloud, and voxel labels projected back to its rows
+ * (pointwise_amd/csrc/conv3p_grid.hpp; tests/grid_ref.py restates it in numpy).  The step in front of the scene calls:
+ * a raw room or scan is thinned to one row per occupied voxel, the model runs on those rows, and every raw row gets its
+ * voxel's prediction.  One cloud per call; rows are float32, xyz first.  Additions: nothing above changes.
+ *
+ * conv3p_grid_subsample_f32:  data (N, K), K >= 3; labels (N) of label_bytes = 1 / 4 / 8 (uint8 / int32 / int64), NULL
+ *   together with labels_out: no labels.  voxel is the lattice step, mode 0 the mean, mode 1 the centre.
+ *    1. A row is finite iff x, y and z are finite.  Other rows belong to no voxel and are counted in stats[5].
+ *    2. lo[a] = minimum of coordinate a over the finite rows, -0.0 taken as below +0.0 (IEEE 754-2019 minimum, the
+ *       device's min instruction, as in conv3p_scene_blocks_rooms_f32), so lo does not depend on the order of the
+ *       reduction; s[a] = v[a] - lo[a], one float32 subtraction, a = x, y, z.
+ *    3. i_a = (int)floorf(s_a / voxel), one correctly rounded float32 division, the quotient held at 2^30 (an
+ *       overflowed s is +inf).  n_a = 1 + the largest i_a over the finite rows; n_a = 0 without a finite row.
+ *    4. The row's cell is (i_x, i_y, i_z), its id c = (i_x n_y + i_y) n_z + i_z in 64-bit integers.
+ *    5. Voxels are the occupied cells, numbered in ascending c, that is, ascending (i_x, i_y, i_z).  Voxels numbered
+ *       >= max_voxels are not emitted.
+ *    6. A voxel's member list is in ascending row.
+ *    7. mode 0 (mean), n = the members m_0 < m_1 < ...:  out[v][k] = (((x_k[m_0] + x_k[m_1]) + ...) ) / float(n) for
+ *       every channel k of the K, on the ORIGINAL values (xyz not shifted), each step a single float32 operation in
+ *       list order (n = 1: x / 1.0f).  voxel_row[v] = m_0.  labels_out[v] = the class with the most members among
+ *       those whose label l has 0 <= l < num_class (compared in the label's own width), the lowest class on a tie,
+ *       -1 with no such member.
+ *    8. mode 1 (centre):  the representative is the member that minimises d = ((s_x - c_x)^2 + (s_y - c_y)^2) +
+ *       (s_z - c_z)^2 with c_a = (float(i_a) + 0.5f) * voxel, every operation a single float32 one, uncontracted, in
+ *       that order; the lowest row on a tie.  out[v] = that row copied, voxel_row[v] = that row, labels_out[v] = its
+ *       label cast to int32.  num_class is not read.
+ *   Outputs: out float32 (max_voxels, K); labels_out int32 (max_voxels); voxel_row, voxel_count int32 (max_voxels),
+ *   the members per voxel; voxel_cell int32 (max_voxels, 3) = (i_x, i_y, i_z); inverse int32 (N), the voxel number of
+ *   every row, -1 for a non-finite row and for a row of a voxel that is not emitted; stats int32 (8) = {emitted
+ *   voxels, occupied voxels, n_x, n_y, n_z, non-finite rows, the largest member count over the occupied voxels,
+ *   error}.  Voxels nv..max_voxels-1 (nv = emitted voxels) get data 0, label -1, row -1, count 0, cell -1.
+ *   The error known on the device only: some n_a > 2^20, or n_x n_y n_z > 2^40 (a cell id has 40 bits of a sorted
+ *   pair): stats = {0, 0, n_x, n_y, n_z, non-finite rows, 0, 1}, nothing is emitted, inverse is all -1.
+ *   Status, in this order, all before any launch: N < 0, K < 3, max_voxels < 0, mode not 0 / 1, voxel not finite or
+ *   <= 0, labels given without labels_out or the reverse, labels with label_bytes not 1 / 4 / 8, num_class < 1 where it
+ *   is read (mode 0 with labels): CONV3P_ERR_INVALID_ARGUMENT; N == 0 or max_voxels == 0: CONV3P_OK, nothing launched,
+ *   nothing written; data, out, voxel_row, voxel_count, voxel_cell, inverse or stats NULL: CONV3P_ERR_INVALID_ARGUMENT;
+ *   N > 2^24 (a row has 24 bits of a sorted pair), K > 65536, or num_class > 128 where it is read:
+ *   CONV3P_ERR_UNSUPPORTED; workspace NULL, misaligned or shorter than conv3p_grid_subsample_workspace_bytes(N,
+ *   max_voxels): CONV3P_ERR_WORKSPACE.  That size is a host-side bound from its two arguments (two buffers of N pairs of
+ *   8 bytes and N + 1 list starts dominate: about 21 bytes a row), monotone in N, a multiple of 256, 0 for N <= 0, N >
+ *   2^24 or max_voxels <= 0; never a data-dependent failure.  The workspace need not be initialised and nothing is kept
+ *   in it.  The member lists come from a stable radix sort of (cell, row) pairs, 8 bits a pass: 24 launches in mode 0,
+ *   23 in mode 1, whatever the data (a pass over digits above the top bit of cells - 1 returns at once, by a word the
+ *   device wrote); no float atomics; every output word is written once by a plain store; bitwise reproducible and
+ *   independent of the launch geometry.
+ *
+ * conv3p_grid_project_labels:  out[i] = voxel_labels[inverse[i]] where 0 <= inverse[i] < M, otherwise -1; voxel_labels
+ *   int32 (M), inverse and out int32 (N).  Status: N < 0 or M < 0: CONV3P_ERR_INVALID_ARGUMENT; N == 0: CONV3P_OK,
+ *   nothing launched; inverse or out NULL, or voxel_labels NULL with M > 0: CONV3P_ERR_INVALID_ARGUMENT; N or M > 2^31 -
+ *   1: CONV3P_ERR_UNSUPPORTED.  One launch.
+ * ------------------------------------------------------------------------------------------- */
+#define CONV3P_GRID_MEAN 0
+#define CONV3P_GRID_CENTER 1
+size_t conv3p_grid_subsample_workspace_bytes(int64_t N, int max_voxels);
+int conv3p_grid_subsample_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float voxel,
+                              int mode, int num_class, int max_voxels, float *out, int32_t *labels_out,
+                              int32_t *voxel_row, int32_t *voxel_count, int32_t *voxel_cell, int32_t *inverse,
+                              int32_t *stats, void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_grid_project_labels(const int32_t *voxel_labels, const int32_t *inverse, int64_t N, int64_t M, int32_t *out,
+                               void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:
  * view (B, N*36) -> fully_connected 512, selu -> dropout_selu -> fully_connected num_class, selu).
  * tf.contrib.layers.fully_connected is y = activation(x . W + b) with W of shape (K, N).

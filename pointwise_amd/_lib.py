@@ -39,6 +39,11 @@ SCENE_MAX_NUM_POINT = 65536
 SCENE_ROOMS_MAX_CELLS = 1 << 20    # CONV3P_SCENE_ROOMS_MAX_CELLS; conv3p_scene_blocks_rooms_f32's limits: rooms, rows
 SCENE_ROOMS_MAX_ROOMS = 65536
 SCENE_ROOMS_MAX_ROWS = 1 << 26
+GRID_MEAN, GRID_CENTER = 0, 1     # CONV3P_GRID_*: the modes of conv3p_grid_subsample_f32
+GRID_MAX_ROWS = 1 << 24           # its limits: rows, cells along an axis, cells, classes of the majority
+GRID_MAX_AXIS = 1 << 20
+GRID_MAX_CELLS = 1 << 40
+GRID_MAX_CLASS = 128
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -140,6 +145,10 @@ SYMBOLS = {
     "conv3p_scene_vote_scores_f32": (_i, [_vp, _vp, _sz, ctypes.c_int64, _i, _vp, _vp, _vp]),
     "conv3p_scene_score_labels_workspace_bytes": (_sz, [ctypes.c_int64, _i]),
     "conv3p_scene_score_labels": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_grid_subsample_workspace_bytes": (_sz, [ctypes.c_int64, _i]),
+    "conv3p_grid_subsample_f32": (_i, [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_float, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_grid_project_labels": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

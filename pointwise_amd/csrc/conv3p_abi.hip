@@ -28,6 +28,7 @@
 #include "conv3p_scene.hpp"
 #include "conv3p_scene_cover.hpp"
 #include "conv3p_scene_rooms.hpp"
+#include "conv3p_grid.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3826,6 +3827,114 @@ int conv3p_scene_blocks_rooms_f32(const float *data, const void *labels, const i
     hipLaunchKernelGGL(rooms_table_kernel, dim3(scene_grid((size_t)max_blocks)), dim3(kSceneThreads), 0, s, a);
     hipLaunchKernelGGL(rooms_stats_kernel, dim3(scene_grid((size_t)R + 1)), dim3(kSceneThreads), 0, s, a);
     hipLaunchKernelGGL(rooms_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
+    return hip_ok();
+}
+
+namespace {
+// The workspace of conv3p_grid_subsample_f32 (conv3p_grid.hpp): a host-side bound from the arguments.  The two pair
+// buffers dominate it, 16 bytes a row; the list starts add 4.
+struct GridPlan {
+    int row_tiles, sort_tiles, voxel_grid;
+    size_t hdr, rec, tile, hist, digits, heads, start, part, pairs, total;
+};
+bool grid_plan(int64_t N, int max_voxels, GridPlan &w)
+{
+    if (N <= 0 || N > kGridMaxN || max_voxels <= 0) return false;
+    w.row_tiles = (int)((N + kGridRowTile - 1) / kGridRowTile);
+    w.sort_tiles = (int)((N + kGridSortTile - 1) / kGridSortTile);
+    const int64_t voxels = N > max_voxels ? N : (int64_t)max_voxels;               // occupied voxels and fillers
+    const int64_t vg = (voxels + kGridVoxelGroups - 1) / kGridVoxelGroups;
+    w.voxel_grid = (int)(vg < kSceneMaxGrid ? vg : kSceneMaxGrid);
+    w.hdr = up(sizeof(GridHeader));
+    w.rec = up((size_t)w.row_tiles * 8 * sizeof(float));
+    w.tile = up((size_t)w.row_tiles * sizeof(int));
+    w.hist = up((size_t)w.sort_tiles * kGridDigits * sizeof(int));
+    w.digits = up((size_t)kGridPasses * kGridDigits * sizeof(int));
+    w.heads = up((size_t)w.sort_tiles * sizeof(int));
+    w.start = up(((size_t)N + 1) * sizeof(int));
+    w.part = up((size_t)kSceneMaxGrid * sizeof(int));
+    w.pairs = up((size_t)N * sizeof(unsigned long long));
+    w.total = w.hdr + w.rec + w.tile + w.hist + w.digits + w.heads + w.start + w.part + 2 * w.pairs;
+    return true;
+}
+}  // namespace
+
+size_t conv3p_grid_subsample_workspace_bytes(int64_t N, int max_voxels)
+{
+    GridPlan w;
+    return grid_plan(N, max_voxels, w) ? w.total : 0;
+}
+
+// Every status first, in the order include/conv3p.h gives; then the launches, their number fixed by the arguments.
+int conv3p_grid_subsample_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float voxel,
+                              int mode, int num_class, int max_voxels, float *out, int32_t *labels_out,
+                              int32_t *voxel_row, int32_t *voxel_count, int32_t *voxel_cell, int32_t *inverse,
+                              int32_t *stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || K < 3 || max_voxels < 0 || (mode != 0 && mode != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
+    const bool votes = labels && mode == 0;              // num_class is read by the majority only
+    if (votes && num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N == 0 || max_voxels == 0) return CONV3P_OK;
+    if (!data || !out || !voxel_row || !voxel_count || !voxel_cell || !inverse || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > kGridMaxN || K > 65536 || (votes && num_class > kGridMaxClass)) return CONV3P_ERR_UNSUPPORTED;
+    GridPlan w;
+    if (!grid_plan(N, max_voxels, w)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, w.total));
+    GridArgs a;
+    a.data = data; a.labels = labels;
+    a.N = (int)N; a.K = K; a.label_bytes = label_bytes; a.mode = mode; a.num_class = num_class; a.max_voxels = max_voxels;
+    a.voxel = voxel;
+    a.out = out; a.labels_out = labels_out; a.voxel_row = voxel_row; a.voxel_count = voxel_count; a.voxel_cell = voxel_cell;
+    a.inverse = inverse; a.stats = stats;
+    char *ws = static_cast<char *>(workspace);
+    a.hdr = reinterpret_cast<GridHeader *>(ws); ws += w.hdr;
+    a.records = reinterpret_cast<float *>(ws); ws += w.rec;
+    a.tile_off = reinterpret_cast<int *>(ws); ws += w.tile;
+    a.hist = reinterpret_cast<int *>(ws); ws += w.hist;
+    a.digit_total = reinterpret_cast<int *>(ws); ws += w.digits;
+    a.heads = reinterpret_cast<int *>(ws); ws += w.heads;
+    a.start = reinterpret_cast<int *>(ws); ws += w.start;
+    a.part_max = reinterpret_cast<int *>(ws); ws += w.part;
+    a.pairs_a = reinterpret_cast<unsigned long long *>(ws); ws += w.pairs;
+    a.pairs_b = reinterpret_cast<unsigned long long *>(ws);
+    a.row_tiles = w.row_tiles; a.voxel_grid = w.voxel_grid;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned sgrid = (unsigned)(w.sort_tiles < kSceneMaxGrid ? w.sort_tiles : kSceneMaxGrid);
+    hipLaunchKernelGGL(grid_bounds_kernel, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_frame_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_pairs_kernel, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
+    for (int pass = 0; pass < kGridPasses; ++pass) {     // a pass above the cell ids' top bit returns at once
+        hipLaunchKernelGGL(grid_sort_hist_kernel, dim3(sgrid), dim3(kSceneThreads), 0, s, a, pass);
+        hipLaunchKernelGGL(grid_sort_scan_kernel, dim3(kGridDigits), dim3(kGridScanThreads), 0, s, a, pass);
+        hipLaunchKernelGGL(grid_sort_scatter_kernel, dim3(sgrid), dim3(64), 0, s, a, pass);
+    }
+    hipLaunchKernelGGL(grid_heads_kernel<false>, dim3(sgrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_heads_scan_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_heads_kernel<true>, dim3(sgrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_voxel_kernel, dim3((unsigned)w.voxel_grid), dim3(kSceneThreads), 0, s, a);
+    if (mode == 0) {
+        const size_t work = ((size_t)max_voxels * (size_t)K + kSceneThreads - 1) / kSceneThreads;
+        hipLaunchKernelGGL(grid_mean_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
+                           dim3(kSceneThreads), 0, s, a);
+    }
+    hipLaunchKernelGGL(grid_stats_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
+    return hip_ok();
+}
+
+int conv3p_grid_project_labels(const int32_t *voxel_labels, const int32_t *inverse, int64_t N, int64_t M, int32_t *out,
+                               void *stream)
+{
+    if (N < 0 || M < 0) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N == 0) return CONV3P_OK;
+    if (!inverse || !out || (M > 0 && !voxel_labels)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX || M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;   // inverse is int32
+    const size_t work = ((size_t)N + kSceneThreads - 1) / kSceneThreads;
+    hipLaunchKernelGGL(grid_project_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
+                       dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream), voxel_labels, inverse, (long long)N,
+                       (long long)M, out);
     return hip_ok();
 }
 

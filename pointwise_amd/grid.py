@@ -1,0 +1,155 @@
+"""Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
+conv3p_grid_subsample_f32, conv3p_grid_project_labels; kernels in csrc/conv3p_grid.hpp).
+
+A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
+first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
+every raw row takes the prediction of its voxel.  include/conv3p.h defines the result bit for bit -- the voxels in
+ascending (i_x, i_y, i_z), a voxel's members in ascending row, the mean a chain of float32 additions in that order -- and
+tests/grid_ref.py restates it in numpy.
+
+    grid_subsample   one cloud (N, K) -> GridSubsample: data (max_voxels, K), labels, inverse (the voxel of every raw
+                     row), voxel_row, voxel_count, voxel_cell, stats
+    GridSubsample.project   voxel labels (num_voxels) -> a label per raw row (N) int32, -1 for a row without a voxel
+
+mode="mean" averages every channel over a voxel's members and takes their majority label; mode="center" keeps the member
+nearest the voxel's centre as it is.
+
+From a raw room to the model and back:
+
+    g = grid_subsample(room, room_labels, voxel=0.04, num_class=13).trim()
+    sb = scene_blocks(g.data, g.labels, num_point=4096, stride=0.5, cover=True, min_points=1).trim()
+    pv = BatchProvider(sb.data, sb.index, batch_size, training=False, sort_cloud=True)   # index: the voxel of every row
+    scores = SceneScores(g.num_voxels(), num_class, room.device)
+    per batch:  points, inp, idx = pv.get_batch_point_cloud();  scores.add(model(points, inp), idx)
+    labels = g.project(scores.labels())                              # (N) int32 over the raw rows
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .conv3p_op import _call, _require
+from .scene import _LABEL_DTYPES
+
+_MODES = {"mean": _lib.GRID_MEAN, "center": _lib.GRID_CENTER}
+
+
+class GridSubsample:
+    """The outputs of grid_subsample: data float32 (max_voxels, K), labels int32 (max_voxels) or None, inverse int32
+    (N) (the voxel number of every raw row; -1 for a non-finite row and for a row of a voxel that max_voxels cut),
+    voxel_row (mean: the lowest member row; center: the representative), voxel_count, voxel_cell (max_voxels, 3), stats
+    int32 (8) = {emitted voxels, occupied voxels, n_x, n_y, n_z, non-finite rows, largest member count, error}.  Voxels
+    past the emitted ones hold data 0, labels -1, voxel_row -1, voxel_count 0, voxel_cell -1."""
+
+    def __init__(self, num_rows, max_voxels, K, with_labels, device, workspace_bytes=0):
+        N, M = int(num_rows), int(max_voxels)
+        self.shape = (N, M, int(K), bool(with_labels))
+        self.data = torch.empty((M, K), dtype=torch.float32, device=device)
+        self.labels = torch.empty((M,), dtype=torch.int32, device=device) if with_labels else None
+        self.inverse = torch.empty((N,), dtype=torch.int32, device=device)
+        self.voxel_row = torch.empty((M,), dtype=torch.int32, device=device)
+        self.voxel_count = torch.empty((M,), dtype=torch.int32, device=device)
+        self.voxel_cell = torch.empty((M, 3), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((8,), dtype=torch.int32, device=device)
+        self.workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=device) if workspace_bytes else None
+
+    def num_voxels(self):
+        """The number of emitted voxels: the one host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def trim(self):
+        """Views of the first num_voxels() voxels, as a GridSubsample (inverse and stats shared)."""
+        nv = self.num_voxels()
+        t = object.__new__(GridSubsample)
+        t.shape = (self.shape[0], nv) + self.shape[2:]
+        t.data = self.data[:nv]
+        t.labels = self.labels[:nv] if self.labels is not None else None
+        t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[:nv], self.voxel_count[:nv], self.voxel_cell[:nv]
+        t.inverse, t.stats, t.workspace = self.inverse, self.stats, None
+        return t
+
+    def project(self, voxel_labels, out=None):
+        """voxel_labels int32 (M), a label per voxel (the model's, SceneVotes.labels(), ...) -> (N) int32, the label of
+        every raw row's voxel; -1 for a row whose inverse is -1 or not below M.  One launch, nothing synchronised on."""
+        dev = self.inverse.device
+        _require(isinstance(voxel_labels, torch.Tensor) and voxel_labels.dtype == torch.int32 and voxel_labels.dim() == 1
+                 and voxel_labels.device == dev and voxel_labels.is_contiguous(),
+                 "voxel_labels must be a contiguous int32 (M,) tensor on the cloud's device")
+        N, M = self.inverse.numel(), voxel_labels.numel()
+        if out is None:
+            out = torch.empty((N,), dtype=torch.int32, device=dev)
+        _require(isinstance(out, torch.Tensor) and out.dtype == torch.int32 and tuple(out.shape) == (N,) and out.device == dev
+                 and out.is_contiguous(), "out must be a contiguous int32 (N,) tensor on the cloud's device")
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        if N == 0:
+            return out
+        with torch.cuda.device(dev):
+            _call(_lib.load().conv3p_grid_project_labels, voxel_labels.data_ptr() if M else None, self.inverse.data_ptr(), N,
+                  M, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+
+def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, max_voxels=None, out=None):
+    """One cloud -> GridSubsample, by the eight steps of include/conv3p.h (conv3p_grid_subsample_f32).
+
+    data float32 (N, K >= 3), xyz first; labels (N) uint8 / int32 / int64 or None.  voxel, the lattice step, is taken
+    as float32.  mode "mean": every channel averaged over the voxel's members in ascending row, the label their majority
+    among 0 <= l < num_class (num_class in [1, 128], required with labels); mode "center": the member nearest the
+    voxel's centre, copied with its label (num_class is not used).  max_voxels=None means N, which never cuts.  out: a
+    GridSubsample of an earlier call with the same shapes, written into.  Nothing is synchronised on; stats[7] != 0
+    reports a lattice of more than 2^20 cells along an axis or 2^40 in all (nothing emitted, inverse all -1)."""
+    _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
+             "data must be a float32 (N, K >= 3) tensor, xyz first")
+    dev = data.device
+    N, K = data.shape
+    _require(data.is_contiguous(), "data must be contiguous")
+    if labels is not None:
+        _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
+        _require(labels.device == dev and tuple(labels.shape) == (N,) and labels.is_contiguous(),
+                 "labels must be a contiguous (N,) tensor on the data's device")
+    _require(isinstance(voxel, (int, float)) and not isinstance(voxel, bool) and math.isfinite(voxel)
+             and math.isfinite(float(np.float32(voxel))) and float(np.float32(voxel)) > 0, "voxel must be finite and positive")
+    voxel = float(np.float32(voxel))
+    _require(isinstance(mode, str) and mode in _MODES, "mode must be \"mean\" or \"center\"")
+    if labels is not None and mode == "mean":
+        _require(isinstance(num_class, int) and not isinstance(num_class, bool) and 1 <= num_class <= _lib.GRID_MAX_CLASS,
+                 "num_class must be an integer in [1, %d] for the majority label" % _lib.GRID_MAX_CLASS)
+    else:
+        _require(num_class is None or (isinstance(num_class, int) and not isinstance(num_class, bool)),
+                 "num_class must be an integer or None")
+    _require(N <= _lib.GRID_MAX_ROWS, "at most 2^24 rows")
+    _require(K <= 65536, "at most 65536 channels")
+    if max_voxels is None:
+        max_voxels = N
+    _require(isinstance(max_voxels, int) and not isinstance(max_voxels, bool) and 0 <= max_voxels < 2 ** 31,
+             "max_voxels must be a non-negative integer")
+    if out is not None:
+        _require(isinstance(out, GridSubsample) and out.shape == (N, max_voxels, K, labels is not None)
+                 and out.data.device == dev, "out was made for another shape")
+    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
+    lib = _lib.load()
+    need = lib.conv3p_grid_subsample_workspace_bytes(N, max_voxels)
+    if out is None:
+        out = GridSubsample(N, max_voxels, K, labels is not None, dev, need)
+    elif need and (out.workspace is None or out.workspace.numel() < need):
+        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if N == 0 or max_voxels == 0:            # nothing is launched, so nothing is written
+        out.data.zero_()
+        out.inverse.fill_(-1)
+        out.voxel_row.fill_(-1)
+        out.voxel_count.zero_()
+        out.voxel_cell.fill_(-1)
+        out.stats.zero_()
+        if out.labels is not None:
+            out.labels.fill_(-1)
+        return out
+    ws = out.workspace
+    with torch.cuda.device(dev):
+        _call(lib.conv3p_grid_subsample_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None, N, K,
+              _LABEL_DTYPES[labels.dtype] if labels is not None else 0, voxel, _MODES[mode],
+              num_class if num_class is not None else 0, max_voxels, out.data.data_ptr(),
+              out.labels.data_ptr() if labels is not None else None, out.voxel_row.data_ptr(), out.voxel_count.data_ptr(),
+              out.voxel_cell.data_ptr(), out.inverse.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out
