@@ -642,7 +642,8 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  * Voxel-grid subsampling of a cloud, and voxel labels projected back to its rows
  * (pointwise_amd/csrc/conv3p_grid.hpp; tests/grid_ref.py restates it in numpy).  The step in front of the scene calls:
  * a raw room or scan is thinned to one row per occupied voxel, the model runs on those rows, and every raw row gets its
- * voxel's prediction.  One cloud per call; rows are float32, xyz first.  Additions: nothing above changes.
+ * voxel's prediction.  One cloud per call, or many with a room_start; rows are float32, xyz first.  Additions: nothing
+ * above changes.
  *
  * conv3p_grid_subsample_f32:  data (N, K), K >= 3; labels (N) of label_bytes = 1 / 4 / 8 (uint8 / int32 / int64), NULL
  *   together with labels_out: no labels.  voxel is the lattice step, mode 0 the mean, mode 1 the centre.
@@ -690,6 +691,50 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   int32 (M), inverse and out int32 (N).  Status: N < 0 or M < 0: CONV3P_ERR_INVALID_ARGUMENT; N == 0: CONV3P_OK,
  *   nothing launched; inverse or out NULL, or voxel_labels NULL with M > 0: CONV3P_ERR_INVALID_ARGUMENT; N or M > 2^31 -
  *   1: CONV3P_ERR_UNSUPPORTED.  One launch.
+ *
+ * conv3p_grid_subsample_rooms_f32:  MANY CLOUDS in one call (pointwise_amd/csrc/conv3p_grid_rooms.hpp;
+ *   tests/grid_rooms_ref.py restates it on the single-cloud reference).  data (N, K) holds the rooms' rows one room
+ *   after the other; room_start, int32 (R + 1) ON THE DEVICE, gives room r the rows [room_start[r], room_start[r+1]).
+ *   Rows before room_start[0] or from room_start[R] on belong to no room: their inverse is -1 and they are counted
+ *   nowhere.  The result is the concatenation of the single-cloud calls:
+ *    a. Room r is subsampled exactly as by conv3p_grid_subsample_f32 run on the room's own rows with the same voxel,
+ *       mode and num_class.  Steps 1-8 hold per room; lo, n_x, n_y, n_z and the cell ids are the room's own, so two
+ *       rooms that overlap in space never share a voxel.
+ *    b. Voxels are numbered room after room, within a room in ascending cell id; first_r = the occupied voxels of the
+ *       rooms before r.  Voxels numbered >= max_voxels are not emitted: room r behaves as its single call with
+ *       max_voxels_r = max(0, max_voxels - first_r).  Voxels past the emitted ones get the single call's filler and
+ *       voxel_room -1.
+ *    c. inverse (N) holds the GLOBAL voxel number, voxel_row the GLOBAL row; labels is (N), indexed by global row.
+ *       voxel_cell is (i_x, i_y, i_z) in the room's own lattice, voxel_room (max_voxels) the room of each voxel.
+ *    d. voxel_start int32 (R + 1): the prefix of the emitted voxels per room, voxel_start[R] = stats[0] -- unchanged and
+ *       still on the device, the room_start of conv3p_scene_blocks_rooms_f32 over the rows of out.
+ *       room_stats int32 (R, 8): the eight words the single call would write for room r with max_voxels_r -- words 1-7
+ *       also when max_voxels_r = 0 (word 0 is then 0); word 6, the largest member count, is taken over the room's
+ *       occupied voxels as in the single call; an empty room gives eight zeros.
+ *       stats int32 (8) = {emitted voxels, occupied voxels over all rooms without an error of their own, R, rooms with
+ *       at least one emitted voxel, rooms with an error of their own, non-finite rows inside the rooms, the largest
+ *       member count over all rooms, error bits}.
+ *    e. Errors known on the device only, stats[7]:  bit 0: some room's own lattice has an n_a > 2^20 or more than 2^40
+ *       cells; that room emits nothing, its room_stats[r] is {0, 0, n_x, n_y, n_z, non-finite rows, 0, 1} and its rows
+ *       have inverse -1; every other room is unaffected.  bit 1: room_start is malformed (room_start[0] < 0, a
+ *       decrease, room_start[R] > N): nothing is read through it, nothing is emitted, inverse is all -1, voxel_start
+ *       and room_stats are all 0 (so stats = {0, 0, R, 0, 0, 0, 0, 2}).  bit 2: the cells, summed over the rooms
+ *       without an error of their own, exceed 2^40 -- a global cell id is cell_base[r] + c, cell_base the 64-bit prefix
+ *       of the rooms' cell counts, and must fit the 40 bits of a sorted pair: nothing is emitted, voxel_start is all 0,
+ *       inverse is all -1, room_stats keeps words 2, 3, 4, 5 and 7 and has 0 elsewhere.
+ *   Status, in this order, all before any launch: N < 0, R < 0, K < 3, max_voxels < 0, mode not 0 / 1, voxel not finite
+ *   or <= 0, labels given without labels_out or the reverse, labels with label_bytes not 1 / 4 / 8, num_class < 1 where
+ *   it is read (mode 0 with labels): CONV3P_ERR_INVALID_ARGUMENT; R == 0, N == 0 or max_voxels == 0: CONV3P_OK, nothing
+ *   launched, nothing written; a NULL data, room_start or output (labels_out apart): CONV3P_ERR_INVALID_ARGUMENT;
+ *   N > 2^24 summed over all rooms (a GLOBAL row keeps the 24 bits of a sorted pair), R > 65536, K > 65536, or
+ *   num_class > 128 where it is read: CONV3P_ERR_UNSUPPORTED; then CONV3P_ERR_WORKSPACE against
+ *   conv3p_grid_subsample_rooms_workspace_bytes(N, R, max_voxels), a host-side bound from its three arguments (the
+ *   single call's, plus 32 bytes of a bounds record, a frame of 48 bytes and two prefix words per room), monotone in N
+ *   and R, a multiple of 256, 0 for arguments the call refuses or does nothing for; never a data-dependent failure.
+ *   The workspace need not be initialised and nothing is kept in it.  One stable radix sort orders all rooms' (global
+ *   cell, global row) pairs, by the single call's sort, heads and mean kernels: 28 launches in mode 0, 27 in mode 1,
+ *   fixed by mode alone whatever R, the rooms' sizes and the data; no float atomics; every output word is written once
+ *   by a plain store; bitwise reproducible and independent of the launch geometry.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_GRID_MEAN 0
 #define CONV3P_GRID_CENTER 1
@@ -700,6 +745,13 @@ int conv3p_grid_subsample_f32(const float *data, const void *labels, int64_t N, 
                               int32_t *stats, void *workspace, size_t workspace_bytes, void *stream);
 int conv3p_grid_project_labels(const int32_t *voxel_labels, const int32_t *inverse, int64_t N, int64_t M, int32_t *out,
                                void *stream);
+size_t conv3p_grid_subsample_rooms_workspace_bytes(int64_t N, int64_t R, int max_voxels);
+int conv3p_grid_subsample_rooms_f32(const float *data, const void *labels, const int32_t *room_start, int64_t N, int64_t R,
+                                    int K, int label_bytes, float voxel, int mode, int num_class, int max_voxels,
+                                    float *out, int32_t *labels_out, int32_t *voxel_row, int32_t *voxel_count,
+                                    int32_t *voxel_cell, int32_t *voxel_room, int32_t *voxel_start, int32_t *inverse,
+                                    int32_t *room_stats, int32_t *stats, void *workspace, size_t workspace_bytes,
+                                    void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

@@ -44,6 +44,7 @@ GRID_MAX_ROWS = 1 << 24           # its limits: rows, cells along an axis, cells
 GRID_MAX_AXIS = 1 << 20
 GRID_MAX_CELLS = 1 << 40
 GRID_MAX_CLASS = 128
+GRID_ROOMS_MAX_ROOMS = 65536      # conv3p_grid_subsample_rooms_f32: rooms; its rows, summed, share GRID_MAX_ROWS
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -149,6 +150,9 @@ SYMBOLS = {
     "conv3p_grid_subsample_f32": (_i, [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_float, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _sz, _vp]),
     "conv3p_grid_project_labels": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
+    "conv3p_grid_subsample_rooms_workspace_bytes": (_sz, [ctypes.c_int64, ctypes.c_int64, _i]),
+    "conv3p_grid_subsample_rooms_f32": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, ctypes.c_float, _i, _i, _i,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

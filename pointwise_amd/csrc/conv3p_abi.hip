@@ -29,6 +29,7 @@
 #include "conv3p_scene_cover.hpp"
 #include "conv3p_scene_rooms.hpp"
 #include "conv3p_grid.hpp"
+#include "conv3p_grid_rooms.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3935,6 +3936,112 @@ int conv3p_grid_project_labels(const int32_t *voxel_labels, const int32_t *inver
     hipLaunchKernelGGL(grid_project_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
                        dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream), voxel_labels, inverse, (long long)N,
                        (long long)M, out);
+    return hip_ok();
+}
+
+namespace {
+// The workspace of conv3p_grid_subsample_rooms_f32 (conv3p_grid_rooms.hpp): the single call's words -- the records grown
+// by one per room, the tiles' pair offsets giving way to the voxel tiles' maxima -- and per room a frame and two prefixes.
+struct GridRoomsPlan {
+    GridPlan g;
+    size_t xhdr, room, cbase, pbase, rec, total;
+};
+bool grid_rooms_plan(int64_t N, int64_t R, int max_voxels, GridRoomsPlan &w)
+{
+    if (R <= 0 || R > kGridRoomsMaxRooms || !grid_plan(N, max_voxels, w.g)) return false;
+    w.xhdr = up(sizeof(GridRoomsHeader));
+    w.room = up((size_t)R * sizeof(GridRoomFrame));
+    w.cbase = up(((size_t)R + 1) * sizeof(long long));
+    w.pbase = up(((size_t)R + 1) * sizeof(int));
+    w.rec = up(((size_t)w.g.row_tiles + (size_t)R) * 8 * sizeof(float));
+    w.total = w.g.hdr + w.xhdr + w.room + w.cbase + w.pbase + w.rec + w.g.tile + w.g.hist + w.g.digits + w.g.heads +
+              w.g.start + w.g.part + 2 * w.g.pairs;
+    return true;
+}
+}  // namespace
+
+size_t conv3p_grid_subsample_rooms_workspace_bytes(int64_t N, int64_t R, int max_voxels)
+{
+    GridRoomsPlan w;
+    return grid_rooms_plan(N, R, max_voxels, w) ? w.total : 0;
+}
+
+// Every status first, in the order include/conv3p.h gives; then the launches, their number fixed by mode alone.
+int conv3p_grid_subsample_rooms_f32(const float *data, const void *labels, const int32_t *room_start, int64_t N, int64_t R,
+                                    int K, int label_bytes, float voxel, int mode, int num_class, int max_voxels,
+                                    float *out, int32_t *labels_out, int32_t *voxel_row, int32_t *voxel_count,
+                                    int32_t *voxel_cell, int32_t *voxel_room, int32_t *voxel_start, int32_t *inverse,
+                                    int32_t *room_stats, int32_t *stats, void *workspace, size_t workspace_bytes,
+                                    void *stream)
+{
+    if (N < 0 || R < 0 || K < 3 || max_voxels < 0 || (mode != 0 && mode != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
+    const bool votes = labels && mode == 0;              // num_class is read by the majority only
+    if (votes && num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (R == 0 || N == 0 || max_voxels == 0) return CONV3P_OK;
+    if (!data || !room_start || !out || !voxel_row || !voxel_count || !voxel_cell || !voxel_room || !voxel_start ||
+        !inverse || !room_stats || !stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > kGridMaxN || R > kGridRoomsMaxRooms || K > 65536 || (votes && num_class > kGridMaxClass))
+        return CONV3P_ERR_UNSUPPORTED;
+    GridRoomsPlan w;
+    if (!grid_rooms_plan(N, R, max_voxels, w)) return CONV3P_ERR_UNSUPPORTED;
+    TRY(buf_check(workspace, workspace_bytes, w.total));
+    GridRoomsArgs a;
+    GridArgs &g = a.g;
+    g.data = data; g.labels = labels;
+    g.N = (int)N; g.K = K; g.label_bytes = label_bytes; g.mode = mode; g.num_class = num_class; g.max_voxels = max_voxels;
+    g.voxel = voxel;
+    g.out = out; g.labels_out = labels_out; g.voxel_row = voxel_row; g.voxel_count = voxel_count; g.voxel_cell = voxel_cell;
+    g.inverse = inverse; g.stats = stats;
+    a.room_start = room_start; a.R = (int)R;
+    a.voxel_room = voxel_room; a.voxel_start = voxel_start; a.room_stats = room_stats;
+    char *ws = static_cast<char *>(workspace);
+    g.hdr = reinterpret_cast<GridHeader *>(ws); ws += w.g.hdr;
+    a.xh = reinterpret_cast<GridRoomsHeader *>(ws); ws += w.xhdr;
+    a.room = reinterpret_cast<GridRoomFrame *>(ws); ws += w.room;
+    a.cell_base = reinterpret_cast<long long *>(ws); ws += w.cbase;
+    a.pair_base = reinterpret_cast<int *>(ws); ws += w.pbase;
+    g.records = reinterpret_cast<float *>(ws); ws += w.rec;
+    a.tile_max = reinterpret_cast<int *>(ws); ws += w.g.tile;
+    g.tile_off = nullptr;
+    g.hist = reinterpret_cast<int *>(ws); ws += w.g.hist;
+    g.digit_total = reinterpret_cast<int *>(ws); ws += w.g.digits;
+    g.heads = reinterpret_cast<int *>(ws); ws += w.g.heads;
+    g.start = reinterpret_cast<int *>(ws); ws += w.g.start;
+    g.part_max = reinterpret_cast<int *>(ws); ws += w.g.part;
+    g.pairs_a = reinterpret_cast<unsigned long long *>(ws); ws += w.g.pairs;
+    g.pairs_b = reinterpret_cast<unsigned long long *>(ws);
+    g.row_tiles = w.g.row_tiles; g.voxel_grid = w.g.voxel_grid;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned tgrid = (unsigned)w.g.row_tiles;
+    const unsigned rgrid = (unsigned)(R < kSceneMaxGrid ? R : kSceneMaxGrid);
+    const unsigned sgrid = (unsigned)(w.g.sort_tiles < kSceneMaxGrid ? w.g.sort_tiles : kSceneMaxGrid);
+    hipLaunchKernelGGL(grid_rooms_check_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_rooms_bounds_kernel, dim3(tgrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_rooms_frame_kernel, dim3(rgrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_rooms_base_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_rooms_pairs_kernel, dim3(tgrid), dim3(kSceneThreads), 0, s, a);
+    for (int pass = 0; pass < kGridPasses; ++pass) {     // a pass above the global cell ids' top bit returns at once
+        hipLaunchKernelGGL(grid_sort_hist_kernel, dim3(sgrid), dim3(kSceneThreads), 0, s, g, pass);
+        hipLaunchKernelGGL(grid_sort_scan_kernel, dim3(kGridDigits), dim3(kGridScanThreads), 0, s, g, pass);
+        hipLaunchKernelGGL(grid_sort_scatter_kernel, dim3(sgrid), dim3(64), 0, s, g, pass);
+    }
+    hipLaunchKernelGGL(grid_heads_kernel<false>, dim3(sgrid), dim3(kSceneThreads), 0, s, g);
+    hipLaunchKernelGGL(grid_heads_scan_kernel, dim3(1), dim3(kGridScanThreads), 0, s, g);
+    hipLaunchKernelGGL(grid_heads_kernel<true>, dim3(sgrid), dim3(kSceneThreads), 0, s, g);
+    hipLaunchKernelGGL(grid_rooms_voxel_kernel, dim3((unsigned)w.g.voxel_grid), dim3(kSceneThreads), 0, s, a);
+    if (mode == 0) {
+        const size_t work = ((size_t)max_voxels * (size_t)K + kSceneThreads - 1) / kSceneThreads;
+        hipLaunchKernelGGL(grid_mean_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
+                           dim3(kSceneThreads), 0, s, g);
+    }
+    hipLaunchKernelGGL(grid_rooms_count_max_kernel, dim3(tgrid), dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_rooms_out_kernel, dim3((unsigned)((R + 3) / 4 < kSceneMaxGrid ? (R + 3) / 4 : kSceneMaxGrid)),
+                       dim3(kSceneThreads), 0, s, a);
+    hipLaunchKernelGGL(grid_rooms_stats_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
     return hip_ok();
 }
 

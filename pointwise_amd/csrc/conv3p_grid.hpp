@@ -378,10 +378,28 @@ __device__ __forceinline__ int32_t grid_label(const GridArgs &p, size_t idx)
     return (int32_t) static_cast<const long long *>(p.labels)[idx];
 }
 
+// The frame of one room of conv3p_grid_subsample_rooms_f32 (conv3p_grid_rooms.hpp), and what grid_voxel_body reads of
+// the rooms: a voxel's cell id is cell_base[r] + c, c the id in room r's own lattice.
+struct GridRoomFrame {
+    float lo[3];
+    int n[3];                          // room_stats[r][2..4]
+    long long cells;                   // 0 with the room's error, without a finite row, and when nothing may be emitted
+    int error, nonfinite;
+    int pairs, pad;                    // the room's finite rows (0 where cells is 0)
+};
+
+struct GridRoomsView {
+    const GridRoomFrame *room;         // (R)
+    const long long *cell_base;        // (R + 1): the prefix of the rooms' cells
+    int32_t *voxel_room;               // (max_voxels)
+    int R;
+};
+
 // Eight lanes per voxel, v over the occupied voxels and the fillers behind them: short lists dominate, and a list of any
 // length is walked eight members a step.  Everything a group does depends on its own voxel alone; the shuffles stay
-// inside the group's eight lanes, which are active together.
-__global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArgs p)
+// inside the group's eight lanes, which are active together.  kRooms: the voxel's room by binary search in cell_base,
+// the cell decoded with the room's n, the centre's s formed with the room's lo; the rows are global either way.
+template <bool kRooms> __device__ __forceinline__ void grid_voxel_body(const GridArgs &p, const GridRoomsView &rv)
 {
     __shared__ int hist_s[kGridVoxelGroups][kGridMaxClass];
     __shared__ int max_s[kSceneThreads / 64];
@@ -404,6 +422,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArg
                 p.voxel_cell[3 * (size_t)v + 1] = -1;
                 p.voxel_cell[3 * (size_t)v + 2] = -1;
                 if (p.labels_out) p.labels_out[v] = -1;
+                if (kRooms) rv.voxel_room[v] = -1;
             }
             if (!mean)
                 for (int k = gl; k < K; k += kGridGroup) p.out[(size_t)v * K + k] = 0.0f;
@@ -413,8 +432,23 @@ __global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArg
         longest = n > longest ? n : longest;
         const bool emit = v < ne;
         const unsigned long long head = sorted[s0];
-        const long long c = (long long)(head >> kGridRowBits);
-        const int iz = (int)(c % h.n[2]), iy = (int)((c / h.n[2]) % h.n[1]), ix = (int)(c / ((long long)h.n[2] * h.n[1]));
+        long long c = (long long)(head >> kGridRowBits);
+        int room = 0, n1 = h.n[1], n2 = h.n[2];
+        float lo0 = h.lo[0], lo1 = h.lo[1], lo2 = h.lo[2];
+        if (kRooms) {
+            int rl = 0, rh = rv.R - 1;                   // the last room whose cell_base is <= c: the one with cells
+            while (rl < rh) {
+                const int mid = (rl + rh + 1) >> 1;
+                if (rv.cell_base[mid] <= c) rl = mid; else rh = mid - 1;
+            }
+            const GridRoomFrame *f = rv.room + rl;
+            room = rl;
+            c -= rv.cell_base[rl];
+            n1 = f->n[1] > 0 ? f->n[1] : 1;
+            n2 = f->n[2] > 0 ? f->n[2] : 1;
+            lo0 = f->lo[0]; lo1 = f->lo[1]; lo2 = f->lo[2];
+        }
+        const int iz = (int)(c % n2), iy = (int)((c / n2) % n1), ix = (int)(c / ((long long)n2 * n1));
         float best = INFINITY;
         int best_row = 0x7fffffff;
         const float cx = ((float)ix + 0.5f) * p.voxel, cy = ((float)iy + 0.5f) * p.voxel, cz = ((float)iz + 0.5f) * p.voxel;
@@ -429,7 +463,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArg
                 }
             } else {
                 const float *q = p.data + (size_t)row * K;
-                const float dx = (q[0] - h.lo[0]) - cx, dy = (q[1] - h.lo[1]) - cy, dz = (q[2] - h.lo[2]) - cz;
+                const float dx = (q[0] - lo0) - cx, dy = (q[1] - lo1) - cy, dz = (q[2] - lo2) - cz;
                 const float d = ((dx * dx) + (dy * dy)) + (dz * dz);
                 // a lane's rows ascend, so a strict comparison keeps the lowest row of equal distances; the first
                 // member is taken whatever its distance (an overflowed one is +inf)
@@ -486,6 +520,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArg
             p.voxel_cell[3 * (size_t)v + 1] = iy;
             p.voxel_cell[3 * (size_t)v + 2] = iz;
             if (p.labels_out) p.labels_out[v] = label;
+            if (kRooms) rv.voxel_room[v] = room;
         }
     }
     for (int d = 32; d >= 1; d >>= 1) {                  // the groups are back together
@@ -499,6 +534,11 @@ __global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArg
         for (int k = 1; k < kSceneThreads / 64; ++k) m = max_s[k] > m ? max_s[k] : m;
         p.part_max[blockIdx.x] = m;
     }
+}
+
+__global__ __launch_bounds__(kSceneThreads) void grid_voxel_kernel(const GridArgs p)
+{
+    grid_voxel_body<false>(p, GridRoomsView{nullptr, nullptr, nullptr, 0});
 }
 
 // mode 0: out[v][k] = (((x[m_0] + x[m_1]) + ...) ) / float(n), a thread per (voxel, channel); the threads of a voxel's

@@ -10,6 +10,8 @@ tests/grid_ref.py restates it in numpy.
     grid_subsample   one cloud (N, K) -> GridSubsample: data (max_voxels, K), labels, inverse (the voxel of every raw
                      row), voxel_row, voxel_count, voxel_cell, stats
     GridSubsample.project   voxel labels (num_voxels) -> a label per raw row (N) int32, -1 for a row without a voxel
+    grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
+                     voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
 mode="mean" averages every channel over a voxel's members and takes their majority label; mode="center" keeps the member
 nearest the voxel's centre as it is.
@@ -22,6 +24,9 @@ From a raw room to the model and back:
     scores = SceneScores(g.num_voxels(), num_class, room.device)
     per batch:  points, inp, idx = pv.get_batch_point_cloud();  scores.add(model(points, inp), idx)
     labels = g.project(scores.labels())                              # (N) int32 over the raw rows
+
+A whole area or split, room_start its R + 1 row boundaries on the device: one call, and voxel_start is, as it stands, the
+room_start of the tiling (see grid_subsample_rooms).
 """
 import math
 
@@ -90,15 +95,8 @@ class GridSubsample:
         return out
 
 
-def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, max_voxels=None, out=None):
-    """One cloud -> GridSubsample, by the eight steps of include/conv3p.h (conv3p_grid_subsample_f32).
-
-    data float32 (N, K >= 3), xyz first; labels (N) uint8 / int32 / int64 or None.  voxel, the lattice step, is taken
-    as float32.  mode "mean": every channel averaged over the voxel's members in ascending row, the label their majority
-    among 0 <= l < num_class (num_class in [1, 128], required with labels); mode "center": the member nearest the
-    voxel's centre, copied with its label (num_class is not used).  max_voxels=None means N, which never cuts.  out: a
-    GridSubsample of an earlier call with the same shapes, written into.  Nothing is synchronised on; stats[7] != 0
-    reports a lattice of more than 2^20 cells along an axis or 2^40 in all (nothing emitted, inverse all -1)."""
+def _check_arguments(data, labels, voxel, mode, num_class):
+    """The argument checks grid_subsample and grid_subsample_rooms share, in grid_subsample's order -> voxel as float32."""
     _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
              "data must be a float32 (N, K >= 3) tensor, xyz first")
     dev = data.device
@@ -110,7 +108,6 @@ def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, m
                  "labels must be a contiguous (N,) tensor on the data's device")
     _require(isinstance(voxel, (int, float)) and not isinstance(voxel, bool) and math.isfinite(voxel)
              and math.isfinite(float(np.float32(voxel))) and float(np.float32(voxel)) > 0, "voxel must be finite and positive")
-    voxel = float(np.float32(voxel))
     _require(isinstance(mode, str) and mode in _MODES, "mode must be \"mean\" or \"center\"")
     if labels is not None and mode == "mean":
         _require(isinstance(num_class, int) and not isinstance(num_class, bool) and 1 <= num_class <= _lib.GRID_MAX_CLASS,
@@ -120,6 +117,137 @@ def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, m
                  "num_class must be an integer or None")
     _require(N <= _lib.GRID_MAX_ROWS, "at most 2^24 rows")
     _require(K <= 65536, "at most 65536 channels")
+    return float(np.float32(voxel))
+
+
+class GridRoomSubsample(GridSubsample):
+    """The outputs of grid_subsample_rooms: everything a GridSubsample has -- inverse holds GLOBAL voxel numbers, voxel_row
+    GLOBAL rows, voxel_cell the cell in the room's own lattice -- and voxel_room int32 (max_voxels), the room of every
+    voxel (-1 past the emitted ones), voxel_start int32 (R + 1), the prefix of the emitted voxels per room
+    (voxel_start[R] = stats[0]), and room_stats int32 (R, 8), the single-cloud stats of every room.  stats int32 (8) =
+    {emitted voxels, occupied voxels, R, rooms with an emitted voxel, rooms with an error of their own, non-finite rows
+    inside the rooms, largest member count, error bits: 1 a room's lattice too large, 2 room_start malformed, 4 too
+    many cells in all}.  project is GridSubsample's: one call serves every room."""
+
+    def __init__(self, num_rows, num_rooms, max_voxels, K, with_labels, device, workspace_bytes=0):
+        GridSubsample.__init__(self, num_rows, max_voxels, K, with_labels, device, workspace_bytes)
+        R = int(num_rooms)
+        self.shape = self.shape + (R,)
+        self.voxel_room = torch.empty((int(max_voxels),), dtype=torch.int32, device=device)
+        self.voxel_start = torch.zeros((R + 1,), dtype=torch.int32, device=device)
+        self.room_stats = torch.zeros((R, 8), dtype=torch.int32, device=device)
+
+    def trim(self):
+        """Views of the first num_voxels() voxels, as a GridRoomSubsample (inverse, stats, voxel_start and room_stats
+        shared)."""
+        nv = self.num_voxels()
+        t = object.__new__(GridRoomSubsample)
+        t.shape = (self.shape[0], nv) + self.shape[2:]
+        t.data = self.data[:nv]
+        t.labels = self.labels[:nv] if self.labels is not None else None
+        t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[:nv], self.voxel_count[:nv], self.voxel_cell[:nv]
+        t.voxel_room = self.voxel_room[:nv]
+        t.inverse, t.stats, t.workspace = self.inverse, self.stats, None
+        t.voxel_start, t.room_stats = self.voxel_start, self.room_stats
+        return t
+
+    def room(self, r):
+        """Views of room r's emitted voxels, as a GridSubsample whose stats is room_stats[r].  Reads voxel_start on the
+        host (a synchronisation).  inverse is shared: it holds global voxel numbers, so subtract voxel_start[r] to index
+        the view."""
+        R = self.voxel_start.numel() - 1
+        _require(isinstance(r, int) and not isinstance(r, bool) and 0 <= r < R, "r must be a room number in [0, R)")
+        a, b = (int(x) for x in self.voxel_start[r:r + 2].cpu())
+        t = object.__new__(GridSubsample)
+        t.shape = (self.shape[0], b - a) + self.shape[2:4]
+        t.data = self.data[a:b]
+        t.labels = self.labels[a:b] if self.labels is not None else None
+        t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[a:b], self.voxel_count[a:b], self.voxel_cell[a:b]
+        t.inverse, t.stats, t.workspace = self.inverse, self.room_stats[r], None
+        return t
+
+
+def grid_subsample_rooms(data, room_start, labels=None, voxel=0.05, mode="mean", num_class=None, max_voxels=None, out=None):
+    """Many clouds in one call -> GridRoomSubsample (include/conv3p.h: conv3p_grid_subsample_rooms_f32).
+
+    data float32 (N, K >= 3) holds the rooms' rows one room after the other; room_start, a contiguous int32 (R + 1,)
+    tensor ON THE DEVICE, gives room r the rows [room_start[r], room_start[r + 1]); rows outside belong to no room
+    (inverse -1).  Every room is subsampled as grid_subsample does it on the room's own rows -- its own lo and lattice,
+    so rooms that overlap in space share no voxel -- and the voxels are numbered room after room; max_voxels (None:
+    N) cuts by that global number.  labels, voxel, mode, num_class as grid_subsample; at most 2^24 rows summed over the
+    rooms, at most 65536 rooms.  Nothing is synchronised on; stats[7] reports what only the device knows (bit 0 a
+    room's lattice past 2^20 cells along an axis or 2^40 in all: that room emits nothing; bit 1 room_start malformed;
+    bit 2 more than 2^40 cells over all rooms: nothing emitted).
+
+    voxel_start is the tiling's room_start, and the untrimmed data works, since rows from room_start[R] on belong to
+    no room -- a whole area from raw rows to blocks without a host read:
+
+        g = grid_subsample_rooms(area, room_start, area_labels, voxel=0.04, num_class=13)
+        sb = scene_blocks_rooms(g.data, g.voxel_start, g.labels, num_point=4096, stride=0.5, cover=True, min_points=1,
+                                max_blocks=...)
+        scores = SceneScores(g.shape[1], num_class, area.device)       # or g.num_voxels() rows, the one host read
+        ...
+        labels = g.project(scores.labels())                            # (N) int32 over the raw rows of every room
+    """
+    voxel = _check_arguments(data, labels, voxel, mode, num_class)
+    dev = data.device
+    N, K = data.shape
+    if max_voxels is None:
+        max_voxels = N
+    _require(isinstance(max_voxels, int) and not isinstance(max_voxels, bool) and 0 <= max_voxels < 2 ** 31,
+             "max_voxels must be a non-negative integer")
+    _require(isinstance(room_start, torch.Tensor) and room_start.dtype == torch.int32 and room_start.dim() == 1
+             and room_start.numel() >= 1 and room_start.is_contiguous() and room_start.device == dev,
+             "room_start must be a contiguous int32 (R + 1,) tensor on the data's device")
+    R = room_start.numel() - 1
+    _require(R <= _lib.GRID_ROOMS_MAX_ROOMS, "at most 65536 rooms")
+    if out is not None:
+        _require(isinstance(out, GridRoomSubsample) and out.shape == (N, max_voxels, K, labels is not None, R)
+                 and out.data.device == dev, "out was made for another shape")
+    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
+    lib = _lib.load()
+    need = lib.conv3p_grid_subsample_rooms_workspace_bytes(N, R, max_voxels)
+    if out is None:
+        out = GridRoomSubsample(N, R, max_voxels, K, labels is not None, dev, need)
+    elif need and (out.workspace is None or out.workspace.numel() < need):
+        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if N == 0 or R == 0 or max_voxels == 0:   # nothing is launched, so nothing is written
+        out.data.zero_()
+        out.inverse.fill_(-1)
+        out.voxel_row.fill_(-1)
+        out.voxel_count.zero_()
+        out.voxel_cell.fill_(-1)
+        out.voxel_room.fill_(-1)
+        out.voxel_start.zero_()
+        out.room_stats.zero_()
+        out.stats.zero_()
+        if out.labels is not None:
+            out.labels.fill_(-1)
+        return out
+    ws = out.workspace
+    with torch.cuda.device(dev):
+        _call(lib.conv3p_grid_subsample_rooms_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None,
+              room_start.data_ptr(), N, R, K, _LABEL_DTYPES[labels.dtype] if labels is not None else 0, voxel, _MODES[mode],
+              num_class if num_class is not None else 0, max_voxels, out.data.data_ptr(),
+              out.labels.data_ptr() if labels is not None else None, out.voxel_row.data_ptr(), out.voxel_count.data_ptr(),
+              out.voxel_cell.data_ptr(), out.voxel_room.data_ptr(), out.voxel_start.data_ptr(), out.inverse.data_ptr(),
+              out.room_stats.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, max_voxels=None, out=None):
+    """One cloud -> GridSubsample, by the eight steps of include/conv3p.h (conv3p_grid_subsample_f32).
+
+    data float32 (N, K >= 3), xyz first; labels (N) uint8 / int32 / int64 or None.  voxel, the lattice step, is taken
+    as float32.  mode "mean": every channel averaged over the voxel's members in ascending row, the label their majority
+    among 0 <= l < num_class (num_class in [1, 128], required with labels); mode "center": the member nearest the
+    voxel's centre, copied with its label (num_class is not used).  max_voxels=None means N, which never cuts.  out: a
+    GridSubsample of an earlier call with the same shapes, written into.  Nothing is synchronised on; stats[7] != 0
+    reports a lattice of more than 2^20 cells along an axis or 2^40 in all (nothing emitted, inverse all -1)."""
+    voxel = _check_arguments(data, labels, voxel, mode, num_class)
+    dev = data.device
+    N, K = data.shape
     if max_voxels is None:
         max_voxels = N
     _require(isinstance(max_voxels, int) and not isinstance(max_voxels, bool) and 0 <= max_voxels < 2 ** 31,
