@@ -735,6 +735,52 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   cell, global row) pairs, by the single call's sort, heads and mean kernels: 28 launches in mode 0, 27 in mode 1,
  *   fixed by mode alone whatever R, the rooms' sizes and the data; no float atomics; every output word is written once
  *   by a plain store; bitwise reproducible and independent of the launch geometry.
+ *
+ * conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64:  voxel SCORES interpolated onto every raw row from the
+ *   nearest voxels of the 3 x 3 x 3 cells around its own, with inverse-distance weights
+ *   (pointwise_amd/csrc/conv3p_grid_interp.hpp; tests/grid_interp_ref.py restates it in numpy).  conv3p_grid_project_labels
+ *   gives a row the label of its own voxel and of no other: a voxel nobody voted for leaves its rows at -1, and class
+ *   boundaries follow the lattice.  This is the other ending, for the single-cloud and the many-clouds result alike.
+ *
+ *   The neighbour table, neigh int32 (max_voxels, 27), from voxel_cell (max_voxels, 3) and the subsampling's stats:
+ *    N1. nv = stats[0], the emitted voxels, read ON THE DEVICE (held to [0, max_voxels]); there is no host read.
+ *    N2. For an emitted voxel v with cell (i, j, l) and t = (dx+1)*9 + (dy+1)*3 + (dz+1), dx, dy, dz in {-1, 0, 1}:
+ *        neigh[v][t] = the number of the emitted voxel whose cell is (i+dx, j+dy, l+dz), -1 if there is none (the cell
+ *        is not occupied, lies outside the lattice, or its voxel was cut by max_voxels).  neigh[v][13] = v.
+ *    N3. Rows nv..max_voxels-1 are all -1.
+ *    N4. With voxel_room (max_voxels) and voxel_start (num_rooms + 1) of conv3p_grid_subsample_rooms_f32 -- both or
+ *        neither -- only voxels of the same room are neighbours: cells are compared in the room's own lattice and the
+ *        search runs over [voxel_start[r], voxel_start[r+1]), r = voxel_room[v].  Rooms that overlap in space share
+ *        nothing.
+ *   Status: max_voxels < 0, num_rooms < 0, one of voxel_room / voxel_start without the other:
+ *   CONV3P_ERR_INVALID_ARGUMENT; max_voxels == 0: CONV3P_OK, nothing launched; voxel_cell, grid_stats or neigh NULL:
+ *   CONV3P_ERR_INVALID_ARGUMENT; num_rooms > 65536: CONV3P_ERR_UNSUPPORTED.  One launch: a lane per (voxel, (dx, dy)),
+ *   one binary search for (i+dx, j+dy, l-1) in the ascending cells, then up to three consecutive entries.
+ *
+ *   The interpolation.  data (N, K) is the raw cloud the subsampling was given, inverse (N) its voxel per row;
+ *   voxel_data (>= M, voxel_K) the voxels' rows (xyz first: the mean, or the centre member), neigh (>= M, 27);
+ *   voxel_scores (M, C), float32 or the int64 fixed-point sums of conv3p_scene_vote_scores_f32; valid_labels int32 (M) or
+ *   NULL; 1 <= k <= 8; 1 <= C <= 128.  Per raw row i, with p = data[i][0..2] and v0 = inverse[i]:
+ *    1. v0 < 0 or v0 >= M: label -1, score row all 0; counted in stats[1] ("no voxel").
+ *    2. The candidates are the u = neigh[v0][t] with u >= 0, u < M and, with valid_labels, valid_labels[u] >= 0.
+ *       q = voxel_data[u][0..2]; d2 = ((p_x-q_x)^2 + (p_y-q_y)^2) + (p_z-q_z)^2, every operation a single float32 one,
+ *       uncontracted, in that order.  A candidate whose d2 is NaN or inf is dropped.
+ *    3. The min(k, candidates) smallest by the total order (d2, u) are kept, ranked j = 0, 1, ... in that order.
+ *    4. None left: label -1, score row 0; counted in stats[2] ("no candidate").
+ *    5. Otherwise, counted in stats[0]:  w_j = 1.0f / fmaxf(d2_j, 1e-10f), a correctly rounded division;
+ *       W = ((w_0 + w_1) + w_2) + ...; for every class c:  out[c] = (((w_0 s_0c + w_1 s_1c) + w_2 s_2c) + ...) / W,
+ *       products and sums rounded separately.  s_jc = voxel_scores[u_j][c] (_f32), or (float)voxel_scores[u_j][c] *
+ *       2^-30 (_i64: the conversion rounds to nearest even, the scaling is exact).  The label is class 0 unless a later
+ *       class is strictly greater than the best so far: the lowest class wins a tie and a NaN never wins.
+ *   Scores are NOT normalised per voxel: a voxel that overlapping blocks voted for twice weighs twice, as it does in
+ *   conv3p_scene_score_labels.  out_labels int32 (N); out_scores float32 (N, C) or NULL; stats int64 (3) = {rows
+ *   interpolated, rows without a voxel, rows without a candidate}, exact, overwritten by every call.
+ *   Status, in this order, all before any launch: N < 0, M < 0, K < 3, voxel_K < 3, C outside [1, 128], k outside [1, 8]:
+ *   CONV3P_ERR_INVALID_ARGUMENT; stats NULL; data, inverse or out_labels NULL with N > 0; voxel_data, neigh or voxel_scores
+ *   NULL with N > 0 and M > 0: CONV3P_ERR_INVALID_ARGUMENT; N or M > 2^31 - 1: CONV3P_ERR_UNSUPPORTED.  N == 0 and M == 0
+ *   are valid: with M == 0 every row has "no voxel".  One kernel launch behind a 24-byte memset of stats; 16 lanes a row;
+ *   the only atomics are the integer adds of the three counts; no float atomics; bitwise reproducible and independent of
+ *   the launch geometry.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_GRID_MEAN 0
 #define CONV3P_GRID_CENTER 1
@@ -752,6 +798,16 @@ int conv3p_grid_subsample_rooms_f32(const float *data, const void *labels, const
                                     int32_t *voxel_cell, int32_t *voxel_room, int32_t *voxel_start, int32_t *inverse,
                                     int32_t *room_stats, int32_t *stats, void *workspace, size_t workspace_bytes,
                                     void *stream);
+int conv3p_grid_neighbors(const int32_t *voxel_cell, const int32_t *voxel_room, const int32_t *voxel_start,
+                          const int32_t *grid_stats, int max_voxels, int64_t num_rooms, int32_t *neigh, void *stream);
+int conv3p_grid_interpolate_f32(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                int voxel_K, const int32_t *neigh, const float *voxel_scores, int64_t M, int C,
+                                const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
+                                void *stream);
+int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                int voxel_K, const int32_t *neigh, const int64_t *voxel_scores, int64_t M, int C,
+                                const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
+                                void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

@@ -153,6 +153,11 @@ SYMBOLS = {
     "conv3p_grid_subsample_rooms_workspace_bytes": (_sz, [ctypes.c_int64, ctypes.c_int64, _i]),
     "conv3p_grid_subsample_rooms_f32": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, ctypes.c_float, _i, _i, _i,
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_grid_neighbors": (_i, [_vp, _vp, _vp, _vp, _i, ctypes.c_int64, _vp, _vp]),
+    "conv3p_grid_interpolate_f32": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _i, _vp,
+                                         _vp, _vp, _vp]),
+    "conv3p_grid_interpolate_i64": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _i, _vp,
+                                         _vp, _vp, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

@@ -30,6 +30,7 @@
 #include "conv3p_scene_rooms.hpp"
 #include "conv3p_grid.hpp"
 #include "conv3p_grid_rooms.hpp"
+#include "conv3p_grid_interp.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3937,6 +3938,63 @@ int conv3p_grid_project_labels(const int32_t *voxel_labels, const int32_t *inver
                        dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream), voxel_labels, inverse, (long long)N,
                        (long long)M, out);
     return hip_ok();
+}
+
+int conv3p_grid_neighbors(const int32_t *voxel_cell, const int32_t *voxel_room, const int32_t *voxel_start,
+                          const int32_t *grid_stats, int max_voxels, int64_t num_rooms, int32_t *neigh, void *stream)
+{
+    if (max_voxels < 0 || num_rooms < 0) return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((voxel_room == nullptr) != (voxel_start == nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (max_voxels == 0) return CONV3P_OK;
+    if (!voxel_cell || !grid_stats || !neigh) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (num_rooms > kGridRoomsMaxRooms) return CONV3P_ERR_UNSUPPORTED;
+    const size_t work = ((size_t)max_voxels * 9 + kSceneThreads - 1) / kSceneThreads;
+    hipLaunchKernelGGL(grid_neighbors_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
+                       dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream), voxel_cell, voxel_room, voxel_start,
+                       grid_stats, max_voxels, (int)num_rooms, neigh);
+    return hip_ok();
+}
+
+extern "C++" {
+namespace {
+template <typename S>
+int grid_interpolate(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data, int voxel_K,
+                     const int32_t *neigh, const S *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k,
+                     int32_t *out_labels, float *out_scores, int64_t *stats, void *stream)
+{
+    if (N < 0 || M < 0 || K < 3 || voxel_K < 3 || C < 1 || C > kInterpMaxClass || k < 1 || k > kInterpMaxK)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!stats || (N > 0 && (!data || !inverse || !out_labels)) || (N > 0 && M > 0 && (!voxel_data || !neigh || !voxel_scores)))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX || M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;   // inverse is int32
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(stats, 0, 3 * sizeof(int64_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
+    if (N == 0) return hip_ok();
+    const size_t work = ((size_t)N + kInterpRows - 1) / kInterpRows;
+    hipLaunchKernelGGL((grid_interpolate_kernel<S>), dim3((unsigned)(work < (size_t)kInterpMaxGrid ? work : (size_t)kInterpMaxGrid)),
+                       dim3(kInterpThreads), 0, s, data, (long long)N, K, inverse, voxel_data, voxel_K, neigh, voxel_scores,
+                       (int)M, C, valid_labels, k, out_labels, out_scores, reinterpret_cast<unsigned long long *>(stats));
+    return hip_ok();
+}
+}  // namespace
+}  // extern "C++": a template
+
+int conv3p_grid_interpolate_f32(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                int voxel_K, const int32_t *neigh, const float *voxel_scores, int64_t M, int C,
+                                const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
+                                void *stream)
+{
+    return grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_scores, M, C, valid_labels, k, out_labels,
+                            out_scores, stats, stream);
+}
+
+int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                int voxel_K, const int32_t *neigh, const int64_t *voxel_scores, int64_t M, int C,
+                                const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
+                                void *stream)
+{
+    return grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, reinterpret_cast<const long long *>(voxel_scores),
+                            M, C, valid_labels, k, out_labels, out_scores, stats, stream);
 }
 
 namespace {

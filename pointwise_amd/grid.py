@@ -1,5 +1,6 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
-conv3p_grid_subsample_f32, conv3p_grid_project_labels; kernels in csrc/conv3p_grid.hpp).
+conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64;
+kernels in csrc/conv3p_grid.hpp and csrc/conv3p_grid_interp.hpp).
 
 A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
 first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
@@ -10,6 +11,9 @@ tests/grid_ref.py restates it in numpy.
     grid_subsample   one cloud (N, K) -> GridSubsample: data (max_voxels, K), labels, inverse (the voxel of every raw
                      row), voxel_row, voxel_count, voxel_cell, stats
     GridSubsample.project   voxel labels (num_voxels) -> a label per raw row (N) int32, -1 for a row without a voxel
+    GridSubsample.neighbors     -> int32 (max_voxels, 27), the voxels of the 3 x 3 x 3 cells around every voxel
+    GridSubsample.interpolate   voxel scores (num_voxels, C) -> a label (and a score row) per raw row, blended from the
+                     k nearest voxels around the row with inverse-distance weights (tests/grid_interp_ref.py)
     grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
                      voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
@@ -23,7 +27,10 @@ From a raw room to the model and back:
     pv = BatchProvider(sb.data, sb.index, batch_size, training=False, sort_cloud=True)   # index: the voxel of every row
     scores = SceneScores(g.num_voxels(), num_class, room.device)
     per batch:  points, inp, idx = pv.get_batch_point_cloud();  scores.add(model(points, inp), idx)
-    labels = g.project(scores.labels())                              # (N) int32 over the raw rows
+    labels = g.project(scores.labels())                              # (N) int32 over the raw rows: its voxel's label
+  or
+    labels = g.interpolate(room, scores, k=3)                        # the 3 nearest voted voxels' scores, blended: rows
+                                                                     # of an unvoted voxel are labelled from its neighbours
 
 A whole area or split, room_start its R + 1 row boundaries on the device: one call, and voxel_start is, as it stands, the
 room_start of the tiling (see grid_subsample_rooms).
@@ -72,6 +79,8 @@ class GridSubsample:
         t.labels = self.labels[:nv] if self.labels is not None else None
         t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[:nv], self.voxel_count[:nv], self.voxel_cell[:nv]
         t.inverse, t.stats, t.workspace = self.inverse, self.stats, None
+        if getattr(self, "_neigh", None) is not None:
+            t._neigh = self._neigh[:nv]
         return t
 
     def project(self, voxel_labels, out=None):
@@ -93,6 +102,96 @@ class GridSubsample:
             _call(_lib.load().conv3p_grid_project_labels, voxel_labels.data_ptr() if M else None, self.inverse.data_ptr(), N,
                   M, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         return out
+
+    def neighbors(self):
+        """int32 (max_voxels, 27): neigh[v][(dx+1)*9 + (dy+1)*3 + (dz+1)] is the emitted voxel of the cell (i+dx, j+dy,
+        l+dz) of voxel v's cell (i, j, l), -1 if there is none; rows past the emitted voxels are -1.  Built on first use
+        (one launch, nothing synchronised on: the number of voxels is read on the device) and kept on the object."""
+        neigh = getattr(self, "_neigh", None)
+        if neigh is not None:
+            return neigh
+        dev = self.voxel_cell.device
+        M = self.voxel_cell.shape[0]
+        room, start = getattr(self, "voxel_room", None), getattr(self, "voxel_start", None)
+        for name, t, shape in (("voxel_cell", self.voxel_cell, (M, 3)), ("stats", self.stats, (8,))) + (
+                (("voxel_room", room, (M,)), ("voxel_start", start, None)) if room is not None else ()):
+            _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()
+                     and (shape is None or tuple(t.shape) == shape),
+                     "%s must be a contiguous int32 tensor of the subsampling's shape on its device" % name)
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        neigh = torch.empty((M, 27), dtype=torch.int32, device=dev)
+        if M:
+            with torch.cuda.device(dev):
+                _call(_lib.load().conv3p_grid_neighbors, self.voxel_cell.data_ptr(),
+                      room.data_ptr() if room is not None else None, start.data_ptr() if room is not None else None,
+                      self.stats.data_ptr(), M, start.numel() - 1 if room is not None else 0, neigh.data_ptr(),
+                      torch.cuda.current_stream(dev).cuda_stream)
+        self._neigh = neigh
+        return neigh
+
+    def interpolate(self, data, voxel_scores, k=3, valid_labels=None, return_scores=False, out=None):
+        """Scores per voxel -> a label per raw row (N) int32, or (labels, scores float32 (N, C)) with return_scores: the
+        scores of the k nearest voxels among the 3 x 3 x 3 cells around the row's own, blended with weights 1 / max(d^2,
+        1e-10), d from the raw row to the voxel's representative (include/conv3p.h: conv3p_grid_interpolate_f32, rules 1-5).
+
+        data is the raw (N, K) tensor the subsampling was given.  voxel_scores: a contiguous float32 (M, C) tensor, C <=
+        128 (valid_labels=None: every voxel is a candidate), or a SceneScores, whose exact int64 sums are read as they
+        are and whose labels() are the default valid_labels, so a voxel nobody voted for is no candidate.  valid_labels
+        int32 (M): voxels with a negative entry are no candidates.  -1 and a zero score row for a row without a voxel or
+        without a candidate; interp_stats int64 (3) on the device = {rows interpolated, without a voxel, without a
+        candidate}.  out: the labels tensor, or (labels, scores) with return_scores.  One kernel launch behind a 24-byte
+        memset of interp_stats (and the neighbour table's launch on first use), nothing synchronised on."""
+        from .scene import SceneScores
+        dev = self.inverse.device
+        N = self.inverse.numel()
+        _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
+                 "data must be a float32 (N, K >= 3) tensor, xyz first")
+        _require(data.is_contiguous() and data.device == dev, "data must be contiguous and on the cloud's device")
+        _require(data.shape[0] == N, "data must have the rows the subsampling was given (inverse has %d)" % N)
+        _require(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= 8, "k must be an integer in [1, 8]")
+        if isinstance(voxel_scores, SceneScores):
+            _require(voxel_scores.device == dev, "voxel_scores must live on the cloud's device")
+            scores, entry = voxel_scores.scores, "conv3p_grid_interpolate_i64"
+        else:
+            _require(isinstance(voxel_scores, torch.Tensor) and voxel_scores.dtype == torch.float32 and voxel_scores.dim() == 2
+                     and voxel_scores.is_contiguous() and voxel_scores.device == dev,
+                     "voxel_scores must be a contiguous float32 (M, C) tensor on the cloud's device, or a SceneScores")
+            scores, entry = voxel_scores, "conv3p_grid_interpolate_f32"
+        M, C = scores.shape
+        _require(1 <= C <= 128, "at most 128 classes (and at least one)")
+        _require(M <= self.data.shape[0], "voxel_scores has more rows than the subsampling has voxels")
+        if valid_labels is not None:
+            _require(isinstance(valid_labels, torch.Tensor) and valid_labels.dtype == torch.int32 and valid_labels.device == dev
+                     and tuple(valid_labels.shape) == (M,) and valid_labels.is_contiguous(),
+                     "valid_labels must be a contiguous int32 (M,) tensor on the cloud's device")
+        _require(out is None or not return_scores or (isinstance(out, (tuple, list)) and len(out) == 2),
+                 "out must be (labels, scores) with return_scores")
+        lab, sc = (out if return_scores else (out, None)) if out is not None else (None, None)
+        if out is not None:
+            _require(isinstance(lab, torch.Tensor) and lab.dtype == torch.int32 and tuple(lab.shape) == (N,)
+                     and lab.device == dev and lab.is_contiguous(),
+                     "out labels must be a contiguous int32 (N,) tensor on the cloud's device")
+            _require(not return_scores or (isinstance(sc, torch.Tensor) and sc.dtype == torch.float32
+                                           and tuple(sc.shape) == (N, C) and sc.device == dev and sc.is_contiguous()),
+                     "out scores must be a contiguous float32 (N, C) tensor on the cloud's device")
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        if valid_labels is None and isinstance(voxel_scores, SceneScores):
+            valid_labels = voxel_scores.labels()
+        if lab is None:
+            lab = torch.empty((N,), dtype=torch.int32, device=dev)
+        if return_scores and sc is None:
+            sc = torch.empty((N, C), dtype=torch.float32, device=dev)
+        if getattr(self, "interp_stats", None) is None:
+            self.interp_stats = torch.zeros((3,), dtype=torch.int64, device=dev)
+        neigh = self.neighbors()
+        with torch.cuda.device(dev):
+            _call(getattr(_lib.load(), entry), data.data_ptr() if N else None, N, data.shape[1],
+                  self.inverse.data_ptr() if N else None, self.data.data_ptr() if M else None, self.data.shape[1],
+                  neigh.data_ptr() if M else None, scores.data_ptr() if M else None, M, C,
+                  valid_labels.data_ptr() if valid_labels is not None and M else None, k, lab.data_ptr() if N else None,
+                  sc.data_ptr() if sc is not None and N else None, self.interp_stats.data_ptr(),
+                  torch.cuda.current_stream(dev).cuda_stream)
+        return (lab, sc) if return_scores else lab
 
 
 def _check_arguments(data, labels, voxel, mode, num_class):
@@ -149,6 +248,8 @@ class GridRoomSubsample(GridSubsample):
         t.voxel_room = self.voxel_room[:nv]
         t.inverse, t.stats, t.workspace = self.inverse, self.stats, None
         t.voxel_start, t.room_stats = self.voxel_start, self.room_stats
+        if getattr(self, "_neigh", None) is not None:
+            t._neigh = self._neigh[:nv]
         return t
 
     def room(self, r):
@@ -211,6 +312,7 @@ def grid_subsample_rooms(data, room_start, labels=None, voxel=0.05, mode="mean",
         out = GridRoomSubsample(N, R, max_voxels, K, labels is not None, dev, need)
     elif need and (out.workspace is None or out.workspace.numel() < need):
         out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    out._neigh = None                        # the neighbour table of an earlier call's voxels
     if N == 0 or R == 0 or max_voxels == 0:   # nothing is launched, so nothing is written
         out.data.zero_()
         out.inverse.fill_(-1)
@@ -262,6 +364,7 @@ def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, m
         out = GridSubsample(N, max_voxels, K, labels is not None, dev, need)
     elif need and (out.workspace is None or out.workspace.numel() < need):
         out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    out._neigh = None                        # the neighbour table of an earlier call's voxels
     if N == 0 or max_voxels == 0:            # nothing is launched, so nothing is written
         out.data.zero_()
         out.inverse.fill_(-1)
