@@ -781,6 +781,44 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   are valid: with M == 0 every row has "no voxel".  One kernel launch behind a 24-byte memset of stats; 16 lanes a row;
  *   the only atomics are the integer adds of the three counts; no float atomics; bitwise reproducible and independent of
  *   the launch geometry.
+ *
+ * conv3p_grid_normals_f32:  a surface normal and a curvature per voxel, from the representatives of the 3 x 3 x 3 cells
+ *   around it (pointwise_amd/csrc/conv3p_grid_normals.hpp; tests/grid_normals_ref.py restates it in numpy).  A raw scan
+ *   carries no normals and normals averaged over a voxel are no unit vectors; this is the estimate a model trained on
+ *   files with normals is fed.  voxel_data (M, K) with row stride K, xyz first; neigh (M, 27) as conv3p_grid_neighbors
+ *   writes it; grid_stats the subsampling's stats, of which grid_stats[0] = nv is read ON THE DEVICE; voxel_room int32 (M)
+ *   or NULL; viewpoint float32 (V, 3) ON THE DEVICE or NULL (V is then not read): V = 1 one point for all voxels, V = R
+ *   one per room, which needs voxel_room; 3 <= min_neighbors <= 27.  Let p_v = voxel_data[v][0..2] and ne = min(max(nv, 0),
+ *   M).  Every float32 step below is one separately rounded operation (the library is built with -ffp-contract=off):
+ *    R1. v >= ne (filler): normal 0, curvature 0, samples 0, flags -1, moments 0.
+ *    R2. For t = 0 .. 26 ascending, u = neigh[v][t] is a SAMPLE when 0 <= u < ne and all three of p_u are finite (t = 13
+ *        is v itself).  samples[v] = n, the number of samples; if p_v is not finite, n = 0.
+ *    R3. q_u = p_u - p_v per component (centred on the voxel's own representative: the size of the room's coordinates does
+ *        not enter).  m = the chain of float32 additions of q_u in ascending t, from 0, divided by float(n).  e_u = q_u -
+ *        m.  C_xx, C_xy, C_xz, C_yy, C_yz, C_zz are each the chain, in ascending t from 0, of the rounded products e_a *
+ *        e_b, divided by float(n).  moments[v] = {m_x, m_y, m_z, C_xx, C_xy, C_xz, C_yy, C_yz, C_zz}; all 0 for n = 0.
+ *        samples and moments are defined bit for bit.
+ *    R4. n < min_neighbors: flags 1.  Otherwise any moment non-finite or (C_xx + C_yy) + C_zz <= 0: flags 2.  Otherwise
+ *        flags 0.  For flags != 0 normal and curvature are 0.  flags are bit for bit: they depend on R2 and R3 alone.
+ *    R5. flags 0: l0 <= l1 <= l2 the eigenvalues of the symmetric C, n^ a unit eigenvector of l0, curvature = l0 / (l0 +
+ *        l1 + l2) held to [0, 1/3].  These two are defined TO A TOLERANCE: against the float64 eigen-decomposition of the
+ *        float32 moments, with u = 2^-24, |n^ x n_ref| <= 64 u l2 / (l1 - l0) up to sign where l1 - l0 >= 1e-3 l2,
+ *        | |n^| - 1 | <= 1e-6, and the curvature within 64 u.  The solver is a cyclic Jacobi iteration of six sweeps in
+ *        float64 on the float32 moments, every rotation taken: deterministic, two calls give the same bits.
+ *    R6. Orientation, an exact rule on the float32 n^ about to be stored.  With a viewpoint, w = viewpoint[0], or
+ *        viewpoint[voxel_room[v]] when V > 1 (a voxel whose room is outside [0, V) has no viewpoint):
+ *        s = ((w_x - p_x) n_x + (w_y - p_y) n_y) + (w_z - p_z) n_z, each difference, product and addition rounded;
+ *        s < 0 stores -n^.  Without a viewpoint, or when s == 0 or s is not finite: the component of largest magnitude
+ *        is made positive, the lowest axis of a tie.  Negation is exact, so the rule holds on the stored vector.
+ *   Outputs: normals float32 (M, 3), curvature float32 (M), samples int32 (M), flags int32 (M), moments float32 (M, 9) or
+ *   NULL, normal_stats int32 (4) = {voxels with a normal, too few samples, degenerate, filler}, overwritten by every call.
+ *   Status, in this order, all before any launch: M < 0, K < 3, min_neighbors outside [3, 27]: CONV3P_ERR_INVALID_ARGUMENT;
+ *   viewpoint given with V < 1, or with V != 1 and voxel_room NULL: CONV3P_ERR_INVALID_ARGUMENT; M == 0: CONV3P_OK, nothing
+ *   launched and nothing written; voxel_data, neigh, grid_stats, normals, curvature, samples, flags or normal_stats NULL:
+ *   CONV3P_ERR_INVALID_ARGUMENT; M > 2^31 - 1, or V with a viewpoint: CONV3P_ERR_UNSUPPORTED.  One kernel launch behind a
+ *   16-byte memset of normal_stats; a thread per voxel; nothing synchronised on; the only atomics are the integer adds
+ *   of the four counts; no float atomics; every output word written once; bitwise reproducible and independent of the
+ *   launch geometry.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_GRID_MEAN 0
 #define CONV3P_GRID_CENTER 1
@@ -808,6 +846,10 @@ int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32
                                 int voxel_K, const int32_t *neigh, const int64_t *voxel_scores, int64_t M, int C,
                                 const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
                                 void *stream);
+int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh, const int32_t *grid_stats,
+                            const int32_t *voxel_room, const float *viewpoint, int64_t V, int64_t M, int min_neighbors,
+                            float *normals, float *curvature, int32_t *samples, int32_t *flags, float *moments,
+                            int32_t *normal_stats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

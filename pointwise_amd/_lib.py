@@ -158,6 +158,8 @@ SYMBOLS = {
                                          _vp, _vp, _vp]),
     "conv3p_grid_interpolate_i64": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _i, _vp,
                                          _vp, _vp, _vp]),
+    "conv3p_grid_normals_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

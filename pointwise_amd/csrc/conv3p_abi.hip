@@ -31,6 +31,7 @@
 #include "conv3p_grid.hpp"
 #include "conv3p_grid_rooms.hpp"
 #include "conv3p_grid_interp.hpp"
+#include "conv3p_grid_normals.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -3995,6 +3996,26 @@ int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32
 {
     return grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, reinterpret_cast<const long long *>(voxel_scores),
                             M, C, valid_labels, k, out_labels, out_scores, stats, stream);
+}
+
+int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh, const int32_t *grid_stats,
+                            const int32_t *voxel_room, const float *viewpoint, int64_t V, int64_t M, int min_neighbors,
+                            float *normals, float *curvature, int32_t *samples, int32_t *flags, float *moments,
+                            int32_t *normal_stats, void *stream)
+{
+    if (M < 0 || K < 3 || min_neighbors < kNormalsMinNeighbors || min_neighbors > kInterpNeigh) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (viewpoint && (V < 1 || (V != 1 && !voxel_room))) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!voxel_data || !neigh || !grid_stats || !normals || !curvature || !samples || !flags || !normal_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX || (viewpoint && V > (int64_t)INT32_MAX)) return CONV3P_ERR_UNSUPPORTED;   // neigh is int32
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(normal_stats, 0, 4 * sizeof(int32_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
+    const size_t work = ((size_t)M + kNormalsThreads - 1) / kNormalsThreads;
+    hipLaunchKernelGGL(grid_normals_kernel, dim3((unsigned)(work < (size_t)kNormalsMaxGrid ? work : (size_t)kNormalsMaxGrid)),
+                       dim3(kNormalsThreads), 0, s, voxel_data, K, neigh, grid_stats, voxel_room, viewpoint,
+                       viewpoint ? (int)V : 0, (int)M, min_neighbors, normals, curvature, samples, flags, moments, normal_stats);
+    return hip_ok();
 }
 
 namespace {

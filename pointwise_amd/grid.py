@@ -1,6 +1,6 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
-conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64;
-kernels in csrc/conv3p_grid.hpp and csrc/conv3p_grid_interp.hpp).
+conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64,
+conv3p_grid_normals_f32; kernels in csrc/conv3p_grid.hpp, csrc/conv3p_grid_interp.hpp and csrc/conv3p_grid_normals.hpp).
 
 A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
 first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
@@ -14,6 +14,9 @@ tests/grid_ref.py restates it in numpy.
     GridSubsample.neighbors     -> int32 (max_voxels, 27), the voxels of the 3 x 3 x 3 cells around every voxel
     GridSubsample.interpolate   voxel scores (num_voxels, C) -> a label (and a score row) per raw row, blended from the
                      k nearest voxels around the row with inverse-distance weights (tests/grid_interp_ref.py)
+    GridSubsample.normals       -> GridNormals: a unit normal, a curvature, the sample count and a flag per voxel, from the
+                     representatives of the 3 x 3 x 3 cells around it (tests/grid_normals_ref.py)
+    GridSubsample.with_normals  data and those normals side by side, (M, K + 3): what scene_blocks takes in place of data
     grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
                      voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
@@ -31,6 +34,14 @@ From a raw room to the model and back:
   or
     labels = g.interpolate(room, scores, k=3)                        # the 3 nearest voted voxels' scores, blended: rows
                                                                      # of an unvoted voxel are labelled from its neighbours
+
+A model trained on files with normals, fed from a raw scan that has none (xyz + rgb in, blocks of 12 channels out:
+xyz, rgb, normal, room-normalised xyz):
+
+    g = grid_subsample(room, room_labels, voxel=0.04, num_class=13).trim()
+    nrm = g.normals(viewpoint=(x, y, z))                             # the scanner's position; None: largest component positive
+    sb = scene_blocks(g.with_normals(nrm), g.labels, num_point=4096, stride=0.5, cover=True, min_points=1).trim()
+    ... as above; the many-clouds result takes a (R, 3) tensor of viewpoints, one per room
 
 A whole area or split, room_start its R + 1 row boundaries on the device: one call, and voxel_start is, as it stands, the
 room_start of the tiling (see grid_subsample_rooms).
@@ -192,6 +203,105 @@ class GridSubsample:
                   sc.data_ptr() if sc is not None and N else None, self.interp_stats.data_ptr(),
                   torch.cuda.current_stream(dev).cuda_stream)
         return (lab, sc) if return_scores else lab
+
+    def normals(self, viewpoint=None, min_neighbors=6, return_moments=False, out=None):
+        """A surface normal and a curvature per voxel -> GridNormals, from the representatives (data[:, :3]) of the 3 x 3
+        x 3 cells around every voxel: the moments of the neighbours about the voxel's own representative, the eigenvector
+        of the covariance's smallest eigenvalue, curvature = l0 / (l0 + l1 + l2) (include/conv3p.h:
+        conv3p_grid_normals_f32, rules R1-R6; tests/grid_normals_ref.py).
+
+        viewpoint: None -- the normal's component of largest magnitude is made positive; a sequence of three finite
+        numbers (uploaded as a (1, 3) tensor) or a contiguous float32 (1, 3) tensor on the device -- every normal turned
+        towards that point; on a GridRoomSubsample also a contiguous float32 (R, 3) tensor on the device, a point per
+        room.  A voxel with fewer than min_neighbors (3 .. 27) occupied cells around it, itself included, gets flags 1 and
+        a zero normal; flags 2 marks degenerate moments, -1 the filler rows past the emitted voxels.  return_moments: also
+        the float32 (M, 9) moments {m, C_xx, C_xy, C_xz, C_yy, C_yz, C_zz}.  out: a GridNormals of an earlier call with
+        the same shapes.  Works on a trimmed object and on many clouds as they stand (the table is per room).  One kernel
+        launch behind a 16-byte memset (and the neighbour table's launch on first use), nothing synchronised on."""
+        dev = self.data.device
+        M, K = self.data.shape
+        rooms = getattr(self, "voxel_room", None)
+        _require(isinstance(min_neighbors, int) and not isinstance(min_neighbors, bool) and 3 <= min_neighbors <= 27,
+                 "min_neighbors must be an integer in [3, 27]")
+        _require(isinstance(return_moments, bool), "return_moments must be a bool")
+        upload = None
+        if viewpoint is not None and not isinstance(viewpoint, torch.Tensor):
+            try:
+                upload = [float(x) for x in viewpoint]
+            except (TypeError, ValueError):
+                upload = None
+            _require(upload is not None and len(upload) == 3 and all(math.isfinite(x) for x in upload)
+                     and all(abs(x) <= float(np.finfo(np.float32).max) for x in upload),
+                     "viewpoint must be None, three finite numbers, or a float32 (1, 3) or (R, 3) tensor on the cloud's device")
+        elif viewpoint is not None:
+            _require(viewpoint.dtype == torch.float32 and viewpoint.dim() == 2 and viewpoint.shape[1] == 3
+                     and viewpoint.shape[0] >= 1 and viewpoint.is_contiguous() and viewpoint.device == dev,
+                     "viewpoint must be None, three finite numbers, or a float32 (1, 3) or (R, 3) tensor on the cloud's device")
+            if viewpoint.shape[0] != 1:
+                _require(rooms is not None, "a viewpoint per room needs a GridRoomSubsample")
+                _require(viewpoint.shape[0] == self.voxel_start.numel() - 1,
+                         "viewpoint must have one row, or one per room (%d)" % (self.voxel_start.numel() - 1))
+        _require(isinstance(self.data, torch.Tensor) and self.data.dtype == torch.float32 and self.data.is_contiguous()
+                 and K >= 3, "data must be a contiguous float32 (M, K >= 3) tensor")
+        if rooms is not None:
+            _require(isinstance(rooms, torch.Tensor) and rooms.dtype == torch.int32 and tuple(rooms.shape) == (M,)
+                     and rooms.device == dev and rooms.is_contiguous(),
+                     "voxel_room must be a contiguous int32 (M,) tensor on the cloud's device")
+        if out is not None:
+            _require(isinstance(out, GridNormals) and out.shape == (M, return_moments) and out.normals.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        if out is None:
+            out = GridNormals(M, return_moments, dev)
+        if M == 0:
+            out.stats.zero_()
+            return out
+        if upload is not None:
+            viewpoint = torch.tensor([upload], dtype=torch.float32, device=dev)
+        neigh = self.neighbors()
+        with torch.cuda.device(dev):
+            _call(_lib.load().conv3p_grid_normals_f32, self.data.data_ptr(), K, neigh.data_ptr(), self.stats.data_ptr(),
+                  rooms.data_ptr() if rooms is not None else None, viewpoint.data_ptr() if viewpoint is not None else None,
+                  viewpoint.shape[0] if viewpoint is not None else 0, M, min_neighbors, out.normals.data_ptr(),
+                  out.curvature.data_ptr(), out.samples.data_ptr(), out.flags.data_ptr(),
+                  out.moments.data_ptr() if return_moments else None, out.stats.data_ptr(),
+                  torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def with_normals(self, nrm, curvature=False):
+        """data and the normals of normals() side by side -> a contiguous float32 (M, K + 3) tensor, or (M, K + 4) with
+        curvature: the K channels of data, then the normal, then the curvature.  This is what scene_blocks /
+        scene_blocks_rooms take in place of data: with xyz + rgb in, the blocks come out as xyz, rgb, normal,
+        room-normalised xyz -- 12 channels.  The layout is this project's own: the channel order of SceneNN's files is
+        not in the reference tree.  Voxels without a normal (flags != 0) carry zeros.  A torch concatenation."""
+        M = self.data.shape[0]
+        _require(isinstance(nrm, GridNormals), "nrm must be the GridNormals of normals()")
+        _require(tuple(nrm.normals.shape) == (M, 3) and nrm.normals.device == self.data.device,
+                 "nrm was made for another subsampling (%d voxels here)" % M)
+        _require(isinstance(curvature, bool), "curvature must be a bool")
+        parts = [self.data, nrm.normals] + ([nrm.curvature[:, None]] if curvature else [])
+        return torch.cat(parts, dim=1).contiguous()
+
+
+class GridNormals:
+    """The outputs of GridSubsample.normals: normals float32 (M, 3), unit vectors or 0; curvature float32 (M) in [0,
+    1/3]; samples int32 (M), the occupied cells among the 27 around the voxel; flags int32 (M): 0 a normal, 1 too few
+    samples, 2 degenerate moments, -1 a filler row; moments float32 (M, 9) or None; stats int32 (4) on the device =
+    {voxels with a normal, too few samples, degenerate, filler}."""
+
+    def __init__(self, num_voxels, with_moments, device):
+        M = int(num_voxels)
+        self.shape = (M, bool(with_moments))
+        self.normals = torch.empty((M, 3), dtype=torch.float32, device=device)
+        self.curvature = torch.empty((M,), dtype=torch.float32, device=device)
+        self.samples = torch.empty((M,), dtype=torch.int32, device=device)
+        self.flags = torch.empty((M,), dtype=torch.int32, device=device)
+        self.moments = torch.empty((M, 9), dtype=torch.float32, device=device) if with_moments else None
+        self.stats = torch.zeros((4,), dtype=torch.int32, device=device)
+
+    def count(self):
+        """The number of voxels with a normal: the one host read (a synchronisation)."""
+        return int(self.stats[0])
 
 
 def _check_arguments(data, labels, voxel, mode, num_class):
