@@ -782,6 +782,44 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   the only atomics are the integer adds of the three counts; no float atomics; bitwise reproducible and independent of
  *   the launch geometry.
  *
+ * conv3p_grid_interpolate_rings_f32 / _i64:  the same, and a row that rule 4 leaves without a candidate searches ring
+ *   after ring of cells around its own (pointwise_amd/csrc/conv3p_grid_interp_rings.hpp; tests/grid_interp_rings_ref.py
+ *   restates it in numpy).  rings in [1, 8] is the largest Chebyshev distance, in cells, between the row's own cell and a
+ *   candidate's: the cube of rings = 8 is 17^3 cells, 32 cm at a 4 cm voxel.  voxel_cell (>= M, 3), voxel_room (>= M) and
+ *   voxel_start (num_rooms + 1) -- both or neither -- and grid_stats are the subsampling's; ne = min(max(grid_stats[0], 0),
+ *   M) is read ON THE DEVICE.  For a raw row i with v0 = inverse[i] in [0, M) and (a, b, l) = voxel_cell[v0]:
+ *    6. Rules 1-5 apply unchanged.  A row that rule 5 interpolates has ring = 1; its label and score row are what the plain
+ *       call writes, to the bit, whatever rings is.
+ *    7. A row that rule 4 would leave without a candidate takes r = 2, 3, ..., rings in turn.  The candidates of ring r are
+ *       the emitted voxels u with u < ne; with voxel_room / voxel_start, u in [voxel_start[p], voxel_start[p+1]), p =
+ *       voxel_room[v0], clamped as N4 clamps it (rooms that overlap in space share nothing; v0 >= ne has no candidates,
+ *       as its row of neigh has none); max(|i_x(u) - a|, |i_y(u) - b|, |i_z(u) - l|) <= r; valid_labels[u] >= 0 where
+ *       valid_labels is given; the d2 of rule 2 finite (the same operations in the same order, uncontracted).  The first r
+ *       whose candidate set is not empty ends the search: rules 3 and 5 are applied to that set as they stand -- the min(k,
+ *       candidates) smallest by the total order (d2, u), the chains in rank order, the same label rule -- and ring = r.
+ *    8. No ring up to rings has a candidate: label -1, score row 0, ring = 0, counted in stats[2].  A row of rule 1 (no
+ *       voxel) has ring = 0 too.
+ *    9. out_ring int32 (N) or NULL; stats int64 (3) = {rows interpolated at any ring, rows without a voxel, rows without
+ *       a candidate within rings}; ring_stats int64 (9): ring_stats[r], r = 1 .. 8, the rows interpolated at ring r,
+ *       ring_stats[0] the rows that entered the fallback (no candidate in their 27 cells).  All exact, overwritten by
+ *       every call.
+ *   This is NOT a k-nearest-neighbour search.  The search stops at the first cube that is not empty, so a nearer voxel
+ *   one ring further out is not seen, just as the plain call does not see ring 2; what that buys is that every row the
+ *   plain call labels is untouched, and that the stopping test is an integer fact about cells: no floating-point bound
+ *   on where a mean representative can lie enters.  The cube of ring r - 1 of a row in the fallback holds no candidate,
+ *   so the implementation scans the shell of ring r alone; the set is the same.  rings = 1 gives the plain call's
+ *   labels, scores and stats, to the bit, with ring_stats[1] = stats[0].
+ *   Status, in this order, all before any launch: N < 0, M < 0, K < 3, voxel_K < 3, C outside [1, 128], k outside [1, 8],
+ *   rings outside [1, 8], num_rooms < 0, one of voxel_room / voxel_start without the other: CONV3P_ERR_INVALID_ARGUMENT;
+ *   stats or ring_stats NULL; data, inverse or out_labels NULL with N > 0; voxel_data, neigh, voxel_scores, voxel_cell or
+ *   grid_stats NULL with N > 0 and M > 0: CONV3P_ERR_INVALID_ARGUMENT; N or M > 2^31 - 1, num_rooms > 65536:
+ *   CONV3P_ERR_UNSUPPORTED; workspace NULL or smaller than conv3p_grid_interpolate_rings_workspace_bytes(N) (a counter
+ *   and an int32 per row): CONV3P_ERR_INVALID_ARGUMENT.  The launches depend on nothing but rings > 1: the plain call's
+ *   memset and kernel, two small memsets, the list kernel, and with rings > 1 the ring kernel on a fixed grid; no host
+ *   read; the only atomics are integer adds; a row in the fallback has its label and score row written by the plain pass
+ *   and, where a ring finds a candidate, once more; bitwise reproducible and independent of the launch geometry and of
+ *   the order of the list.
+ *
  * conv3p_grid_normals_f32:  a surface normal and a curvature per voxel, from the representatives of the 3 x 3 x 3 cells
  *   around it (pointwise_amd/csrc/conv3p_grid_normals.hpp; tests/grid_normals_ref.py restates it in numpy).  A raw scan
  *   carries no normals and normals averaged over a voxel are no unit vectors; this is the estimate a model trained on
@@ -846,6 +884,19 @@ int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32
                                 int voxel_K, const int32_t *neigh, const int64_t *voxel_scores, int64_t M, int C,
                                 const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
                                 void *stream);
+size_t conv3p_grid_interpolate_rings_workspace_bytes(int64_t N);
+int conv3p_grid_interpolate_rings_f32(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                      int voxel_K, const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
+                                      const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats,
+                                      const float *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k, int rings,
+                                      int32_t *out_labels, float *out_scores, int32_t *out_ring, int64_t *stats,
+                                      int64_t *ring_stats, void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_grid_interpolate_rings_i64(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                      int voxel_K, const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
+                                      const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats,
+                                      const int64_t *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k, int rings,
+                                      int32_t *out_labels, float *out_scores, int32_t *out_ring, int64_t *stats,
+                                      int64_t *ring_stats, void *workspace, size_t workspace_bytes, void *stream);
 int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh, const int32_t *grid_stats,
                             const int32_t *voxel_room, const float *viewpoint, int64_t V, int64_t M, int min_neighbors,
                             float *normals, float *curvature, int32_t *samples, int32_t *flags, float *moments,

@@ -158,6 +158,11 @@ SYMBOLS = {
                                          _vp, _vp, _vp]),
     "conv3p_grid_interpolate_i64": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _i, _vp,
                                          _vp, _vp, _vp]),
+    "conv3p_grid_interpolate_rings_workspace_bytes": (_sz, [ctypes.c_int64]),
+    "conv3p_grid_interpolate_rings_f32": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp,
+                                               _vp, ctypes.c_int64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_grid_interpolate_rings_i64": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp,
+                                               _vp, ctypes.c_int64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_grid_normals_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),

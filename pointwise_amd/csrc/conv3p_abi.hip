@@ -31,6 +31,7 @@
 #include "conv3p_grid.hpp"
 #include "conv3p_grid_rooms.hpp"
 #include "conv3p_grid_interp.hpp"
+#include "conv3p_grid_interp_rings.hpp"
 #include "conv3p_grid_normals.hpp"
 
 #include <hip/hip_runtime.h>
@@ -3996,6 +3997,78 @@ int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32
 {
     return grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, reinterpret_cast<const long long *>(voxel_scores),
                             M, C, valid_labels, k, out_labels, out_scores, stats, stream);
+}
+
+size_t conv3p_grid_interpolate_rings_workspace_bytes(int64_t N)
+{
+    if (N < 0 || N > (int64_t)INT32_MAX) return 0;
+    return kRingHeaderBytes + up((size_t)N * sizeof(int32_t));       // the list's counter, and a place per row
+}
+
+extern "C++" {
+namespace {
+// The plain pass as it stands, then the list of the rows it left without a candidate, then (rings > 1) their ring search.
+template <typename S>
+int grid_interpolate_rings(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data, int voxel_K,
+                           const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
+                           const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats, const S *voxel_scores,
+                           int64_t M, int C, const int32_t *valid_labels, int k, int rings, int32_t *out_labels,
+                           float *out_scores, int32_t *out_ring, int64_t *stats, int64_t *ring_stats, void *workspace,
+                           size_t workspace_bytes, void *stream)
+{
+    if (N < 0 || M < 0 || K < 3 || voxel_K < 3 || C < 1 || C > kInterpMaxClass || k < 1 || k > kInterpMaxK || rings < 1 ||
+        rings > kRingMax || num_rooms < 0)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if ((voxel_room == nullptr) != (voxel_start == nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (!stats || !ring_stats || (N > 0 && (!data || !inverse || !out_labels)) ||
+        (N > 0 && M > 0 && (!voxel_data || !neigh || !voxel_scores || !voxel_cell || !grid_stats)))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (N > (int64_t)INT32_MAX || M > (int64_t)INT32_MAX || num_rooms > kGridRoomsMaxRooms) return CONV3P_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < conv3p_grid_interpolate_rings_workspace_bytes(N)) return CONV3P_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t *counter = static_cast<int32_t *>(workspace);
+    int32_t *list = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + kRingHeaderBytes);
+    if (hipMemsetAsync(ring_stats, 0, (kRingMax + 1) * sizeof(int64_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
+    if (hipMemsetAsync(counter, 0, sizeof(int32_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
+    const int rc = grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_scores, M, C, valid_labels, k,
+                                    out_labels, out_scores, stats, stream);
+    if (rc != CONV3P_OK || N == 0) return rc;
+    const size_t work = ((size_t)N + kRingListThreads - 1) / kRingListThreads;
+    hipLaunchKernelGGL(grid_ring_list_kernel, dim3((unsigned)(work < (size_t)kRingListMaxGrid ? work : (size_t)kRingListMaxGrid)),
+                       dim3(kRingListThreads), 0, s, inverse, out_labels, (long long)N, (int)M, rings, counter, list, out_ring,
+                       reinterpret_cast<unsigned long long *>(ring_stats));
+    if (rings > 1)
+        hipLaunchKernelGGL((grid_ring_search_kernel<S>), dim3(kRingGrid), dim3(kRingThreads), 0, s, data, (long long)N, K, inverse,
+                           voxel_data, voxel_K, voxel_cell, voxel_room, voxel_start, (int)num_rooms, grid_stats, voxel_scores,
+                           (int)M, C, valid_labels, k, rings, counter, list, out_labels, out_scores, out_ring,
+                           reinterpret_cast<unsigned long long *>(stats), reinterpret_cast<unsigned long long *>(ring_stats));
+    return hip_ok();
+}
+}  // namespace
+}  // extern "C++": a template
+
+int conv3p_grid_interpolate_rings_f32(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                      int voxel_K, const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
+                                      const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats,
+                                      const float *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k, int rings,
+                                      int32_t *out_labels, float *out_scores, int32_t *out_ring, int64_t *stats,
+                                      int64_t *ring_stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grid_interpolate_rings(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_cell, voxel_room, voxel_start, num_rooms,
+                                  grid_stats, voxel_scores, M, C, valid_labels, k, rings, out_labels, out_scores, out_ring, stats,
+                                  ring_stats, workspace, workspace_bytes, stream);
+}
+
+int conv3p_grid_interpolate_rings_i64(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
+                                      int voxel_K, const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
+                                      const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats,
+                                      const int64_t *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k, int rings,
+                                      int32_t *out_labels, float *out_scores, int32_t *out_ring, int64_t *stats,
+                                      int64_t *ring_stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grid_interpolate_rings(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_cell, voxel_room, voxel_start, num_rooms,
+                                  grid_stats, reinterpret_cast<const long long *>(voxel_scores), M, C, valid_labels, k, rings,
+                                  out_labels, out_scores, out_ring, stats, ring_stats, workspace, workspace_bytes, stream);
 }
 
 int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh, const int32_t *grid_stats,

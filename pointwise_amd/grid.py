@@ -1,6 +1,7 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
 conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64,
-conv3p_grid_normals_f32; kernels in csrc/conv3p_grid.hpp, csrc/conv3p_grid_interp.hpp and csrc/conv3p_grid_normals.hpp).
+conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32; kernels in csrc/conv3p_grid.hpp,
+csrc/conv3p_grid_interp.hpp, csrc/conv3p_grid_interp_rings.hpp and csrc/conv3p_grid_normals.hpp).
 
 A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
 first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
@@ -13,7 +14,8 @@ tests/grid_ref.py restates it in numpy.
     GridSubsample.project   voxel labels (num_voxels) -> a label per raw row (N) int32, -1 for a row without a voxel
     GridSubsample.neighbors     -> int32 (max_voxels, 27), the voxels of the 3 x 3 x 3 cells around every voxel
     GridSubsample.interpolate   voxel scores (num_voxels, C) -> a label (and a score row) per raw row, blended from the
-                     k nearest voxels around the row with inverse-distance weights (tests/grid_interp_ref.py)
+                     k nearest voxels around the row with inverse-distance weights (tests/grid_interp_ref.py); rings > 1:
+                     a row with no voted voxel in its 27 cells searches ring after ring (tests/grid_interp_rings_ref.py)
     GridSubsample.normals       -> GridNormals: a unit normal, a curvature, the sample count and a flag per voxel, from the
                      representatives of the 3 x 3 x 3 cells around it (tests/grid_normals_ref.py)
     GridSubsample.with_normals  data and those normals side by side, (M, K + 3): what scene_blocks takes in place of data
@@ -32,8 +34,9 @@ From a raw room to the model and back:
     per batch:  points, inp, idx = pv.get_batch_point_cloud();  scores.add(model(points, inp), idx)
     labels = g.project(scores.labels())                              # (N) int32 over the raw rows: its voxel's label
   or
-    labels = g.interpolate(room, scores, k=3)                        # the 3 nearest voted voxels' scores, blended: rows
-                                                                     # of an unvoted voxel are labelled from its neighbours
+    labels = g.interpolate(room, scores, k=3, rings=4)               # the 3 nearest voted voxels' scores, blended: rows
+                                                                     # of an unvoted voxel are labelled from its neighbours,
+                                                                     # up to 4 cells away where the 27 cells around hold none
 
 A model trained on files with normals, fed from a raw scan that has none (xyz + rgb in, blocks of 12 channels out:
 xyz, rgb, normal, room-normalised xyz):
@@ -140,18 +143,30 @@ class GridSubsample:
         self._neigh = neigh
         return neigh
 
-    def interpolate(self, data, voxel_scores, k=3, valid_labels=None, return_scores=False, out=None):
+    def interpolate(self, data, voxel_scores, k=3, valid_labels=None, return_scores=False, out=None, rings=1,
+                    return_ring=False):
         """Scores per voxel -> a label per raw row (N) int32, or (labels, scores float32 (N, C)) with return_scores: the
         scores of the k nearest voxels among the 3 x 3 x 3 cells around the row's own, blended with weights 1 / max(d^2,
         1e-10), d from the raw row to the voxel's representative (include/conv3p.h: conv3p_grid_interpolate_f32, rules 1-5).
+
+        rings in [1, 8]: a row whose 27 cells hold no candidate searches the cells at Chebyshev distance 2, 3, ..., rings
+        of its own and is interpolated from the first ring that has one (conv3p_grid_interpolate_rings_f32, rules 6-9: not
+        a k-NN, the search stops at the first cube that is not empty; rows labelled at rings=1 keep their bits).
+        return_ring: also ring int32 (N), the ring a row was interpolated at, 0 for a row left at -1; the return value is
+        labels, (labels, scores), (labels, ring) or (labels, scores, ring), and out= has the same shape.  With rings > 1 or
+        return_ring the call goes through the ring entry: ring_stats int64 (9) on the device = {rows that entered the
+        fallback, rows interpolated at ring 1, ..., at ring 8}, interp_stats[0] counts the rows interpolated at any ring,
+        and the launches are the plain call's, a list kernel and, with rings > 1, the ring kernel (the workspace, an int32
+        per row, is kept on the object).
 
         data is the raw (N, K) tensor the subsampling was given.  voxel_scores: a contiguous float32 (M, C) tensor, C <=
         128 (valid_labels=None: every voxel is a candidate), or a SceneScores, whose exact int64 sums are read as they
         are and whose labels() are the default valid_labels, so a voxel nobody voted for is no candidate.  valid_labels
         int32 (M): voxels with a negative entry are no candidates.  -1 and a zero score row for a row without a voxel or
         without a candidate; interp_stats int64 (3) on the device = {rows interpolated, without a voxel, without a
-        candidate}.  out: the labels tensor, or (labels, scores) with return_scores.  One kernel launch behind a 24-byte
-        memset of interp_stats (and the neighbour table's launch on first use), nothing synchronised on."""
+        candidate}.  out: the labels tensor, or (labels, scores) with return_scores.  The default call is one kernel launch
+        behind a 24-byte memset of interp_stats (and the neighbour table's launch on first use); nothing is synchronised on
+        in either form."""
         from .scene import SceneScores
         dev = self.inverse.device
         N = self.inverse.numel()
@@ -175,16 +190,35 @@ class GridSubsample:
             _require(isinstance(valid_labels, torch.Tensor) and valid_labels.dtype == torch.int32 and valid_labels.device == dev
                      and tuple(valid_labels.shape) == (M,) and valid_labels.is_contiguous(),
                      "valid_labels must be a contiguous int32 (M,) tensor on the cloud's device")
-        _require(out is None or not return_scores or (isinstance(out, (tuple, list)) and len(out) == 2),
-                 "out must be (labels, scores) with return_scores")
-        lab, sc = (out if return_scores else (out, None)) if out is not None else (None, None)
+        _require(isinstance(rings, int) and not isinstance(rings, bool) and 1 <= rings <= 8, "rings must be an integer in [1, 8]")
+        _require(isinstance(return_ring, bool), "return_ring must be a bool")
+        parts = 1 + bool(return_scores) + return_ring
+        _require(out is None or parts == 1 or (isinstance(out, (tuple, list)) and len(out) == parts),
+                 "out must be (labels, scores) with return_scores" if not return_ring else
+                 "out must be (labels, ring) with return_ring, (labels, scores, ring) with return_scores too")
+        lab = sc = rg = None
         if out is not None:
+            lab = out if parts == 1 else out[0]
+            sc = out[1] if return_scores else None
+            rg = out[parts - 1] if return_ring else None
             _require(isinstance(lab, torch.Tensor) and lab.dtype == torch.int32 and tuple(lab.shape) == (N,)
                      and lab.device == dev and lab.is_contiguous(),
                      "out labels must be a contiguous int32 (N,) tensor on the cloud's device")
             _require(not return_scores or (isinstance(sc, torch.Tensor) and sc.dtype == torch.float32
                                            and tuple(sc.shape) == (N, C) and sc.device == dev and sc.is_contiguous()),
                      "out scores must be a contiguous float32 (N, C) tensor on the cloud's device")
+            _require(not return_ring or (isinstance(rg, torch.Tensor) and rg.dtype == torch.int32 and tuple(rg.shape) == (N,)
+                                         and rg.device == dev and rg.is_contiguous()),
+                     "out ring must be a contiguous int32 (N,) tensor on the cloud's device")
+        ringed = rings > 1 or return_ring
+        if ringed:
+            room, start = getattr(self, "voxel_room", None), getattr(self, "voxel_start", None)
+            Mv = self.data.shape[0]
+            for name, t, shape in (("voxel_cell", self.voxel_cell, (Mv, 3)), ("stats", self.stats, (8,))) + (
+                    (("voxel_room", room, (Mv,)), ("voxel_start", start, None)) if room is not None else ()):
+                _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()
+                         and (tuple(t.shape) == shape if shape is not None else t.dim() == 1 and t.numel() >= 1),
+                         "%s must be a contiguous int32 tensor of the subsampling's shape on its device" % name)
         _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
         if valid_labels is None and isinstance(voxel_scores, SceneScores):
             valid_labels = voxel_scores.labels()
@@ -195,14 +229,35 @@ class GridSubsample:
         if getattr(self, "interp_stats", None) is None:
             self.interp_stats = torch.zeros((3,), dtype=torch.int64, device=dev)
         neigh = self.neighbors()
+        lib = _lib.load()
+        if not ringed:
+            with torch.cuda.device(dev):
+                _call(getattr(lib, entry), data.data_ptr() if N else None, N, data.shape[1],
+                      self.inverse.data_ptr() if N else None, self.data.data_ptr() if M else None, self.data.shape[1],
+                      neigh.data_ptr() if M else None, scores.data_ptr() if M else None, M, C,
+                      valid_labels.data_ptr() if valid_labels is not None and M else None, k, lab.data_ptr() if N else None,
+                      sc.data_ptr() if sc is not None and N else None, self.interp_stats.data_ptr(),
+                      torch.cuda.current_stream(dev).cuda_stream)
+            return (lab, sc) if return_scores else lab
+        rooms = room is not None and M > 0               # without voxels no row has one: the rooms are not read
+        if return_ring and rg is None:
+            rg = torch.empty((N,), dtype=torch.int32, device=dev)
+        if getattr(self, "ring_stats", None) is None:
+            self.ring_stats = torch.zeros((9,), dtype=torch.int64, device=dev)
+        need = int(lib.conv3p_grid_interpolate_rings_workspace_bytes(N))
+        if getattr(self, "_ring_workspace", None) is None or self._ring_workspace.numel() < need:
+            self._ring_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _call(getattr(_lib.load(), entry), data.data_ptr() if N else None, N, data.shape[1],
-                  self.inverse.data_ptr() if N else None, self.data.data_ptr() if M else None, self.data.shape[1],
-                  neigh.data_ptr() if M else None, scores.data_ptr() if M else None, M, C,
-                  valid_labels.data_ptr() if valid_labels is not None and M else None, k, lab.data_ptr() if N else None,
-                  sc.data_ptr() if sc is not None and N else None, self.interp_stats.data_ptr(),
-                  torch.cuda.current_stream(dev).cuda_stream)
-        return (lab, sc) if return_scores else lab
+            _call(getattr(lib, entry.replace("interpolate", "interpolate_rings")), data.data_ptr() if N else None, N,
+                  data.shape[1], self.inverse.data_ptr() if N else None, self.data.data_ptr() if M else None,
+                  self.data.shape[1], neigh.data_ptr() if M else None, self.voxel_cell.data_ptr() if M else None,
+                  room.data_ptr() if rooms else None, start.data_ptr() if rooms else None,
+                  start.numel() - 1 if rooms else 0, self.stats.data_ptr(), scores.data_ptr() if M else None, M, C,
+                  valid_labels.data_ptr() if valid_labels is not None and M else None, k, rings,
+                  lab.data_ptr() if N else None, sc.data_ptr() if sc is not None and N else None,
+                  rg.data_ptr() if rg is not None and N else None, self.interp_stats.data_ptr(), self.ring_stats.data_ptr(),
+                  self._ring_workspace.data_ptr(), self._ring_workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        return tuple(t for t in (lab, sc, rg) if t is not None) if parts > 1 else lab
 
     def normals(self, viewpoint=None, min_neighbors=6, return_moments=False, out=None):
         """A surface normal and a curvature per voxel -> GridNormals, from the representatives (data[:, :3]) of the 3 x 3
