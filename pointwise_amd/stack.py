@@ -56,8 +56,11 @@ class Conv3pStack:
         # first batch) -- saves one empty launch per dilated layer and step
         self.sparse_neighbourhoods = None
         self.c_stack = c_stack and use_cache and fuse_selu
+        # ONE piece of bookkeeping for the stack-level entry points and the op-by-op composition (prefetch()'s docstring):
         self._inflight = None          # cache index of the batch between forward() and backward()
-        self._pending = {}             # cache index -> points tensor whose geometry was prefetched into it
+        # cache index -> (points tensor whose geometry was prefetched into it, its per-layer events or None when the
+        # library keeps them), oldest prefetch first.  The tensor is HELD: its address cannot be recycled while recorded
+        self._pending = {}
         self._scratch = None
         # SELU fused into the op's epilogues (conv3p_layer_*): 1 activation launch per step instead of 8
         self.fuse_selu = fuse_selu and use_cache
@@ -72,8 +75,7 @@ class Conv3pStack:
         self._side = None
         self._cache = None
         self._caches = [None, None]    # two neighbour caches: the batch in flight and the prefetched one
-        self._which = 0
-        self._prefetched = None        # (tensor, cache index, events) of the last prefetch()
+        self._which = 0                # cache index of the last forward()
         self.device = torch.device(device)
         self.dtype = dtype
         self.num_class = num_class
@@ -149,24 +151,55 @@ class Conv3pStack:
     def _real(self, v):
         return ctypes.c_float(v) if self.dtype == torch.float32 else ctypes.c_double(v)
 
+    def _pending_index(self, points):
+        """The cache that holds the outstanding prefetch of this very tensor, or None."""
+        for idx, rec in self._pending.items():
+            if rec[0] is points:
+                return idx
+        return None
+
     def _free_cache_index(self):
         """The cache a new prefetch may use: never the one serving the batch between forward() and backward(); a
-        cache that holds a prefetch nobody consumed yet is taken only when nothing else is free (that prefetch
-        is then simply lost: its batch will search for itself)."""
-        order = (1 - self._which, self._which)
-        for idx in order:
+        cache that holds a prefetch nobody consumed yet is taken only when nothing else is free, the OLDEST such
+        prefetch first (it is then simply lost: its batch will search for itself).  The new searches go to the side
+        stream, behind whatever the superseded prefetch still has enqueued there."""
+        for idx in (1 - self._which, self._which):
             if idx != self._inflight and idx not in self._pending:
                 return idx
-        for idx in order:
+        for idx in self._pending:
             if idx != self._inflight:
-                self._pending.pop(idx, None)
+                del self._pending[idx]
                 return idx
         raise op.Conv3pRuntimeError("prefetch(): no neighbour cache is free")   # unreachable with two caches
 
+    def _take_cache_index(self, points):
+        """The cache forward() runs in, and the record of the prefetch it consumes (None: it searches for itself): the
+        cache this tensor was prefetched into; else a cache without an outstanding prefetch, the last forward's first (a
+        new forward supersedes a forward that never had its backward); else the one of the oldest prefetch, which is lost
+        -- its searches may still be writing that cache on the side stream, so the main stream waits for them.  Either
+        way no record keeps pointing at the cache taken."""
+        idx = self._pending_index(points)
+        if idx is not None:
+            return idx, self._pending.pop(idx)
+        for idx in (self._which, 1 - self._which):
+            if idx not in self._pending:
+                return idx, None
+        idx = next(iter(self._pending))
+        del self._pending[idx]
+        self._join_side(points.device)
+        return idx, None
+
+    def _leave_c_stack(self, device):
+        """A shape the stack-level entry points do not take: op-by-op from now on.  Whatever they prefetched is dropped
+        (their events live in the library), after the main stream has waited for it."""
+        self._join_side(device)
+        self._pending.clear()
+        self._inflight = None
+        self.c_stack = False
+
     def _c_prefetch(self, points):
-        for idx, t in self._pending.items():
-            if t is points:
-                return True
+        if self._pending_index(points) is not None:
+            return True
         idx = self._free_cache_index()
         cache = self._cache_slot(idx, points)
         main = torch.cuda.current_stream(points.device)
@@ -178,27 +211,18 @@ class Conv3pStack:
             ok = self._c_call("prefetch", points.data_ptr(), self._real(VOXEL), B, N, cache.buf.data_ptr(), cache.nbytes,
                               cache.cfg_ptr(False), self._side.cuda_stream, main.cuda_stream)
         if ok:
-            self._pending[idx] = points
+            self._pending[idx] = (points, None)
         return ok
 
     def _c_forward(self, points, features):
         B, N = points.shape[0], points.shape[1]
-        idx = None
-        for i, t in self._pending.items():
-            if t is points:
-                idx = i
-        if idx is None:
-            idx = self._which if self._which not in self._pending else 1 - self._which
-            if self._pending.pop(idx, None) is not None:
-                # a prefetch that was never consumed is overwritten: its searches may still be writing this cache on
-                # the side stream, and this batch's search may run on the main stream
-                self._join_side(points.device)
+        idx, prefetched = self._take_cache_index(points)
         cache = self._cache_slot(idx, points)
         concat = torch.empty((B, N, HIDDEN * 4), dtype=self.dtype, device=points.device)
         head = torch.empty((B, N, self.num_class), dtype=self.dtype, device=points.device) if self.num_class else None
         main = torch.cuda.current_stream(points.device)
         side = None
-        if self.overlap_search and idx not in self._pending:
+        if self.overlap_search and prefetched is None:
             if self._side is None:
                 self._side = _side_stream(points.device)
             side = self._side.cuda_stream
@@ -210,7 +234,6 @@ class Conv3pStack:
                               cache.buf.data_ptr(), cache.nbytes, cache.cfg_ptr(False), main.cuda_stream, side)
         if not ok:
             return None
-        self._pending.pop(idx, None)
         self._which = idx
         self._inflight = idx
         self._cache = cache
@@ -291,49 +314,58 @@ class Conv3pStack:
         return self.sparse_neighbourhoods
 
     def prepare(self, B, N):
-        """Set-up outside any timed region: allocate both neighbour caches for (B, N) clouds."""
+        """Set-up outside any timed region: allocate both neighbour caches for (B, N) clouds.  Called mid-run, it leaves
+        alone a cache that serves the batch between forward() and backward() or holds an outstanding prefetch."""
         if self.use_cache:
             for idx in (0, 1):
+                if idx == self._inflight or idx in self._pending:
+                    continue
                 cmax = max(max(ci, co) for ci, co, _ in self.layers)
                 c = self._caches[idx]
                 if c is None or not c.fits(B, N, self.dtype, self.device, 27, cmax, cmax):
+                    if c is not None:
+                        # (a superseded prefetch may still be writing the old buffer on the side stream)
+                        self._join_side(self.device)
                     self._caches[idx] = op.NeighborCache(B, N, self.dtype, self.device, slots=len(self.layers),
                                                          max_taps=27, max_cin=cmax, max_cout=cmax,
                                                          sparse_neighbourhoods=self.sparse_neighbourhoods,
                                                          fused_stack=self._fused_flag())
 
-    def _cache_for(self, points):
-        if not self.use_cache:
-            return None
-        self._cache = self._cache_slot(self._which, points)
-        return self._cache
-
     def prefetch(self, points):
         """Software pipelining across steps: enqueue the geometry (sort + every layer's neighbour search) of the
         NEXT batch on the side stream, typically right after forward() of the current batch, so that it runs under
-        the current batch's backward.  Geometry depends on `points` only.  The caller must not modify `points`
-        between prefetch() and the forward() that consumes it (that forward trusts the prefetch)."""
+        the current batch's backward.  Geometry depends on `points` only.
+
+        The contract (the same for the stack-level entry points and the op-by-op composition; exercised over seeded
+        schedules by tests/test_stack_schedules.py):
+          * The stack has two neighbour caches.  The batch between forward() and backward() keeps one of them, so TWO
+            prefetches can be outstanding while no batch is in flight and ONE while one is.  A forward() without a
+            backward() stays "in flight" until the next forward() replaces it.
+          * prefetch() may be called at any point and any number of times.  One that finds no cache free supersedes the
+            OLDEST outstanding prefetch; a prefetch of a tensor whose prefetch is outstanding does nothing.  Between
+            forward() and backward() it touches only the cache that does NOT serve the batch in flight (and the side
+            stream), never that batch's geometry.
+          * forward(points) consumes the outstanding prefetch of that very tensor object (identity, not content; the
+            stack holds the tensor until then, so its address cannot be recycled), the older or the newer one alike.  A
+            forward() that matches none searches for itself, in a cache without an outstanding prefetch if there is one,
+            else superseding the oldest prefetch.  A superseded prefetch is simply lost: its batch searches for itself.
+          * The caller must not modify `points` between prefetch() and the forward() that consumes it (that forward
+            trusts the prefetch), unless the prefetch has been superseded; nor, as for any saved tensor, between a
+            forward() and its backward().  Otherwise a batch tensor may be rewritten in place, or dropped, at will."""
         if not self.use_cache:
             return
         if self.c_stack:
             points = points.contiguous()
             if self._c_prefetch(points):
                 return
-            self.c_stack = False           # shapes the stack-level entry points do not take: op-by-op from now on
-        # the cache that holds no pending prefetch: normally the one the current batch is NOT using; when
-        # prefetch() is called before forward() of the batch prefetched earlier (i.e. the batch in `_which` is
-        # finished: its backward has been enqueued), that finished batch's cache
-        pend = self._prefetched
-        idx = 1 - self._which
-        if pend is not None and pend[1] == idx:
-            if pend[0] is points:
-                return
-            idx = self._which
+            self._leave_c_stack(points.device)
+        if self._pending_index(points) is not None:
+            return
+        idx = self._free_cache_index()
         cache = self._cache_slot(idx, points)
-        self._pending2 = pend                              # keep the earlier prefetch for its forward()
         if not self.batched_prefetch:
             _, events = self._enqueue_searches(points, cache)
-            self._prefetched = (points, idx, events)
+            self._pending[idx] = (points, events)
             return
         # nothing waits for the first layer's lists here, so all layers' searches go out as ONE launch
         main = torch.cuda.current_stream(points.device)
@@ -347,7 +379,7 @@ class Conv3pStack:
         op.cache_prepare_multi(points, (3, 3, 3), strides, VOXEL, cache, stream=self._side)
         ev = torch.cuda.Event()
         ev.record(self._side)
-        self._prefetched = (points, idx, [ev] * len(self.layers))
+        self._pending[idx] = (points, [ev] * len(self.layers))
 
     def _enqueue_searches(self, points, cache):
         """All layers' geometry on the side stream; returns one event per layer."""
@@ -369,23 +401,20 @@ class Conv3pStack:
                                    features.contiguous() if not features.is_contiguous() else features)
             if acts is not None:
                 return acts
-            self.c_stack = False
-        pf = self._prefetched
-        p2 = getattr(self, "_pending2", None)
-        if p2 is not None and p2[0] is points and self.use_cache:
-            pf, keep = p2, self._prefetched               # the older of two outstanding prefetches
-            self._pending2 = None
-        else:
-            keep = None
-        if pf is not None and pf[0] is points and self.use_cache:
-            # geometry was enqueued by prefetch(): switch to that cache, wait for its per-layer events
-            self._which = pf[1]
-            cache = self._cache = self._caches[pf[1]]
-            main, events = torch.cuda.current_stream(points.device), pf[2]
-            self._prefetched = keep
-        else:
-            cache = self._cache_for(points)
-            main, events = (self._enqueue_searches(points, cache) if self.overlap_search else (None, None))
+            self._leave_c_stack(points.device)
+        cache, main, events = None, None, None
+        if self.use_cache:
+            idx, prefetched = self._take_cache_index(points)
+            if prefetched is not None:
+                # geometry was enqueued by prefetch(): switch to that cache, wait for its per-layer events
+                cache = self._caches[idx]
+                main, events = torch.cuda.current_stream(points.device), prefetched[1]
+            else:
+                cache = self._cache_slot(idx, points)
+                if self.overlap_search:
+                    main, events = self._enqueue_searches(points, cache)
+            self._which = self._inflight = idx
+            self._cache = cache
         acts, x = [], features
         for li in range(4):
             _, _, s = self.layers[li]
@@ -414,6 +443,7 @@ class Conv3pStack:
             return self._c_backward(upstream)
         points, features, acts, concat = self._saved
         cache = self._cache if self.use_cache else None
+        self._inflight = None          # (every call below is enqueued before a later prefetch() can take this cache)
         if self.num_class is not None:
             g = op.selu_grad(acts[4], upstream[0])
             dconcat, _ = op.conv3p_grad(g, points, concat, self.filters[4], (1, 1, 1), VOXEL,
