@@ -857,6 +857,54 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   16-byte memset of normal_stats; a thread per voxel; nothing synchronised on; the only atomics are the integer adds
  *   of the four counts; no float atomics; every output word written once; bitwise reproducible and independent of the
  *   launch geometry.
+ *
+ * conv3p_grid_segments, conv3p_grid_absorb_segments:  the voxel labels as a spatial field -- which voxels form one
+ *   connected piece of one class, how large each piece is, and a clean-up that gives small pieces the label around them
+ *   (pointwise_amd/csrc/conv3p_grid_segments.hpp; tests/grid_segments_ref.py restates both in numpy).  neigh int32 (M, 27)
+ *   as conv3p_grid_neighbors writes it (symmetric below ne: u = neigh[v][t] exactly when v = neigh[u][26 - t]);
+ *   voxel_labels int32 (L), L <= M, or NULL (L is then not read); voxel_count int32 (M); grid_stats the subsampling's
+ *   stats, of which ne = min(max(grid_stats[0], 0), M) is read ON THE DEVICE; num_class in [1, 128]; connectivity 6, 18
+ *   or 26.  Everything is int32 arithmetic: exact, and independent of the launch geometry and of thread order.
+ *    S1. Voxel v is LABELLED with c = voxel_labels[v] when v < ne, v < L and 0 <= c < num_class.  With voxel_labels NULL
+ *        every v < ne is labelled 0 and num_class is taken as 1: the geometric components.  Every other voxel -- filler
+ *        rows, v >= L, negative labels, labels >= num_class -- is unlabelled.
+ *    S2. The taps of a connectivity are the t != 13 with |dx| + |dy| + |dz| <= 1 (6), <= 2 (18), <= 3 (26), t = (dx+1)*9 +
+ *        (dy+1)*3 + (dz+1).  Labelled voxels u, v are JOINED when u = neigh[v][t] for such a tap, 0 <= u < ne, and both
+ *        have the same label.  A segment is an equivalence class of the transitive closure.  The table is per room in the
+ *        many-clouds result, so a segment never crosses a room.
+ *    S3. The ROOT of a segment is its smallest voxel number; segments are numbered 0 .. S-1 in ascending root.  For one
+ *        class that is scipy.ndimage.label's numbering on the dense lattice with generate_binary_structure(3, 1 | 2 | 3),
+ *        minus 1.  In the many-clouds result the numbers run room after room; a segment's room is voxel_room[root].
+ *    S4. Outputs, int32 (M) each, every word written: segment[v] the segment number, -1 for an unlabelled voxel; for s < S
+ *        seg_root[s], seg_size[s] in voxels, seg_rows[s] the sum of voxel_count over the members (at most 2^24),
+ *        seg_label[s]; for s >= S root -1, size 0, rows 0, label -1.  seg_stats int32 (8) = {S, labelled voxels,
+ *        unlabelled voxels below ne, M - ne, largest seg_size, largest seg_rows, 0, 0}, overwritten by every call.
+ *   The absorb is ONE pass over such a segmentation (segment, seg_size, seg_label, seg_stats as written above, the same
+ *   neigh, voxel_labels, L, grid_stats, num_class and connectivity), with min_size >= 1 and drop_orphans 0 or 1:
+ *    A1. Segment s is SMALL when seg_size[s] < min_size.
+ *    A2. For a small s, votes[c] is the number of pairs (u, t), u in s, t a tap of the connectivity, w = neigh[u][t] with
+ *        0 <= w < ne, segment[w] >= 0, segment[w] != s, that segment NOT small, seg_label[segment[w]] = c.  A neighbour of
+ *        s's own label in another segment cannot exist under the same connectivity, so every vote is for another class.
+ *        Small neighbours do not vote.
+ *    A3. The new label of s is the class with the most votes, the lowest class of a tie.  With no votes s is an ORPHAN: it
+ *        keeps its label, or takes -1 with drop_orphans.  (The geometric segmentation has one class, so every small
+ *        segment is an orphan and drop_orphans is outlier removal.)
+ *    A4. labels_out int32 (M): a voxel in a segment gets the segment's new or kept label; an unlabelled voxel below
+ *        min(L, ne) keeps its input word; everything else -1.  seg_label_out int32 (M): per segment, -1 past S.
+ *        absorb_stats int64 (4) = {small segments, absorbed (small with a vote), orphans, voxels whose label changed (the
+ *        sizes of the small segments whose new label differs, dropped orphans included)}, overwritten by every call.
+ *   With min_size = 1 labels_out is the labelled input to the bit.  The pass is NOT iterated: a small segment surrounded
+ *   only by small segments is an orphan, and sizes are not recomputed behind the relabelling.  A caller may segment the
+ *   result and run it again.
+ *   Status, in this order, all before any launch: M < 0; voxel_labels given with L < 0 or L > M; num_class outside [1, 128];
+ *   connectivity not 6, 18 or 26; (absorb) min_size < 1, drop_orphans not 0 or 1: CONV3P_ERR_INVALID_ARGUMENT; M == 0:
+ *   CONV3P_OK, nothing launched and nothing written; any other pointer NULL: CONV3P_ERR_INVALID_ARGUMENT; M > 2^31 - 1:
+ *   CONV3P_ERR_UNSUPPORTED; workspace NULL or smaller than conv3p_grid_segments_workspace_bytes(M) /
+ *   conv3p_grid_absorb_workspace_bytes(M): CONV3P_ERR_INVALID_ARGUMENT.  The workspaces are 2 M and 4 M int32 plus a word
+ *   or two per 2048 voxels: a function of M alone, whatever num_class.  Seven launches (segments) and six (absorb) whatever
+ *   the data; no host read: ne, S and the number of small segments stay on the device.  The union-find is lock-free: its
+ *   entries only ever decrease, so every retry follows another thread's progress and no loop waits for a thread to arrive.
+ *   The only atomics are int32 CAS / min / max / add and the int64 adds of absorb_stats; bitwise reproducible.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_GRID_MEAN 0
 #define CONV3P_GRID_CENTER 1
@@ -901,6 +949,17 @@ int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh
                             const int32_t *voxel_room, const float *viewpoint, int64_t V, int64_t M, int min_neighbors,
                             float *normals, float *curvature, int32_t *samples, int32_t *flags, float *moments,
                             int32_t *normal_stats, void *stream);
+size_t conv3p_grid_segments_workspace_bytes(int64_t M);
+int conv3p_grid_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *voxel_count,
+                         const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment,
+                         int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label, int32_t *seg_stats,
+                         void *workspace, size_t workspace_bytes, void *stream);
+size_t conv3p_grid_absorb_workspace_bytes(int64_t M);
+int conv3p_grid_absorb_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *segment,
+                                const int32_t *seg_size, const int32_t *seg_label, const int32_t *seg_stats,
+                                const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int min_size,
+                                int drop_orphans, int32_t *labels_out, int32_t *seg_label_out, int64_t *absorb_stats,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

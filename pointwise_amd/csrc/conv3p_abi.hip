@@ -33,6 +33,7 @@
 #include "conv3p_grid_interp.hpp"
 #include "conv3p_grid_interp_rings.hpp"
 #include "conv3p_grid_normals.hpp"
+#include "conv3p_grid_segments.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -4088,6 +4089,120 @@ int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh
     hipLaunchKernelGGL(grid_normals_kernel, dim3((unsigned)(work < (size_t)kNormalsMaxGrid ? work : (size_t)kNormalsMaxGrid)),
                        dim3(kNormalsThreads), 0, s, voxel_data, K, neigh, grid_stats, voxel_room, viewpoint,
                        viewpoint ? (int)V : 0, (int)M, min_neighbors, normals, curvature, samples, flags, moments, normal_stats);
+    return hip_ok();
+}
+
+namespace {
+// The taps of a connectivity as a mask over t = (dx+1)*9 + (dy+1)*3 + (dz+1); 0 for a connectivity that is none.
+unsigned gseg_tapmask(int connectivity)
+{
+    const int reach = connectivity == 6 ? 1 : (connectivity == 18 ? 2 : (connectivity == 26 ? 3 : 0));
+    unsigned mask = 0;
+    for (int t = 0; t < kInterpNeigh; ++t) {
+        const int d = std::abs(t / 9 - 1) + std::abs(t / 3 % 3 - 1) + std::abs(t % 3 - 1);
+        if (d >= 1 && d <= reach) mask |= 1u << t;
+    }
+    return mask;
+}
+size_t gseg_tiles(int64_t M) { return ((size_t)M + kGsegTile - 1) / kGsegTile; }
+unsigned gseg_grid(size_t work) { return (unsigned)(work < (size_t)kGsegMaxGrid ? (work ? work : 1) : (size_t)kGsegMaxGrid); }
+}  // namespace
+
+size_t conv3p_grid_segments_workspace_bytes(int64_t M)
+{
+    if (M <= 0 || M > (int64_t)INT32_MAX) return 0;
+    return up(gseg_tiles(M) * sizeof(int32_t)) + 2 * up((size_t)M * sizeof(int32_t));   // tiles' roots, lab, parent
+}
+
+int conv3p_grid_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *voxel_count,
+                         const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment,
+                         int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label, int32_t *seg_stats,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    const unsigned tapmask = gseg_tapmask(connectivity);
+    if (M < 0 || (voxel_labels && (L < 0 || L > M)) || num_class < 1 || num_class > kGsegMaxClass || !tapmask)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!neigh || !voxel_count || !grid_stats || !segment || !seg_root || !seg_size || !seg_rows || !seg_label || !seg_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < conv3p_grid_segments_workspace_bytes(M)) return CONV3P_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int m = (int)M, ntiles = (int)gseg_tiles(M);
+    char *ws = static_cast<char *>(workspace);
+    int32_t *tile_count = reinterpret_cast<int32_t *>(ws);
+    int32_t *lab = reinterpret_cast<int32_t *>(ws + up((size_t)ntiles * sizeof(int32_t)));
+    int32_t *parent = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(lab) + up((size_t)M * sizeof(int32_t)));
+    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)ntiles);
+    hipLaunchKernelGGL(gseg_local_kernel, dim3(gseg_grid(((size_t)M + kGsegLocalTile - 1) / kGsegLocalTile)),
+                       dim3(kGsegLocalTile), 0, s, neigh, voxel_labels,
+                       voxel_labels ? (int)L : 0, grid_stats, m, voxel_labels ? num_class : 1, tapmask, lab, parent, seg_root,
+                       seg_size, seg_rows, seg_label, seg_stats);
+    hipLaunchKernelGGL(gseg_link_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, neigh, lab, parent, grid_stats, m, tapmask);
+    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count);
+    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, tile_count, static_cast<int32_t *>(nullptr),
+                       ntiles, seg_stats, static_cast<int32_t *>(nullptr));
+    hipLaunchKernelGGL(gseg_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count, segment,
+                       seg_root, seg_label);
+    // consecutive voxels a wave: more of them where there are waves enough to fill the device anyway
+    const int steps = M >= (1 << 20) ? 16 : (M >= (1 << 16) ? 4 : 1);
+    const size_t per_wave = (size_t)64 * steps * (kGsegThreads / 64);
+    hipLaunchKernelGGL(gseg_assign_kernel, dim3(gseg_grid(((size_t)M + per_wave - 1) / per_wave)), dim3(kGsegThreads), 0, s, lab,
+                       parent, voxel_count, grid_stats, m, steps, segment, seg_size, seg_rows, seg_stats);
+    hipLaunchKernelGGL(gseg_max_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_size, seg_rows, m, seg_stats);
+    return hip_ok();
+}
+
+size_t conv3p_grid_absorb_workspace_bytes(int64_t M)
+{
+    if (M <= 0 || M > (int64_t)INT32_MAX) return 0;
+    // the two counts, two words per tile of segments, and cursor, small_list, small_off, members
+    return kGsegHeaderBytes + 2 * up(gseg_tiles(M) * sizeof(int32_t)) + 4 * up((size_t)M * sizeof(int32_t));
+}
+
+int conv3p_grid_absorb_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *segment,
+                                const int32_t *seg_size, const int32_t *seg_label, const int32_t *seg_stats,
+                                const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int min_size,
+                                int drop_orphans, int32_t *labels_out, int32_t *seg_label_out, int64_t *absorb_stats,
+                                void *workspace, size_t workspace_bytes, void *stream)
+{
+    const unsigned tapmask = gseg_tapmask(connectivity);
+    if (M < 0 || (voxel_labels && (L < 0 || L > M)) || num_class < 1 || num_class > kGsegMaxClass || !tapmask || min_size < 1 ||
+        (drop_orphans != 0 && drop_orphans != 1))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!neigh || !segment || !seg_size || !seg_label || !seg_stats || !grid_stats || !labels_out || !seg_label_out ||
+        !absorb_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < conv3p_grid_absorb_workspace_bytes(M)) return CONV3P_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t tile_bytes = up(gseg_tiles(M) * sizeof(int32_t)), row_bytes = up((size_t)M * sizeof(int32_t));
+    char *ws = static_cast<char *>(workspace);
+    AbsorbArgs p{};
+    p.neigh = neigh; p.voxel_labels = voxel_labels; p.segment = segment; p.seg_size = seg_size; p.seg_label = seg_label;
+    p.seg_stats = seg_stats; p.grid_stats = grid_stats;
+    p.L = voxel_labels ? (int)L : 0; p.M = (int)M; p.num_class = voxel_labels ? num_class : 1; p.min_size = min_size;
+    p.drop_orphans = drop_orphans; p.ntiles = (int)gseg_tiles(M); p.tapmask = tapmask;
+    p.labels_out = labels_out; p.seg_label_out = seg_label_out;
+    p.stats = reinterpret_cast<unsigned long long *>(absorb_stats);
+    p.hdr = reinterpret_cast<int32_t *>(ws);
+    p.tile_small = reinterpret_cast<int32_t *>(ws + kGsegHeaderBytes);
+    p.tile_members = reinterpret_cast<int32_t *>(ws + kGsegHeaderBytes + tile_bytes);
+    char *rows = ws + kGsegHeaderBytes + 2 * tile_bytes;
+    p.cursor = reinterpret_cast<int32_t *>(rows);
+    p.small_list = reinterpret_cast<int32_t *>(rows + row_bytes);
+    p.small_off = reinterpret_cast<int32_t *>(rows + 2 * row_bytes);
+    p.members = reinterpret_cast<int32_t *>(rows + 3 * row_bytes);
+    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)p.ntiles);
+    hipLaunchKernelGGL(absorb_count_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, p.tile_small, p.tile_members, p.ntiles, p.hdr,
+                       p.hdr + 1);
+    hipLaunchKernelGGL(absorb_plan_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(absorb_scatter_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(absorb_vote_kernel, dim3(gseg_grid(((size_t)M + kGsegThreads / 64 - 1) / (kGsegThreads / 64))),
+                       dim3(kGsegThreads), 0, s, p);      // a wave per small segment, and there are at most M
+    hipLaunchKernelGGL(absorb_labels_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
     return hip_ok();
 }
 

@@ -1,7 +1,8 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
 conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64,
-conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32; kernels in csrc/conv3p_grid.hpp,
-csrc/conv3p_grid_interp.hpp, csrc/conv3p_grid_interp_rings.hpp and csrc/conv3p_grid_normals.hpp).
+conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32, conv3p_grid_segments, conv3p_grid_absorb_segments;
+kernels in csrc/conv3p_grid.hpp, csrc/conv3p_grid_interp.hpp, csrc/conv3p_grid_interp_rings.hpp,
+csrc/conv3p_grid_normals.hpp and csrc/conv3p_grid_segments.hpp).
 
 A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
 first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
@@ -19,6 +20,9 @@ tests/grid_ref.py restates it in numpy.
     GridSubsample.normals       -> GridNormals: a unit normal, a curvature, the sample count and a flag per voxel, from the
                      representatives of the 3 x 3 x 3 cells around it (tests/grid_normals_ref.py)
     GridSubsample.with_normals  data and those normals side by side, (M, K + 3): what scene_blocks takes in place of data
+    GridSubsample.segments      voxel labels -> GridSegments: the connected pieces of one class over the 27-cell table (a
+                     lock-free union-find), their root, size, rows and label (tests/grid_segments_ref.py);
+                     GridSegments.absorb / GridSubsample.clean_labels: pieces below a size take the label around them
     grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
                      voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
@@ -33,6 +37,8 @@ From a raw room to the model and back:
     scores = SceneScores(g.num_voxels(), num_class, room.device)
     per batch:  points, inp, idx = pv.get_batch_point_cloud();  scores.add(model(points, inp), idx)
     labels = g.project(scores.labels())                              # (N) int32 over the raw rows: its voxel's label
+  or
+    labels = g.project(g.clean_labels(scores.labels(), num_class, min_size=4))   # speckles of < 4 voxels absorbed first
   or
     labels = g.interpolate(room, scores, k=3, rings=4)               # the 3 nearest voted voxels' scores, blended: rows
                                                                      # of an unvoted voxel are labelled from its neighbours,
@@ -336,6 +342,166 @@ class GridSubsample:
         _require(isinstance(curvature, bool), "curvature must be a bool")
         parts = [self.data, nrm.normals] + ([nrm.curvature[:, None]] if curvature else [])
         return torch.cat(parts, dim=1).contiguous()
+
+    def segments(self, voxel_labels=None, num_class=None, connectivity=26, out=None):
+        """The connected segments of a label per voxel -> GridSegments: voxels are joined when they are neighbours under
+        the connectivity (6: faces, 18: and edges, 26: and corners of the 27 cells of neighbors()) and carry the same
+        label; a segment's number is its rank by lowest voxel, so for one class it is scipy.ndimage.label's numbering
+        minus 1 (include/conv3p.h: conv3p_grid_segments, rules S1-S4; tests/grid_segments_ref.py).
+
+        voxel_labels: a contiguous int32 (L <= rows) tensor on the device, for example scores.labels(); voxels past L,
+        negative labels and labels >= num_class are in no segment (-1).  None: every emitted voxel is labelled 0 -- the
+        geometric components of the occupied cells.  num_class in [1, 128] is required with labels.  out: a GridSegments
+        of an earlier call with the same number of rows.  Works on a trimmed object and on the many-clouds result as they
+        stand: the table is per room, so no segment crosses a room, the numbers run room after room and a segment's room
+        is voxel_room[root].  g.project(seg.segment) gives the segment number of every raw row.  Seven launches whatever
+        the data (and the neighbour table's on first use), nothing synchronised on."""
+        dev = self.voxel_count.device
+        M = self.voxel_count.shape[0]
+        L = _check_segment_arguments(voxel_labels, num_class, connectivity, M, dev)
+        _require(isinstance(self.voxel_count, torch.Tensor) and self.voxel_count.dtype == torch.int32
+                 and self.voxel_count.is_contiguous() and tuple(self.voxel_cell.shape) == (M, 3),
+                 "voxel_count must be a contiguous int32 (M,) tensor beside voxel_cell (M, 3)")
+        if out is not None:
+            _require(isinstance(out, GridSegments) and out.shape == (M,) and out.segment.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        if out is None:
+            out = GridSegments(M, dev)
+        out._source = (self, voxel_labels, L, 1 if voxel_labels is None else num_class, connectivity)
+        if M == 0:
+            out.stats.zero_()
+            return out
+        lib = _lib.load()
+        need = int(lib.conv3p_grid_segments_workspace_bytes(M))
+        if out.workspace is None or out.workspace.numel() < need:
+            out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        neigh = self.neighbors()
+        with torch.cuda.device(dev):
+            _call(lib.conv3p_grid_segments, neigh.data_ptr(), _labels_pointer(voxel_labels, L, out.segment), L,
+                  self.voxel_count.data_ptr(),
+                  self.stats.data_ptr(), M, out._source[3], connectivity, out.segment.data_ptr(), out.root.data_ptr(),
+                  out.size.data_ptr(), out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr(),
+                  out.workspace.data_ptr(), out.workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def clean_labels(self, voxel_labels, num_class, min_size, connectivity=26, drop_orphans=False):
+        """voxel_labels with every segment of fewer than min_size voxels given the label that surrounds it -> int32 (M):
+        segments(voxel_labels, num_class, connectivity).absorb(min_size, drop_orphans).  One pass; run it again on the
+        result to absorb what the first pass left (GridSegments.absorb)."""
+        _require(isinstance(min_size, int) and not isinstance(min_size, bool) and 1 <= min_size < 2 ** 31,
+                 "min_size must be a positive integer")
+        _require(isinstance(drop_orphans, bool), "drop_orphans must be a bool")
+        return self.segments(voxel_labels, num_class, connectivity).absorb(min_size, drop_orphans)
+
+
+def _check_segment_arguments(voxel_labels, num_class, connectivity, M, dev):
+    """The argument checks of GridSubsample.segments -> L, the number of label words (0 without labels)."""
+    L = 0
+    if voxel_labels is not None:
+        _require(isinstance(voxel_labels, torch.Tensor) and voxel_labels.dtype == torch.int32 and voxel_labels.dim() == 1
+                 and voxel_labels.device == dev and voxel_labels.is_contiguous(),
+                 "voxel_labels must be a contiguous int32 (L,) tensor on the cloud's device, or None")
+        L = voxel_labels.numel()
+        _require(L <= M, "voxel_labels has more rows than the subsampling has voxels (%d)" % M)
+        _require(isinstance(num_class, int) and not isinstance(num_class, bool) and 1 <= num_class <= _lib.GRID_MAX_CLASS,
+                 "num_class must be an integer in [1, %d] with voxel_labels" % _lib.GRID_MAX_CLASS)
+    else:
+        _require(num_class is None or (isinstance(num_class, int) and not isinstance(num_class, bool)
+                                       and 1 <= num_class <= _lib.GRID_MAX_CLASS),
+                 "num_class must be None or an integer in [1, %d]" % _lib.GRID_MAX_CLASS)
+    _require(isinstance(connectivity, int) and not isinstance(connectivity, bool) and connectivity in (6, 18, 26),
+             "connectivity must be 6, 18 or 26")
+    return L
+
+
+def _labels_pointer(voxel_labels, L, stand_in):
+    """The labels' address for the C entries, where NULL means "no labels": an EMPTY labels tensor, whose own address may
+    be NULL, goes in as another valid address with L = 0, of which nothing is read."""
+    if voxel_labels is None:
+        return None
+    return voxel_labels.data_ptr() if L else stand_in.data_ptr()
+
+
+class GridSegments:
+    """The outputs of GridSubsample.segments, int32 (M) each: segment, the segment number of every voxel (-1: in none);
+    root, size (voxels), rows (raw rows: the members' voxel_count summed) and label per segment, -1 / 0 / 0 / -1 past the
+    last one; stats int32 (8) on the device = {segments, labelled voxels, unlabelled voxels below the emitted ones, filler
+    rows, largest size, largest rows, 0, 0}.  After absorb(): absorbed_label int32 (M), the label per segment behind the
+    clean-up, and absorb_stats int64 (4) = {small segments, absorbed, orphans, voxels whose label changed}."""
+
+    def __init__(self, num_voxels, device):
+        M = int(num_voxels)
+        self.shape = (M,)
+        self.segment = torch.empty((M,), dtype=torch.int32, device=device)
+        self.root = torch.empty((M,), dtype=torch.int32, device=device)
+        self.size = torch.empty((M,), dtype=torch.int32, device=device)
+        self.rows = torch.empty((M,), dtype=torch.int32, device=device)
+        self.label = torch.empty((M,), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((8,), dtype=torch.int32, device=device)
+        self.workspace = None
+        self.absorbed_label = None
+        self.absorb_stats = None
+        self._absorb_workspace = None
+        self._source = None
+
+    def num_segments(self):
+        """The number of segments: the one host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def trim(self):
+        """Views of the first num_segments() segment rows, as a GridSegments (segment and stats shared)."""
+        S = self.num_segments()
+        t = object.__new__(GridSegments)
+        t.shape = self.shape
+        t.segment, t.stats = self.segment, self.stats
+        t.root, t.size, t.rows, t.label = self.root[:S], self.size[:S], self.rows[:S], self.label[:S]
+        t.absorbed_label = self.absorbed_label[:S] if self.absorbed_label is not None else None
+        t.absorb_stats = self.absorb_stats
+        t.workspace = t._absorb_workspace = t._source = None
+        return t
+
+    def absorb(self, min_size, drop_orphans=False, out=None):
+        """One clean-up pass -> labels int32 (M): every segment of fewer than min_size voxels takes the label most of the
+        (member, tap) pairs around it vote for -- only segments that are not small vote, the lowest class wins a tie --
+        and one nobody votes for (an orphan) keeps its label, or takes -1 with drop_orphans (include/conv3p.h:
+        conv3p_grid_absorb_segments, rules A1-A4).  On the geometric segmentation (voxel_labels=None) every small segment
+        is an orphan, so drop_orphans=True marks floating clusters -1.  min_size=1 returns the labelled input.  Not
+        iterated: a small segment among small segments is an orphan; segment the result and absorb again for more.  Sets
+        absorbed_label and absorb_stats.  out: a contiguous int32 (M,) tensor.  Six launches whatever the data, nothing
+        synchronised on."""
+        _require(isinstance(min_size, int) and not isinstance(min_size, bool) and 1 <= min_size < 2 ** 31,
+                 "min_size must be a positive integer")
+        _require(isinstance(drop_orphans, bool), "drop_orphans must be a bool")
+        _require(self._source is not None, "absorb works on the object segments() returned, not on its trim()")
+        grid, voxel_labels, L, num_class, connectivity = self._source
+        dev = self.segment.device
+        M = self.shape[0]
+        _require(out is None or (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and tuple(out.shape) == (M,)
+                                 and out.device == dev and out.is_contiguous()),
+                 "out must be a contiguous int32 (M,) tensor on the cloud's device")
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        if out is None:
+            out = torch.empty((M,), dtype=torch.int32, device=dev)
+        if self.absorbed_label is None:
+            self.absorbed_label = torch.empty((M,), dtype=torch.int32, device=dev)
+            self.absorb_stats = torch.zeros((4,), dtype=torch.int64, device=dev)
+        if M == 0:
+            self.absorb_stats.zero_()
+            return out
+        lib = _lib.load()
+        need = int(lib.conv3p_grid_absorb_workspace_bytes(M))
+        if self._absorb_workspace is None or self._absorb_workspace.numel() < need:
+            self._absorb_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        neigh = grid.neighbors()
+        with torch.cuda.device(dev):
+            _call(lib.conv3p_grid_absorb_segments, neigh.data_ptr(), _labels_pointer(voxel_labels, L, self.segment), L,
+                  self.segment.data_ptr(),
+                  self.size.data_ptr(), self.label.data_ptr(), self.stats.data_ptr(), grid.stats.data_ptr(), M, num_class,
+                  connectivity, min_size, int(drop_orphans), out.data_ptr(), self.absorbed_label.data_ptr(),
+                  self.absorb_stats.data_ptr(), self._absorb_workspace.data_ptr(), self._absorb_workspace.numel(),
+                  torch.cuda.current_stream(dev).cuda_stream)
+        return out
 
 
 class GridNormals:
