@@ -14,6 +14,7 @@
 //   the generic forms of forward_kernel / backward_kernel (any channel counts, fp64)
 // The stateless entry points run the same kernels on the caller's scratch with force = 1.
 #include "../../include/conv3p.h"
+#include "conv3p_host.hpp"
 #include "conv3p_kernels.hpp"
 #include "conv3p_stack_fused.hpp"
 #include "conv3p_prestep.hpp"
@@ -48,9 +49,6 @@
 using namespace conv3p;
 
 namespace {
-
-constexpr size_t kAlign = 256;
-inline size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
 // ----------------------------------------------------------------------------- profiling
 enum Kind { K_PREP = 0, K_SEARCH, K_FORWARD, K_BACKWARD, K_REDUCE, K_SELU, K_SELU_GRAD, K_MEMSET,
@@ -223,9 +221,8 @@ Layout<T> carve(int B, int N, int ntiles, int ntap_max, int nslots, int pairs_pe
                 void *base)
 {
     Layout<T> L;
-    size_t off = 0;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *r = p ? p + off : nullptr; off += up(n); return r; };
+    Carver cv(base);
+    const size_t tiles = (size_t)B * ntiles;
     // hit masks take 512 B per candidate tile of a group; leave room for the [taps][65] populations
     int gmax = kGroupTiles;
     {
@@ -236,42 +233,40 @@ Layout<T> carve(int B, int N, int ntiles, int ntap_max, int nslots, int pairs_pe
     }
     L.gtiles = ntiles < gmax ? (ntiles > 0 ? ntiles : 1) : gmax;
     L.ngroups = ntiles > 0 ? (ntiles + L.gtiles - 1) / L.gtiles : 1;
-    L.hash = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * (size_t)B));
-    L.version = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B));
-    L.pts = reinterpret_cast<PointRec<T> *>(take(sizeof(PointRec<T>) * (size_t)B * ntiles * kTile));
-    L.boxes = reinterpret_cast<T *>(take(sizeof(T) * (size_t)B * ntiles * 6));
-    L.cmin = reinterpret_cast<T *>(take(sizeof(T) * (size_t)B * 3));
-    L.ftab = N <= kFusedMaxPoints
-                 ? reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * (size_t)B * ntiles * kFTableU64))
-                 : nullptr;
-    L.tab_version = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B));
-    L.tab_ticket = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B));
-    L.tab_inv = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B));
+    L.hash = cv.take<unsigned long long>((size_t)B);
+    L.version = cv.take<uint32_t>((size_t)B);
+    L.pts = cv.take<PointRec<T>>(tiles * kTile);
+    L.boxes = cv.take<T>(tiles * 6);
+    L.cmin = cv.take<T>((size_t)B * 3);
+    L.ftab = N <= kFusedMaxPoints ? cv.take<unsigned long long>(tiles * kFTableU64) : nullptr;
+    L.tab_version = cv.take<uint32_t>((size_t)B);
+    L.tab_ticket = cv.take<uint32_t>((size_t)B);
+    L.tab_inv = cv.take<uint32_t>((size_t)B);
     size_t ppc = (size_t)N * (size_t)pairs_per_point;
     if ((size_t)B * ppc > 0xFFFFFFF0ull) ppc = B ? 0xFFFFFFF0ull / (size_t)B : 0;
     if (ppc > 0x7FFFFFFFull) ppc = 0x7FFFFFFFull;   // headroom for the allocator's transient overshoot (search_tile P2)
     L.pairs_per_cloud = (uint32_t)ppc;
     L.slot.resize(nslots);
     L.nclouds = B;
-    L.cursor_all = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B * nslots * 2));
+    L.cursor_all = cv.take<uint32_t>((size_t)B * nslots * 2);
     for (int s = 0; s < nslots; ++s) {
         auto &S = L.slot[s];
-        S.built_version = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B));
+        S.built_version = cv.take<uint32_t>((size_t)B);
         S.cursor = L.cursor_all ? L.cursor_all + (size_t)(2 * s) * B : nullptr;
         S.ticket = L.cursor_all ? L.cursor_all + (size_t)(2 * s + 1) * B : nullptr;
-        S.built_tag = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * (size_t)B));
-        S.count = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * (size_t)B * N * ntap_max));
-        S.tcount = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * (size_t)B * ntiles * kTile * ntap_max));
-        S.segs = reinterpret_cast<uint2 *>(take(sizeof(uint2) * (size_t)B * ntiles * L.ngroups));
-        S.qsegs = reinterpret_cast<uint2 *>(take(sizeof(uint2) * (size_t)B * ntiles * L.ngroups * 64));
-        S.qbm = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)B * ntiles * 64 * (ntap_max > 64 ? 4 : ntap_max > 32 ? 2 : 1)));   // one plane per 32 taps (up to 128)
-        S.qbm_hi = ntap_max > 32 && S.qbm != nullptr ? S.qbm + (size_t)B * ntiles * 64 : nullptr;
-        S.sched = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * 8 * (size_t)((B + 7) / 8) * ntiles));
-        S.regime = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t)));
-        S.pairs = reinterpret_cast<PairEntry *>(take(sizeof(PairEntry) * (size_t)B * ppc));
+        S.built_tag = cv.take<unsigned long long>((size_t)B);
+        S.count = cv.take<int32_t>((size_t)B * N * ntap_max);
+        S.tcount = cv.take<int32_t>(tiles * kTile * ntap_max);
+        S.segs = cv.take<uint2>(tiles * L.ngroups);
+        S.qsegs = cv.take<uint2>(tiles * L.ngroups * 64);
+        S.qbm = cv.take<uint32_t>(tiles * 64 * (ntap_max > 64 ? 4 : ntap_max > 32 ? 2 : 1));   // one plane per 32 taps (up to 128)
+        S.qbm_hi = ntap_max > 32 && S.qbm != nullptr ? S.qbm + tiles * 64 : nullptr;
+        S.sched = cv.take<uint32_t>(8 * (size_t)((B + 7) / 8) * ntiles);
+        S.regime = cv.take<uint32_t>(1);
+        S.pairs = cv.take<PairEntry>((size_t)B * ppc);
     }
-    L.partials = reinterpret_cast<T *>(take(scratch_bytes));
-    L.bytes = off;
+    L.partials = reinterpret_cast<T *>(cv.take<char>(scratch_bytes));
+    L.bytes = cv.bytes();
     return L;
 }
 
@@ -338,14 +333,30 @@ inline bool wide_shape(int elem, int cin, int cout)
 {
     return elem == 4 && cin >= 1 && cout >= 1 && (cin > kWideBlk || cout > kWideBlk);
 }
-inline size_t wide_scratch_bytes(const Dims &d, size_t pair_slots, bool forward_only = false)
+struct WideScratch {
+    float *xp, *yp, *zp;   // [B N][256] packed rows: block input, block grad_out (backward), block result
+    float *wp, *dwp;       // [ntap][256][256] packed filter block, its grad_filter block
+};
+// forward_part: the packs follow the forward's part of the block scratch only
+inline size_t carve_wide_scratch(const Dims &d, size_t pair_slots, bool forward_part, void *base, WideScratch &w)
 {
     Dims db = d;
     db.Cin = kWideBlk;    // (blocks are padded to 128 or 256 channels: sized for the largest)
     db.Cout = kWideBlk;
     const size_t rows = (size_t)d.B * d.N;
-    return up(forward_only ? deep_forward_bytes(db, pair_slots) : deep_scratch_bytes(db, pair_slots)) + 3 * up(rows * kWideBlk * 4) +
-           2 * up((size_t)d.ntap * kWideBlk * kWideBlk * 4);
+    Carver cv(base);
+    (void)cv.take<char>(forward_part ? deep_forward_bytes(db, pair_slots) : deep_scratch_bytes(db, pair_slots));
+    w.xp = cv.take<float>(rows * kWideBlk);
+    w.yp = cv.take<float>(rows * kWideBlk);
+    w.zp = cv.take<float>(rows * kWideBlk);
+    w.wp = cv.take<float>((size_t)d.ntap * kWideBlk * kWideBlk);
+    w.dwp = cv.take<float>((size_t)d.ntap * kWideBlk * kWideBlk);
+    return cv.bytes();
+}
+inline size_t wide_scratch_bytes(const Dims &d, size_t pair_slots, bool forward_only = false)
+{
+    WideScratch w;
+    return carve_wide_scratch(d, pair_slots, forward_only, nullptr, w);
 }
 
 // fp64 layers outside the register-path shapes (round 4): blocks of 16 input x 8 output channels, zero-padded, on the
@@ -368,10 +379,27 @@ constexpr int kF64BwdKi = CONV3P_F64_BWD_KI, kF64BwdCo = CONV3P_F64_BWD_CO;   //
 constexpr int kF64Ki = kF64FwdKi > kF64BwdKi ? kF64FwdKi : kF64BwdKi;         // (scratch: sized for the larger of the two)
 constexpr int kF64Co = kF64FwdCo > kF64BwdCo ? kF64FwdCo : kF64BwdCo;
 constexpr int kF64Row = kF64Ki > kF64Co ? kF64Ki : kF64Co;
-inline size_t f64_blocked_bytes(const Dims &d)
+struct F64Scratch {
+    double *parts;          // the block kernel's grad_filter partials
+    double *xp, *yp, *zp;   // packed rows: input block [B N][16], grad_out block / forward result [B N][8], grad_input block [B N][16]
+    double *wp, *dwp;       // [ntap][16][8] filter block, its grad_filter block
+};
+inline size_t carve_f64_scratch(const Dims &d, void *base, F64Scratch &w)
 {
     const size_t rows = (size_t)d.B * d.N, nwb = (size_t)d.ntap * kF64Ki * kF64Co;
-    return up((size_t)grid_of(make_blockmap(d)) * nwb * 8) + 3 * up(rows * kF64Row * 8) + 2 * up(nwb * 8);
+    Carver cv(base);
+    w.parts = cv.take<double>((size_t)grid_of(make_blockmap(d)) * nwb);
+    w.xp = cv.take<double>(rows * kF64Row);
+    w.yp = cv.take<double>(rows * kF64Row);
+    w.zp = cv.take<double>(rows * kF64Row);
+    w.wp = cv.take<double>(nwb);
+    w.dwp = cv.take<double>(nwb);
+    return cv.bytes();
+}
+inline size_t f64_blocked_bytes(const Dims &d)
+{
+    F64Scratch w;
+    return carve_f64_scratch(d, nullptr, w);
 }
 
 // The transform + gather forward's scratch (conv3p_forward_taps.hpp): Z [B N][ntap][16] floats.
@@ -379,16 +407,9 @@ inline size_t tap_forward_bytes(const Dims &d) { return (size_t)d.B * d.N * (siz
 
 bool cache_cfg_ok(const conv3p_cache_config *cfg);
 
-int hip_ok()
-{
-    return hipGetLastError() == hipSuccess ? CONV3P_OK : CONV3P_ERR_LAUNCH;
-}
-
 template <typename T> size_t lds_common(const Stencil<T> &st) { return (3 * (size_t)st.maxfull * 2 + 15) & ~(size_t)15; }
 inline size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kMaxLds = 160 * 1024;
-
-#define TRY(expr) do { int rc_ = (expr); if (rc_ != CONV3P_OK) return rc_; } while (0)
 
 // Everything one call needs.
 template <typename T> struct Call {
@@ -980,37 +1001,36 @@ struct DeepScratch {   // carved from the per-call scratch region
 DeepScratch carve_deep(const Dims &d, size_t pair_slots, void *base, int which, size_t *order_bytes = nullptr, size_t *forward_bytes = nullptr)
 {
     DeepScratch s{};
-    size_t off = 0;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *r = p ? p + off : nullptr; off += up(n); return r; };
+    Carver cv(base);
     const size_t nw = (size_t)d.ntap * d.Cin * d.Cout;
     const size_t cip = (size_t)deep_pad(d.Cin), cop = (size_t)deep_pad(d.Cout);
+    const size_t tiles = (size_t)d.B * d.ntiles;
     s.sched_cap = ((d.B + 7) / 8) * d.ntiles;
     for (int w = 0; w < 2; ++w) {
-        uint2 *tap_meta = reinterpret_cast<uint2 *>(take(pair_slots * 8));
-        uint32_t *tap_off = reinterpret_cast<uint32_t *>(take((size_t)d.B * d.ntiles * (d.ntap + 1) * 4));
-        uint8_t *tile_flag = reinterpret_cast<uint8_t *>(take((size_t)d.B * d.ntiles));
-        uint4 *tap_split = reinterpret_cast<uint4 *>(take((size_t)d.B * d.ntiles * d.ntap * 16));
-        uint32_t *sched = reinterpret_cast<uint32_t *>(take((size_t)8 * s.sched_cap * 4));
-        uint2 *dsegs = reinterpret_cast<uint2 *>(take((size_t)d.B * d.ntiles * 8));
-        uint32_t *meta_cursor = reinterpret_cast<uint32_t *>(take((size_t)d.B * 4));
+        uint2 *tap_meta = cv.take<uint2>(pair_slots);
+        uint32_t *tap_off = cv.take<uint32_t>(tiles * (d.ntap + 1));
+        uint8_t *tile_flag = cv.take<uint8_t>(tiles);
+        uint4 *tap_split = cv.take<uint4>(tiles * d.ntap);
+        uint32_t *sched = cv.take<uint32_t>((size_t)8 * s.sched_cap);
+        uint2 *dsegs = cv.take<uint2>(tiles);
+        uint32_t *meta_cursor = cv.take<uint32_t>((size_t)d.B);
         if (w == which) {
             s.tap_meta = tap_meta; s.tap_off = tap_off; s.tile_flag = tile_flag; s.tap_split = tap_split;
             s.sched = sched; s.dsegs = dsegs; s.meta_cursor = meta_cursor;
         }
     }
     // backward only
-    s.pop_mask = reinterpret_cast<unsigned long long *>(take((size_t)d.B * d.ntiles * 8));
-    s.tap_cmask = reinterpret_cast<unsigned long long *>(take((size_t)d.B * d.ntiles * d.ntap * 8));
-    s.tap_total = reinterpret_cast<uint32_t *>(take(65 * 4));
-    s.tap_rng = reinterpret_cast<uint2 *>(take(64 * 8));
-    s.items = reinterpret_cast<uint4 *>(take((size_t)(kDwItems + 64) * 16));
-    if (order_bytes) *order_bytes = off;
-    s.wt = reinterpret_cast<float *>(take((size_t)d.ntap * cip * cop * 4));
-    if (forward_bytes) *forward_bytes = off;   // everything below is the backward's (work-item partials, the G tiles)
-    s.partials = reinterpret_cast<float *>(take((size_t)(kDwItems + 64) * cip * cop * 4 + nw * 4));
-    s.gbuf = reinterpret_cast<float *>(take((size_t)d.B * d.ntiles * d.ntap * 64 * cop * 4));
-    s.bytes = off;
+    s.pop_mask = cv.take<unsigned long long>(tiles);
+    s.tap_cmask = cv.take<unsigned long long>(tiles * d.ntap);
+    s.tap_total = cv.take<uint32_t>(65);
+    s.tap_rng = cv.take<uint2>(64);
+    s.items = cv.take<uint4>((size_t)(kDwItems + 64));
+    if (order_bytes) *order_bytes = cv.bytes();
+    s.wt = cv.take<float>((size_t)d.ntap * cip * cop);
+    if (forward_bytes) *forward_bytes = cv.bytes();   // everything below is the backward's (work-item partials, the G tiles)
+    s.partials = cv.take<float>((size_t)(kDwItems + 64) * cip * cop + nw);
+    s.gbuf = cv.take<float>(tiles * d.ntap * 64 * cop);
+    s.bytes = cv.bytes();
     return s;
 }
 
@@ -1212,28 +1232,15 @@ inline bool deep_class(int elem, int cin, int cout, int &cip, int &cop)
 // A block of kw <= 256 channels is packed into rows of 128 or 256 floats, zero-filled past kw: every block then IS one of
 // the instantiated shapes {128, 256}^2 with full rows (the kernels' fast path), whatever the layer's channel counts.
 inline int wide_pad(int n) { return n <= 128 ? 128 : 256; }
-struct WideScratch {
-    float *xp, *yp, *zp;   // [B N][256] packed rows: block input, block grad_out (backward), block result
-    float *wp, *dwp;       // [ntap][256][256] packed filter block, its grad_filter block
-};
 inline WideScratch carve_wide(const Call<float> &c, bool forward_only = false)
 {
     const Dims &d = c.d;
-    Dims db = d;
-    db.Cin = kWideBlk;
-    db.Cout = kWideBlk;
-    const size_t rows = (size_t)d.B * d.N;
     // (a forward-only workspace ends after the forward's part of the block scratch: the packs follow that; a cache sized
     // for the backward keeps ONE placement for both passes)
     const size_t slots = (size_t)d.B * c.L.pairs_per_cloud;
     const bool forward_part = forward_only && c.scratch < wide_scratch_bytes(d, slots);
-    char *p = reinterpret_cast<char *>(c.L.partials) + up(forward_part ? deep_forward_bytes(db, slots) : deep_scratch_bytes(db, slots));
     WideScratch w{};
-    w.xp = reinterpret_cast<float *>(p); p += up(rows * kWideBlk * 4);
-    w.yp = reinterpret_cast<float *>(p); p += up(rows * kWideBlk * 4);
-    w.zp = reinterpret_cast<float *>(p); p += up(rows * kWideBlk * 4);
-    w.wp = reinterpret_cast<float *>(p); p += up((size_t)d.ntap * kWideBlk * kWideBlk * 4);
-    w.dwp = reinterpret_cast<float *>(p);
+    (void)carve_wide_scratch(d, slots, forward_part, c.L.partials, w);
     return w;
 }
 inline unsigned grid_1d(size_t n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
@@ -1329,23 +1336,10 @@ int wide_backward(const Call<float> &c, const Route &r, const float *grad_out, c
 }
 
 // ----------------------------------------------------------------------------- fp64 layers outside the register-path shapes
-struct F64Scratch {
-    double *parts;          // the block kernel's grad_filter partials
-    double *xp, *yp, *zp;   // packed rows: input block [B N][16], grad_out block / forward result [B N][8], grad_input block [B N][16]
-    double *wp, *dwp;       // [ntap][16][8] filter block, its grad_filter block
-};
 inline F64Scratch carve_f64(const Call<double> &c)
 {
-    const Dims &d = c.d;
-    const size_t rows = (size_t)d.B * d.N, nwb = (size_t)d.ntap * kF64Ki * kF64Co;
-    char *p = reinterpret_cast<char *>(c.L.partials);
     F64Scratch w{};
-    w.parts = reinterpret_cast<double *>(p); p += up((size_t)grid_of(make_blockmap(d)) * nwb * 8);
-    w.xp = reinterpret_cast<double *>(p); p += up(rows * kF64Row * 8);
-    w.yp = reinterpret_cast<double *>(p); p += up(rows * kF64Row * 8);
-    w.zp = reinterpret_cast<double *>(p); p += up(rows * kF64Row * 8);
-    w.wp = reinterpret_cast<double *>(p); p += up(nwb * 8);
-    w.dwp = reinterpret_cast<double *>(p);
+    (void)carve_f64_scratch(c.d, c.L.partials, w);
     return w;
 }
 inline int f64_pack_rows(const Call<double> &c, const double *src, int ld_s, double *dst, size_t rows, int cols, int ldp)
@@ -1445,13 +1439,6 @@ int f64_blocked_backward(const Call<double> &c, const Route &r, const double *gr
     if (r.co == kF64BwdCo) return f64_blocked_backward_co<kF64BwdCo>(c, r, grad_out, input, filter, grad_input, grad_filter);
     if (r.co == 4) return f64_blocked_backward_co<4>(c, r, grad_out, input, filter, grad_input, grad_filter);
     return f64_blocked_backward_co<2>(c, r, grad_out, input, filter, grad_input, grad_filter);
-}
-
-int buf_check(const void *p, size_t have, size_t need)
-{
-    if (need == 0) return CONV3P_OK;
-    if (!p || (reinterpret_cast<uintptr_t>(p) % kAlign) != 0 || have < need) return CONV3P_ERR_WORKSPACE;
-    return CONV3P_OK;
 }
 
 // ----------------------------------------------------------------------------- the planners
@@ -2196,11 +2183,17 @@ size_t cache_scratch_bytes(int elem, int B, int N, int max_taps, int max_Cin, in
 
 Where stateless(void *ws, size_t bytes) { return Where{ws, bytes, false, 1, 0, kDefaultPairsPerPoint, 0, 0}; }
 
-Where persistent(int elem, int B, int N, void *cache, size_t bytes, int slots, int max_taps, int ppp, int max_Cin,
-                 int max_Cout, int flags)
+// the caller's hints about the lists' lengths: what the stack's calls pass on of cfg->flags
+inline int hints(const conv3p_cache_config *cfg)
 {
-    return Where{cache, bytes, true, slots, max_taps, ppp > 0 ? ppp : kDefaultPairsPerPoint,
-                 cache_scratch_bytes(elem, B, N, max_taps, max_Cin, max_Cout, ppp > 0 ? ppp : kDefaultPairsPerPoint), flags};
+    return cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS);
+}
+// flags: CONV3P_CACHE_* of this call (cfg->flags is the caller's to pass on or not)
+Where persistent(int elem, int B, int N, void *cache, size_t bytes, const conv3p_cache_config *cfg, int flags)
+{
+    const int ppp = cfg->pairs_per_point > 0 ? cfg->pairs_per_point : kDefaultPairsPerPoint;
+    return Where{cache, bytes, true, cfg->slots, cfg->max_taps, ppp,
+                 cache_scratch_bytes(elem, B, N, cfg->max_taps, cfg->max_Cin, cfg->max_Cout, ppp), flags};
 }
 
 
@@ -2255,17 +2248,14 @@ int stack_geometry(const conv3p_stack_desc *sd, const T *points, T voxel, int B,
                 dup |= strides[3 * m] == sd->strides[l][0] && strides[3 * m + 1] == sd->strides[l][1] && strides[3 * m + 2] == sd->strides[l][2];
             if (!dup) { strides[3 * k] = sd->strides[l][0]; strides[3 * k + 1] = sd->strides[l][1]; strides[3 * k + 2] = sd->strides[l][2]; ++k; }
         }
-        const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                                    cfg->max_Cin, cfg->max_Cout, 0);
+        const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, 0);
         TRY(prepare_multi_impl<T>(points, strides, k, voxel, B, N, sd->fz, sd->fy, sd->fx, wh, s));
         for (int l = 0; l < nl; ++l)
             if (hipEventRecord(ev[l], s) != hipSuccess) return CONV3P_ERR_LAUNCH;
     } else
     for (int l = 0; l < nl; ++l) {
-        conv3p_cache_config c2 = *cfg;
-        c2.flags = (l > 0 ? CONV3P_CACHE_POINTS_UNCHANGED : 0) | (cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS));
-        const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, c2.slots, c2.max_taps, c2.pairs_per_point,
-                                    c2.max_Cin, c2.max_Cout, c2.flags);
+        const int flags = (l > 0 ? CONV3P_CACHE_POINTS_UNCHANGED : 0) | hints(cfg);
+        const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, flags);
         TRY(prepare_impl<T>(points, sd->strides[l], voxel, B, N, sd->fz, sd->fy, sd->fx, wh, s));
         if (hipEventRecord(ev[l], s) != hipSuccess) return CONV3P_ERR_LAUNCH;
     }
@@ -2414,6 +2404,15 @@ bool stack_fusable(const conv3p_stack_desc *sd, T voxel, int B, int N, const con
     }
 }
 
+// The fused forward's hand-off buffers in the cache's scratch: hand[l], l < n_hidden - 1, the dense copy of hidden layer
+// l's activation that layer l + 1 gathers (a buffer of its own: no stale L1 line)
+template <typename T> size_t carve_handoff(const conv3p_stack_desc *sd, size_t rows, void *base, T **hand)
+{
+    Carver cv(base);
+    for (int l = 0; l + 1 < sd->n_hidden; ++l) hand[l] = cv.take<T>(rows * (size_t)sd->hidden);
+    return cv.bytes();
+}
+
 // forward of the hidden layers in ONE launch.  CONV3P_ERR_UNSUPPORTED (nothing enqueued, nothing recorded): take the per-layer path.
 template <typename T>
 int stack_forward_fused(const conv3p_stack_desc *sd, const T *points, const T *input, const T *const *filters, T voxel, int B, int N,
@@ -2424,10 +2423,10 @@ int stack_forward_fused(const conv3p_stack_desc *sd, const T *points, const T *i
     } else {
         const int nh = sd->n_hidden, H = sd->hidden, CW = nh * H;
         const size_t rows = (size_t)B * N;
-        const size_t handoff = up(rows * H * sizeof(T));
-        const Where wh0 = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                                     cfg->max_Cin, cfg->max_Cout, 0);
-        if ((cfg->flags & CONV3P_CACHE_FUSED_FORWARD) == 0 || !stack_fusable<T>(sd, voxel, B, N, cfg, handoff * (size_t)(nh - 1), wh0.scratch_cap))
+        T *hand[CONV3P_STACK_MAX_LAYERS];
+        const size_t handoff = carve_handoff<T>(sd, rows, nullptr, hand);
+        const Where wh0 = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, 0);
+        if ((cfg->flags & CONV3P_CACHE_FUSED_FORWARD) == 0 || !stack_fusable<T>(sd, voxel, B, N, cfg, handoff, wh0.scratch_cap))
             return CONV3P_ERR_UNSUPPORTED;
         const FusedDevice &fd = fused_device();
         const int ntiles = (N + kTile - 1) / kTile;
@@ -2451,14 +2450,12 @@ int stack_forward_fused(const conv3p_stack_desc *sd, const T *points, const T *i
         // from here on the cache's host record is touched exactly as the per-layer calls would touch it
         StackFwdArgs<T> a{};
         for (int l = 0; l < nh; ++l) {
-            const int flags = ((l > 0 || geometry_enqueued) ? CONV3P_CACHE_POINTS_UNCHANGED : 0) |
-                              (cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS));
-            const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                                        cfg->max_Cin, cfg->max_Cout, flags);
+            const int flags = ((l > 0 || geometry_enqueued) ? CONV3P_CACHE_POINTS_UNCHANGED : 0) | hints(cfg);
+            const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, flags);
             Dims d = d0;
             d.Cin = l == 0 ? sd->in_channels : H;
             Call<T> c;
-            TRY(begin_call<T>(c, d, sd->strides[l], voxel, handoff * (size_t)(nh - 1), wh, s));
+            TRY(begin_call<T>(c, d, sd->strides[l], voxel, handoff, wh, s));
             TRY(run_prep<T>(points, c));
             TRY(run_cloud_min<T>(points, c));
             TRY(run_search<T>(c, c.L.slot[c.slot].count, true));
@@ -2466,12 +2463,11 @@ int stack_forward_fused(const conv3p_stack_desc *sd, const T *points, const T *i
             StackFwdLayer<T> &L = a.layer[l];
             L.st = c.st;
             L.count = S.count; L.tcount = S.tcount; L.pairs = S.pairs; L.segs = S.segs; L.qsegs = S.qsegs;
-            char *hand = reinterpret_cast<char *>(c.L.partials);
-            // layer l gathers the dense hand-off copy of layer l - 1's activation (a buffer of its own: no stale L1 line)
-            L.input = l == 0 ? input : reinterpret_cast<const T *>(hand + handoff * (size_t)(l - 1));
+            (void)carve_handoff<T>(sd, rows, c.L.partials, hand);
+            L.input = l == 0 ? input : hand[l - 1];
             L.filter = filters[l];
             L.output = concat + (size_t)H * l;
-            L.out2 = l + 1 < nh ? reinterpret_cast<T *>(hand + handoff * (size_t)l) : nullptr;
+            L.out2 = l + 1 < nh ? hand[l] : nullptr;
             L.ld_out2 = H;
             L.ld = RowLd{l == 0 ? sd->in_channels : H, CW, H, d.Cin, d.Cin};
             if (l == 0) {
@@ -2538,10 +2534,10 @@ int stack_forward_impl(const conv3p_stack_desc *sd, const T *points, const T *in
     // the hidden layers as ONE launch (conv3p_stack_fused.hpp) where the stack, the cache and the device allow it
     int first = 0;
     {
-        const Where wh0 = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                                     cfg->max_Cin, cfg->max_Cout, 0);
+        const Where wh0 = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, 0);
+        T *hand[CONV3P_STACK_MAX_LAYERS];
         if ((cfg->flags & CONV3P_CACHE_FUSED_FORWARD) != 0 &&
-            stack_fusable<T>(sd, voxel, B, N, cfg, up((size_t)B * N * sd->hidden * sizeof(T)) * (size_t)(sd->n_hidden - 1), wh0.scratch_cap)) {
+            stack_fusable<T>(sd, voxel, B, N, cfg, carve_handoff<T>(sd, (size_t)B * N, nullptr, hand), wh0.scratch_cap)) {
             if (events && !prefetched && hipStreamWaitEvent(main, ev[sd->n_hidden - 1], 0) != hipSuccess) return CONV3P_ERR_LAUNCH;
             const int rc = stack_forward_fused<T>(sd, points, input, filters, voxel, B, N, concat, cache, cache_bytes, cfg, main, events);
             if (rc == CONV3P_OK) first = sd->n_hidden;
@@ -2550,17 +2546,14 @@ int stack_forward_impl(const conv3p_stack_desc *sd, const T *points, const T *in
     }
     for (int l = first; l < nl; ++l) {
         if (events && !prefetched && hipStreamWaitEvent(main, ev[l], 0) != hipSuccess) return CONV3P_ERR_LAUNCH;
-        conv3p_cache_config c2 = *cfg;
-        c2.flags = ((l > 0 || events) ? CONV3P_CACHE_POINTS_UNCHANGED : 0) |   // the first call of a step re-validates
-                   (cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS));
+        const int flags = ((l > 0 || events) ? CONV3P_CACHE_POINTS_UNCHANGED : 0) | hints(cfg);   // the first call of a step re-validates
         const bool head = l == sd->n_hidden;
         const int Cin = head ? CW : (l == 0 ? sd->in_channels : sd->hidden);
         const int Cout = head ? sd->num_class : sd->hidden;
         const T *x = head ? concat : (l == 0 ? input : concat + (size_t)sd->hidden * (l - 1));
         T *y = head ? head_out : concat + (size_t)sd->hidden * l;
         const RowLd ld{head ? CW : (l == 0 ? sd->in_channels : CW), head ? sd->num_class : CW, 0, 0, 0};
-        const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, c2.slots, c2.max_taps, c2.pairs_per_point,
-                                    c2.max_Cin, c2.max_Cout, c2.flags);
+        const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, flags);
         if (!filters[l]) return CONV3P_ERR_INVALID_ARGUMENT;
         TRY(forward_impl<T>(points, x, filters[l], sd->strides[l], voxel, B, N, Cin, Cout, sd->fz, sd->fy, sd->fx, y, wh,
                             stream, /*act=*/true, &ld));
@@ -2568,27 +2561,40 @@ int stack_forward_impl(const conv3p_stack_desc *sd, const T *points, const T *in
     return CONV3P_OK;
 }
 
-// bytes of layer l's grad_filter partials (one per backward workgroup)
-template <typename T> size_t stack_region_bytes(const conv3p_stack_desc *sd, int l, int B, int N)
+// values of layer l's grad_filter partials (one copy per backward workgroup)
+inline size_t stack_region_elems(const conv3p_stack_desc *sd, int l, int B, int N)
 {
     const bool head = l == sd->n_hidden;
     const int Cin = head ? sd->n_hidden * sd->hidden : (l == 0 ? sd->in_channels : sd->hidden);
     const int Cout = head ? sd->num_class : sd->hidden;
     Dims d{B, N, Cin, Cout, sd->fz, sd->fy, sd->fx, sd->fz * sd->fy * sd->fx, (N + kTile - 1) / kTile};
-    return up((size_t)d.ntap * Cin * Cout * (size_t)grid_of(make_blockmap(d)) * sizeof(T));
+    return (size_t)d.ntap * Cin * Cout * (size_t)grid_of(make_blockmap(d));
 }
 
-template <typename T> size_t stack_scratch_bytes(const conv3p_stack_desc *sd, int B, int N)
+// The stack backward's scratch.
+template <typename T> struct StackScratch {
+    T *ga, *gb;                                  // two ping-pong gradient buffers
+    T *dconcat;                                  // the head's gradient w.r.t. the concat
+    T *region[CONV3P_STACK_MAX_LAYERS + 1];      // every layer's grad_filter partials
+    T *G[CONV3P_STACK_MAX_LAYERS];               // the fused launch's gradient hand-off buffers, one per hidden layer
+                                                 // (conv3p_stack_fused.hpp: every layer's rows in a buffer of their own)
+};
+template <typename T> size_t carve_stack(const conv3p_stack_desc *sd, int B, int N, void *base, StackScratch<T> &w)
 {
     const size_t rows = (size_t)B * N;
     const size_t wide = (size_t)(sd->hidden > sd->num_class ? sd->hidden : sd->num_class);
-    // two ping-pong gradient buffers + the head's gradient w.r.t. the concat + every layer's grad_filter partials
-    size_t b = up(rows * wide * sizeof(T)) * 2 + up(rows * (size_t)sd->n_hidden * sd->hidden * sizeof(T));
-    for (int l = 0; l < stack_layers(sd); ++l) b += stack_region_bytes<T>(sd, l, B, N);
-    // + the fused launch's gradient hand-off buffers, one per hidden layer (conv3p_stack_fused.hpp: every layer's rows in a
-    // buffer of their own)
-    b += up(rows * (size_t)sd->hidden * sizeof(T)) * (size_t)sd->n_hidden;
-    return b;
+    Carver cv(base);
+    w.ga = cv.take<T>(rows * wide);
+    w.gb = cv.take<T>(rows * wide);
+    w.dconcat = cv.take<T>(rows * (size_t)sd->n_hidden * sd->hidden);
+    for (int l = 0; l < stack_layers(sd); ++l) w.region[l] = cv.take<T>(stack_region_elems(sd, l, B, N));
+    for (int l = 0; l < sd->n_hidden; ++l) w.G[l] = cv.take<T>(rows * (size_t)sd->hidden);
+    return cv.bytes();
+}
+template <typename T> size_t stack_scratch_bytes(const conv3p_stack_desc *sd, int B, int N)
+{
+    StackScratch<T> w;
+    return carve_stack<T>(sd, B, N, nullptr, w);
 }
 
 
@@ -2605,8 +2611,7 @@ int stack_backward_fused(const conv3p_stack_desc *sd, const T *points, const T *
     } else {
         const int nh = sd->n_hidden, H = sd->hidden, CW = nh * H;
         if ((cfg->flags & CONV3P_CACHE_SPARSE_NEIGHBOURHOODS) == 0 || (cfg->flags & CONV3P_CACHE_FUSED_BACKWARD) == 0) return CONV3P_ERR_UNSUPPORTED;
-        const Where wh0 = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                                     cfg->max_Cin, cfg->max_Cout, 0);
+        const Where wh0 = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, 0);
         if (!stack_fusable<T>(sd, voxel, B, N, cfg, 0, wh0.scratch_cap)) return CONV3P_ERR_UNSUPPORTED;
         const FusedDevice &fd = fused_device();
         const int ntiles = (N + kTile - 1) / kTile;
@@ -2627,9 +2632,7 @@ int stack_backward_fused(const conv3p_stack_desc *sd, const T *points, const T *
         StackBwdArgs<T> a{};
         int k = 0;
         for (int l = nh - 1; l >= 1; --l, ++k) {
-            const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                                        cfg->max_Cin, cfg->max_Cout,
-                                        CONV3P_CACHE_POINTS_UNCHANGED | (cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS)));
+            const Where wh = persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, CONV3P_CACHE_POINTS_UNCHANGED | hints(cfg));
             Call<T> c;
             TRY(begin_call<T>(c, d, sd->strides[l], voxel, backward_scratch_bytes(d, (int)sizeof(T), wh.ppp), wh, s));
             TRY(run_prep<T>(points, c));
@@ -2700,26 +2703,17 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
         return CONV3P_ERR_INVALID_ARGUMENT;
     if (has_head && grad_concat) return CONV3P_ERR_UNSUPPORTED;   // (see conv3p.h: not needed by either model) -- before any launch
     TRY(stack_backward_fits<T>(sd, voxel, B, N));
-    TRY(buf_check(scratch, scratch_bytes, stack_scratch_bytes<T>(sd, B, N)));
+    StackScratch<T> ws;
+    TRY(buf_check(scratch, scratch_bytes, carve_stack<T>(sd, B, N, scratch, ws)));
     const size_t rows = (size_t)B * N;
     const int H = sd->hidden, CW = sd->n_hidden * H, nh = sd->n_hidden;
-    const size_t wide = (size_t)(H > sd->num_class ? H : sd->num_class);
-    char *sp = static_cast<char *>(scratch);
-    T *ga = reinterpret_cast<T *>(sp);
-    T *gb = reinterpret_cast<T *>(sp + up(rows * wide * sizeof(T)));
-    T *dconcat = reinterpret_cast<T *>(sp + 2 * up(rows * wide * sizeof(T)));
+    T *ga = ws.ga, *gb = ws.gb, *dconcat = ws.dconcat;
     // every layer leaves its grad_filter partials in its own region.  The per-layer path: a layer's partials are summed by
     // rider workgroups of the NEXT layer's launch (reduce_rider: stream order makes them complete and visible there), and
     // one closing launch reduces what no launch carried -- the first layer's, and those of layers on other kernels; so the
     // chain of dependent backward kernels is not interleaved with reductions
     DeferredReduce<T> red[CONV3P_STACK_MAX_LAYERS + 1];
-    {
-        char *rp = sp + 2 * up(rows * wide * sizeof(T)) + up(rows * (size_t)CW * sizeof(T));
-        for (int l = 0; l < stack_layers(sd); ++l) {
-            red[l].region = reinterpret_cast<T *>(rp);
-            rp += stack_region_bytes<T>(sd, l, B, N);
-        }
-    }
+    for (int l = 0; l < stack_layers(sd); ++l) red[l].region = ws.region[l];
     auto reduce_all = [&]() -> int {
         ReduceJobs<T> jobs{};
         int nj = 0;
@@ -2743,9 +2737,7 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
         return hip_ok();
     };
     auto where = [&]() {
-        return persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point,
-                          cfg->max_Cin, cfg->max_Cout,
-                          CONV3P_CACHE_POINTS_UNCHANGED | (cfg->flags & (CONV3P_CACHE_SPARSE_NEIGHBOURHOODS | CONV3P_CACHE_DENSE_NEIGHBOURHOODS)));
+        return persistent((int)sizeof(T), B, N, cache, cache_bytes, cfg, CONV3P_CACHE_POINTS_UNCHANGED | hints(cfg));
     };
     int pending = -1;   // the layer whose partials wait for a launch to ride in
     auto ride = [&](int l) {
@@ -2770,10 +2762,7 @@ int stack_backward_impl(const conv3p_stack_desc *sd, const T *points, const T *i
     }
     // the hidden layers nh-1 .. 1 as ONE launch (conv3p_stack_fused.hpp) where the stack, the cache and the device allow it
     {
-        T *G[CONV3P_STACK_MAX_LAYERS];
-        char *gp = sp + 2 * up(rows * wide * sizeof(T)) + up(rows * (size_t)CW * sizeof(T));
-        for (int l = 0; l < stack_layers(sd); ++l) gp += stack_region_bytes<T>(sd, l, B, N);
-        for (int l = 0; l < nh; ++l) G[l] = reinterpret_cast<T *>(gp + up(rows * (size_t)H * sizeof(T)) * (size_t)l);
+        T *const *G = ws.G;
         const int rc = stack_backward_fused<T>(sd, points, filters, voxel, B, N, concat, ext, ld_ext, G, red, grad_filters, cache, cache_bytes,
                                                cfg, static_cast<hipStream_t>(stream));
         if (rc == CONV3P_OK) {
@@ -2813,270 +2802,6 @@ bool cache_cfg_ok(const conv3p_cache_config *cfg)
            cfg->max_Cin >= 0 && cfg->max_Cout >= 0;
 }
 
-// ----------------------------------------------------------------------------- the segmentation head
-// Waves per workgroup and grid of one segmentation-head call.  A (T, C) is supported when four wave tiles and the
-// counters fit in the CU's LDS (one wave per SIMD at least: fp32 up to 128 classes, fp64 up to 79); the workgroup is
-// four waves while that leaves three or more workgroups per CU (13 classes: 13.5 KB, 41: 42.5 KB), then two, then one.
-struct SegPlan { int nw; unsigned grid; size_t lds, part_bytes; };
-template <typename T> bool seg_plan(size_t rows, int C, SegPlan &p)
-{
-    if (C > kSegMaxClass || seg_lds_bytes<T>(4, C) > kMaxLds) return false;
-    p.nw = seg_lds_bytes<T>(4, C) <= 48 * 1024 ? 4 : seg_lds_bytes<T>(2, C) <= 48 * 1024 ? 2 : 1;
-    p.lds = seg_lds_bytes<T>(p.nw, C);
-    const size_t tiles = (rows + 63) / 64, wgs = (tiles + p.nw - 1) / p.nw;
-    p.grid = (unsigned)(wgs < (size_t)kSegMaxGrid ? wgs : (size_t)kSegMaxGrid);
-    p.part_bytes = up((size_t)p.grid * seg_record_bytes(C));
-    return true;
-}
-
-template <typename T>
-int seg_head_impl(const T *act, const int32_t *labels, size_t rows, int C, T grad_scale, T *grad_act, int32_t *pred,
-                  double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (rows == 0 || C < 2 || !act || !labels || !loss_sum || !counts) return CONV3P_ERR_INVALID_ARGUMENT;
-    SegPlan p;
-    if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;   // (int32 partial counters)
-    TRY(buf_check(workspace, workspace_bytes, p.part_bytes));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char *part = static_cast<char *>(workspace);
-    {
-        Scope sc(K_SEG_HEAD, s);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(seg_head_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        hipLaunchKernelGGL(seg_head_kernel<T>, dim3(p.grid), dim3(64 * p.nw), p.lds, s, act, labels, rows, C, grad_scale,
-                           grad_act, pred, part);
-        hipLaunchKernelGGL(seg_head_finish_kernel, dim3(1), dim3(kSegFinishThreads), 0, s, part, (int)p.grid, C, loss_sum,
-                           reinterpret_cast<long long *>(counts));
-    }
-    return hip_ok();
-}
-
-// ----------------------------------------------------------------------------- the weighted segmentation head
-// (conv3p_seg_head_weighted.hpp).  All launches are accounted under K_SEG_HEAD.
-inline unsigned seg_total_grid(size_t rows)
-{
-    const size_t wgs = (rows + kSegTotalRowsPerWg - 1) / kSegTotalRowsPerWg;
-    return (unsigned)(wgs < (size_t)kSegTotalMaxGrid ? wgs : (size_t)kSegTotalMaxGrid);
-}
-inline unsigned seg_conf_grid(size_t rows)
-{
-    const size_t wgs = (rows + kSegConfRowsPerWg - 1) / kSegConfRowsPerWg;
-    return (unsigned)(wgs < (size_t)kSegConfMaxGrid ? wgs : (size_t)kSegConfMaxGrid);
-}
-inline size_t seg_total_bytes(size_t rows) { return up((size_t)seg_total_grid(rows) * sizeof(SegTotalRecord)); }
-
-template <typename T>
-int seg_weight_total_impl(const int32_t *labels, size_t rows, int C, const T *class_weight, const T *point_weight,
-                          double *total, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (rows == 0 || C < 2 || !labels || !total) return CONV3P_ERR_INVALID_ARGUMENT;
-    SegPlan p;
-    if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, seg_total_bytes(rows)));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    SegTotalRecord *part = static_cast<SegTotalRecord *>(workspace);
-    const unsigned grid = seg_total_grid(rows);
-    {
-        Scope sc(K_SEG_HEAD, s);
-        hipLaunchKernelGGL(seg_weight_total_kernel<T>, dim3(grid), dim3(kSegTotalThreads), 0, s, labels, rows, C,
-                           class_weight, point_weight, part);
-        hipLaunchKernelGGL(seg_weight_total_finish_kernel, dim3(1), dim3(64), 0, s, part, (int)grid, total);
-    }
-    return hip_ok();
-}
-
-template <typename T>
-int seg_head_weighted_impl(const T *act, const int32_t *labels, size_t rows, int C, const T *class_weight,
-                           const T *point_weight, double smoothing, T grad_scale, const double *denominator, T *grad_act,
-                           int32_t *pred, double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes,
-                           void *stream)
-{
-    if (rows == 0 || C < 2 || !act || !labels || !loss_sum || !counts) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!(smoothing >= 0.0 && smoothing < 1.0)) return CONV3P_ERR_INVALID_ARGUMENT;   // also rejects NaN
-    const T ls = (T)smoothing;                                                         // what the kernel smooths with
-    if (!class_weight && !point_weight && ls == T(0) && !denominator)                  // the plain head, bit for bit
-        return seg_head_impl<T>(act, labels, rows, C, grad_scale, grad_act, pred, loss_sum, counts, workspace,
-                                workspace_bytes, stream);
-    SegPlan p;
-    if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, p.part_bytes));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char *part = static_cast<char *>(workspace);
-    {
-        Scope sc(K_SEG_HEAD, s);
-        auto kern = ls != T(0) ? seg_head_weighted_kernel<T, true> : seg_head_weighted_kernel<T, false>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), p.lds, s, act, labels, rows, C, class_weight,
-                           point_weight, ls, grad_scale, denominator, grad_act, pred, part);
-        hipLaunchKernelGGL(seg_head_finish_kernel, dim3(1), dim3(kSegFinishThreads), 0, s, part, (int)p.grid, C, loss_sum,
-                           reinterpret_cast<long long *>(counts));
-    }
-    return hip_ok();
-}
-
-}  // namespace
-
-namespace {
-static_assert(kOptMaxTensors == CONV3P_OPT_MAX_TENSORS, "conv3p_optim.hpp and conv3p.h disagree");
-
-// The table of a launch from the host arrays: CONV3P_ERR_INVALID_ARGUMENT for a NULL or misaligned entry with a non-zero
-// count; tab.chunks == 0 when there is nothing to do.
-template <typename T>
-int opt_table(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, OptTable<T> &tab)
-{
-    size_t chunks = 0;
-    for (int i = 0; i < kOptMaxTensors; ++i) {
-        const size_t ne = i < n ? numels[i] : 0;
-        if (ne != 0) {
-            if (!params[i] || !grads[i] || !accums[i]) return CONV3P_ERR_INVALID_ARGUMENT;
-            if (((reinterpret_cast<size_t>(params[i]) | reinterpret_cast<size_t>(grads[i]) |
-                  reinterpret_cast<size_t>(accums[i])) & (sizeof(T) - 1)) != 0)
-                return CONV3P_ERR_INVALID_ARGUMENT;
-        }
-        tab.param[i] = ne ? params[i] : nullptr;
-        tab.grad[i] = ne ? grads[i] : nullptr;
-        tab.accum[i] = ne ? accums[i] : nullptr;
-        tab.numel[i] = ne;
-        chunks += (ne + kOptChunk - 1) / kOptChunk;
-        tab.chunk_end[i] = chunks;
-    }
-    tab.chunks = chunks;
-    return CONV3P_OK;
-}
-inline unsigned opt_grid(size_t chunks) { return (unsigned)(chunks < (size_t)kOptMaxGrid ? chunks : (size_t)kOptMaxGrid); }
-
-// status first, then (only if there is anything to do) the table by value and one launch
-template <typename T>
-int momentum_step_impl(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, T lr,
-                       T momentum, void *stream)
-{
-    if (n < 0 || n > kOptMaxTensors) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (n == 0) return CONV3P_OK;
-    if (!params || !grads || !accums || !numels) return CONV3P_ERR_INVALID_ARGUMENT;
-    OptTable<T> tab;
-    TRY(opt_table<T>(n, params, grads, accums, numels, tab));
-    if (tab.chunks == 0) return CONV3P_OK;
-    hipLaunchKernelGGL(momentum_step_kernel<T>, dim3(opt_grid(tab.chunks)), dim3(kOptThreads), 0,
-                       static_cast<hipStream_t>(stream), tab, lr, momentum);
-    return hip_ok();
-}
-
-// The guarded step.  Without Nesterov and without a use for stats this IS momentum_step_impl: the same instantiation
-// of momentum_step_kernel, so the defaults cost and compute what they did.
-template <typename T>
-int momentum_step_guarded_impl(int n, T *const *params, const T *const *grads, T *const *accums, const size_t *numels, T lr,
-                               T momentum, int nesterov, T clip_norm, int skip_nonfinite, const double *stats, void *stream)
-{
-    if (n < 0 || n > kOptMaxTensors) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite((double)clip_norm)) return CONV3P_ERR_INVALID_ARGUMENT;
-    const bool clip = clip_norm > T(0), guarded = clip || skip_nonfinite != 0;
-    if (guarded && !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!nesterov && !guarded) return momentum_step_impl<T>(n, params, grads, accums, numels, lr, momentum, stream);
-    if (n == 0) return CONV3P_OK;
-    if (!params || !grads || !accums || !numels) return CONV3P_ERR_INVALID_ARGUMENT;
-    OptTable<T> tab;
-    TRY(opt_table<T>(n, params, grads, accums, numels, tab));
-    if (tab.chunks == 0) return CONV3P_OK;
-    auto kern = nesterov ? momentum_step_guarded_kernel<T, true> : momentum_step_guarded_kernel<T, false>;
-    hipLaunchKernelGGL(kern, dim3(opt_grid(tab.chunks)), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream), tab, lr,
-                       momentum, guarded ? stats : nullptr, clip ? clip_norm : T(0), skip_nonfinite ? 1 : 0);
-    return hip_ok();
-}
-
-// grad_sumsq_kernel + grad_sumsq_finish_kernel; with nothing to read only the finish runs (stats = 0), and with
-// accumulate nothing at all.  Outside the profile bracket, as momentum_step_kernel.
-inline size_t grad_norm_bytes() { return up((size_t)kOptMaxGrid * sizeof(GradNormRecord)); }
-
-template <typename T>
-int grad_norm_impl(int n, const T *const *grads, const size_t *numels, double *stats, int accumulate, void *workspace,
-                   size_t workspace_bytes, void *stream)
-{
-    if (n < 0 || n > kOptMaxTensors || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (n > 0 && (!grads || !numels)) return CONV3P_ERR_INVALID_ARGUMENT;
-    GradTable<T> tab;
-    size_t chunks = 0;
-    for (int i = 0; i < kOptMaxTensors; ++i) {
-        const size_t ne = i < n ? numels[i] : 0;
-        if (ne != 0 && (!grads[i] || (reinterpret_cast<size_t>(grads[i]) & (sizeof(T) - 1)) != 0))
-            return CONV3P_ERR_INVALID_ARGUMENT;
-        tab.grad[i] = ne ? grads[i] : nullptr;
-        tab.numel[i] = ne;
-        chunks += (ne + kOptChunk - 1) / kOptChunk;
-        tab.chunk_end[i] = chunks;
-    }
-    tab.chunks = chunks;
-    if (chunks == 0 && accumulate) return CONV3P_OK;
-    if (chunks != 0) TRY(buf_check(workspace, workspace_bytes, grad_norm_bytes()));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    GradNormRecord *part = static_cast<GradNormRecord *>(workspace);
-    const unsigned grid = opt_grid(chunks);
-    if (grid != 0) hipLaunchKernelGGL(grad_sumsq_kernel<T>, dim3(grid), dim3(kOptThreads), 0, s, tab, part);
-    hipLaunchKernelGGL(grad_sumsq_finish_kernel, dim3(1), dim3(kGradFinishThreads), 0, s, part, (int)grid,
-                       accumulate ? 1 : 0, stats);
-    return hip_ok();
-}
-}  // namespace
-
-// ----------------------------------------------------------------------------- the classification tail
-namespace {
-struct ClsPlan { size_t drop, dz, loss, pred, total; };
-bool cls_plan(int M, int H, int C, ClsPlan &p)
-{
-    if (M < 1 || M > kClsMaxRows || H < 8 || H % 8 != 0 || H > kClsMaxHidden || C < 2 || C > kClsMaxClass) return false;
-    p.drop = 0;
-    p.dz = p.drop + up((size_t)M * H * 4);
-    p.loss = p.dz + up((size_t)M * C * 4);
-    p.pred = p.loss + up((size_t)M * 8);
-    p.total = p.pred + up((size_t)M * 4);
-    return true;
-}
-
-// Every status first; then cls_tail_row_kernel and cls_tail_dw_kernel, outside the profile bracket (the table of
-// kinds is pinned), as momentum_step_kernel.  accum_W2 != NULL: the _step entry point.
-int cls_tail_impl(const float *fc1, float *W2, float *b2, const int32_t *labels, int M, int H, int C, int training,
-                  double rate, const float *keep_mask, uint64_t seed, uint64_t step, float grad_scale, float *logits,
-                  int32_t *pred, float *dfc1, float *dW2, float *db2, float *accum_W2, float *accum_b2, float lr,
-                  float momentum, uint8_t *keep_out, double *loss_sum, int64_t *counts, void *workspace,
-                  size_t workspace_bytes, void *stream)
-{
-    if (!fc1 || !W2 || !b2 || !labels || !logits || !loss_sum || !counts || M <= 0 || H <= 0 || C < 2)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (training && !(rate >= 0.0 && rate < 1.0)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (dfc1 && !accum_W2 && (!dW2 || !db2)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (((reinterpret_cast<uintptr_t>(fc1) | reinterpret_cast<uintptr_t>(keep_mask)) & 15) != 0)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    ClsPlan pl;
-    if (!cls_plan(M, H, C, pl)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, pl.total));
-    char *ws = static_cast<char *>(workspace);
-    ClsTailArgs a;
-    a.fc1 = fc1; a.W2 = W2; a.b2 = b2; a.labels = labels; a.keep_mask = keep_mask;
-    a.M = M; a.H = H; a.C = C;
-    a.dropout = training && rate > 0.0;
-    a.need_grad = dfc1 != nullptr;
-    // selu.py:36-61 in double, as head.dropout_selu_constants
-    const double alpha = -1.7580993408473766, keep = 1.0 - rate;
-    const double ca = a.dropout ? std::sqrt(1.0 / (keep * ((1.0 - keep) * alpha * alpha + 1.0))) : 1.0;
-    a.keep_prob = (float)keep;
-    a.a = (float)ca;
-    a.b = a.dropout ? (float)(0.0 - ca * ((1.0 - keep) * alpha)) : 0.0f;
-    a.alpha = (float)alpha;
-    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
-    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
-    a.grad_scale = grad_scale;
-    a.logits = logits; a.pred = pred; a.dfc1 = dfc1; a.keep_out = keep_out;
-    a.drop = reinterpret_cast<float *>(ws + pl.drop);
-    a.dz = reinterpret_cast<float *>(ws + pl.dz);
-    a.row_loss = reinterpret_cast<double *>(ws + pl.loss);
-    a.row_pred = reinterpret_cast<int32_t *>(ws + pl.pred);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(cls_tail_row_kernel, dim3((unsigned)M), dim3(kClsRowThreads), 0, s, a);
-    TRY(hip_ok());
-    const unsigned wgs = a.need_grad ? (unsigned)((H * C + kClsDwThreads - 1) / kClsDwThreads) : 0u;
-    hipLaunchKernelGGL(cls_tail_dw_kernel, dim3(wgs + 1), dim3(kClsDwThreads), 0, s, a.drop, a.dz, a.row_loss, a.row_pred,
-                       labels, M, H, C, a.need_grad, W2, b2, accum_W2, accum_b2, lr, momentum, dW2, db2, loss_sum,
-                       reinterpret_cast<long long *>(counts));
-    return hip_ok();
-}
 }  // namespace
 
 extern "C" {
@@ -3181,8 +2906,7 @@ int conv3p_backward_f64(BWD_ARGS(double), void *workspace, size_t workspace_byte
 
 #define CACHE_ARGS void *cache, size_t cache_bytes, const conv3p_cache_config *cfg, void *stream
 #define CACHE_WHERE(elem)                                                                                      \
-    persistent(elem, B, N, cache, cache_bytes, cfg->slots, cfg->max_taps, cfg->pairs_per_point, cfg->max_Cin,   \
-               cfg->max_Cout, cfg->flags)
+    persistent(elem, B, N, cache, cache_bytes, cfg, cfg->flags)
 int conv3p_forward_cached_f32(FWD_ARGS(float), CACHE_ARGS)
 {
     if (!cache_cfg_ok(cfg)) return CONV3P_ERR_INVALID_ARGUMENT;
@@ -3330,1369 +3054,6 @@ size_t conv3p_stack_scratch_bytes(const conv3p_stack_desc *desc, int elem_bytes,
 STACK_ENTRY(f32, float)
 STACK_ENTRY(f64, double)
 
-int conv3p_augment_f32(const float *points_in, const double *cos_sin, const double *noise, double sigma, double clip,
-                       int B, int N, float *points_out, void *stream)
-{
-    if (B < 0 || N < 0 || !(clip > 0.0) || !(sigma >= 0.0)) return CONV3P_ERR_INVALID_ARGUMENT;   // assert(clip > 0), :72
-    const size_t total = (size_t)B * N;
-    if (total == 0) return CONV3P_OK;
-    if (!points_in || !points_out) return CONV3P_ERR_INVALID_ARGUMENT;
-    const unsigned grid = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(augment_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), points_in,
-                       reinterpret_cast<const double2 *>(cos_sin), noise, sigma, clip, points_out, total, N);
-    return hip_ok();
-}
-
-namespace {
-// Both orders of a cloud: one workgroup per cloud, npad keys of key_bytes in dynamic LDS.
-using SortOrderKernel = void (*)(const float *, int, int, int, int32_t *);
-int sort_order_launch(SortOrderKernel kernel, size_t key_bytes, const float *data, int B, int N, int row_floats,
-                      int32_t *order, void *stream)
-{
-    if (B < 0 || N < 0 || row_floats < 3) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((size_t)B * N == 0) return CONV3P_OK;
-    if (!data || !order) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > 8192) return CONV3P_ERR_UNSUPPORTED;
-    int npad = 64;
-    while (npad < N) npad <<= 1;
-    const size_t lds = (size_t)npad * key_bytes;
-    const int threads = npad / 2 < 1024 ? (npad / 2 < 64 ? 64 : npad / 2) : 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, static_cast<hipStream_t>(stream), data, N,
-                       row_floats, npad, order);
-    return hip_ok();
-}
-}  // namespace
-
-int conv3p_sort_xyz_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream)
-{
-    return sort_order_launch(sort_xyz_kernel, sizeof(SortKey), data, B, N, row_floats, order, stream);
-}
-
-int conv3p_sort_morton_order_f32(const float *data, int B, int N, int row_floats, int32_t *order, void *stream)
-{
-    return sort_order_launch(sort_morton_kernel, sizeof(uint64_t), data, B, N, row_floats, order, stream);
-}
-
-int conv3p_gather_rows(const void *src, const int32_t *order, int B, int N, int row_bytes, void *dst, void *stream)
-{
-    if (B < 0 || N < 0 || row_bytes < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    const size_t rows = (size_t)B * N;
-    if (rows == 0) return CONV3P_OK;
-    if (!src || !order || !dst || src == dst) return CONV3P_ERR_INVALID_ARGUMENT;
-    const size_t work = rows * (size_t)((row_bytes & 3) == 0 ? row_bytes >> 2 : row_bytes);
-    const unsigned grid = (unsigned)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const char *>(src), order, N, row_bytes, static_cast<char *>(dst), rows);
-    return hip_ok();
-}
-
-size_t conv3p_provider_workspace_bytes(int B, int N, int flags)
-{
-    if (B <= 0 || N <= 0 || !(flags & CONV3P_PROVIDER_SORT) || N > kProviderMaxSortN) return 0;
-    return ((size_t)B * N * 3 * sizeof(float) + kAlign - 1) / kAlign * kAlign;
-}
-
-extern "C++" {
-namespace {
-// The keys of a cloud in the workspace of the wide sort (conv3p_sort_wide.hpp): npad of them, sorted in chunks.
-struct WidePlan { int npad, chunk, tiles; size_t key_bytes, keys, ranges, total; };
-bool wide_plan(int B, int N, bool morton, WidePlan &w)
-{
-    if (B <= 0 || N <= 0 || N > kWideMaxN) return false;
-    w.npad = 64;
-    while (w.npad < N) w.npad <<= 1;
-    w.chunk = w.npad < kWideChunk ? w.npad : kWideChunk;
-    w.tiles = (N + kProviderTile - 1) / kProviderTile;
-    w.key_bytes = morton ? sizeof(uint64_t) : sizeof(SortKey);
-    w.keys = up((size_t)B * w.npad * w.key_bytes);
-    w.ranges = morton ? up((size_t)B * w.tiles * 6 * sizeof(float)) : 0;
-    w.total = w.keys + w.ranges;
-    return true;
-}
-inline bool wide_grids_ok(int B, const WidePlan &w)
-{
-    return (size_t)B * (size_t)(w.npad / 2) <= (size_t)INT32_MAX;       // bounds every grid: chunks, pairs, tiles
-}
-
-// order[b][r] of B clouds whose rows (xyz first, ld floats a row, cloud_floats a cloud) are on the device: the launches
-// of conv3p_sort_wide.hpp, outside the profile bracket as the provider's.  ws: w.total bytes.  have_ranges: the caller's
-// own pass has written the Morton tile ranges.
-template <bool MORTON>
-void wide_sort_launch(const float *rows, size_t cloud_floats, int ld, int B, int N, const WidePlan &w, char *ws,
-                      bool have_ranges, int32_t *order, hipStream_t s)
-{
-    using Key = typename std::conditional<MORTON, uint64_t, SortKey>::type;
-    using Less = typename std::conditional<MORTON, MortonLess, KeyLess>::type;
-    Key *keys = reinterpret_cast<Key *>(ws);
-    float *ranges = reinterpret_cast<float *>(ws + w.keys);
-    if (MORTON && !have_ranges)
-        hipLaunchKernelGGL(wide_range_kernel, dim3((unsigned)((size_t)B * w.tiles)), dim3(kProviderTile), 0, s, rows, N, ld,
-                           w.tiles, ranges);
-    const int chunks = w.npad / w.chunk;
-    const unsigned cgrid = (unsigned)((size_t)B * chunks);
-    const size_t lds = (size_t)w.chunk * sizeof(Key);
-    const int threads = w.chunk / 2 < 1024 ? (w.chunk / 2 < 64 ? 64 : w.chunk / 2) : 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wide_chunk_kernel<MORTON>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(wide_chunk_kernel<MORTON>, dim3(cgrid), dim3(threads), lds, s, rows, cloud_floats, ld, N, w.npad,
-                       w.chunk, (const float *)ranges, w.tiles, (void *)keys, chunks == 1 ? order : (int32_t *)nullptr);
-    if (chunks == 1) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wide_merge_kernel<Key, Less>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const unsigned sgrid = (unsigned)((size_t)B * (w.npad / 2 / kWideStageThreads));
-    for (int k = 2 * w.chunk; k <= w.npad; k <<= 1) {
-        hipLaunchKernelGGL((wide_stage_kernel<Key, Less>), dim3(sgrid), dim3(kWideStageThreads), 0, s, keys, w.npad, k, 0, 1);
-        for (int j = k >> 2; j >= w.chunk; j >>= 1)
-            hipLaunchKernelGGL((wide_stage_kernel<Key, Less>), dim3(sgrid), dim3(kWideStageThreads), 0, s, keys, w.npad, k, j, 0);
-        hipLaunchKernelGGL((wide_merge_kernel<Key, Less>), dim3(cgrid), dim3(threads), lds, s, keys, w.npad, w.chunk, N,
-                           k == w.npad ? order : (int32_t *)nullptr);
-    }
-}
-}  // namespace
-}  // extern "C++": the templates
-
-size_t conv3p_sort_order_workspace_bytes(int B, int N, int method)
-{
-    WidePlan w;
-    if ((method != CONV3P_SORT_XYZ && method != CONV3P_SORT_MORTON) || !wide_plan(B, N, method == CONV3P_SORT_MORTON, w)) return 0;
-    return w.total;
-}
-
-int conv3p_sort_order_f32(const float *data, int B, int N, int row_floats, int method, int32_t *order, void *workspace,
-                          size_t workspace_bytes, void *stream)
-{
-    if (B < 0 || N < 0 || row_floats < 3 || (method != CONV3P_SORT_XYZ && method != CONV3P_SORT_MORTON))
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((size_t)B * N == 0) return CONV3P_OK;
-    if (!data || !order) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > kWideMaxN) return CONV3P_ERR_UNSUPPORTED;
-    const bool morton = method == CONV3P_SORT_MORTON;
-    WidePlan w;
-    wide_plan(B, N, morton, w);
-    if (!wide_grids_ok(B, w)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, w.total));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t cloud = (size_t)N * row_floats;
-    if (morton) wide_sort_launch<true>(data, cloud, row_floats, B, N, w, static_cast<char *>(workspace), false, order, s);
-    else wide_sort_launch<false>(data, cloud, row_floats, B, N, w, static_cast<char *>(workspace), false, order, s);
-    return hip_ok();
-}
-
-// The wide provider's workspace: the stage (B, N, 3) floats, the order (B, N) int32, then the wide sort's.
-size_t conv3p_provider_wide_workspace_bytes(int B, int N, int flags)
-{
-    WidePlan w;
-    if (!(flags & CONV3P_PROVIDER_SORT) || !wide_plan(B, N, (flags & CONV3P_PROVIDER_MORTON) != 0, w)) return 0;
-    return up((size_t)B * N * 3 * sizeof(float)) + up((size_t)B * N * sizeof(int32_t)) + w.total;
-}
-
-namespace {
-// Every status first; then ONE launch (wide: the launches of conv3p_sort_wide.hpp), outside the profile bracket (the
-// table of kinds is pinned), as cls_tail_impl.
-int provider_impl(bool wide, const float *data, const void *labels, int S, int Nsrc, int K, int label_bytes,
-                  int labels_per_point, const int32_t *perm, int64_t perm_len, int64_t start, int B, int N,
-                  int flags, double sigma, double clip, uint64_t seed, uint64_t step, const double *cos_sin,
-                  const double *noise, float *points, float *input, int32_t *labels_out, double *cos_sin_out,
-                  double *noise_out, int32_t *order_out, int32_t *bad_index, void *workspace,
-                  size_t workspace_bytes, void *stream)
-{
-    const int known = CONV3P_PROVIDER_ROTATE | CONV3P_PROVIDER_JITTER | CONV3P_PROVIDER_SORT | CONV3P_PROVIDER_MORTON;
-    if (B < 0 || N < 0 || S < 0 || K < 3 || Nsrc < N || start < 0 || (flags & ~known)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((flags & CONV3P_PROVIDER_MORTON) && !(flags & CONV3P_PROVIDER_SORT)) return CONV3P_ERR_INVALID_ARGUMENT;   // a qualifier
-    if (wide && !(flags & CONV3P_PROVIDER_SORT)) return CONV3P_ERR_INVALID_ARGUMENT;   // the wide entry is the sorting one
-    if ((flags & CONV3P_PROVIDER_JITTER) && (!(clip > 0.0) || !(sigma >= 0.0))) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (perm ? (perm_len < 0 || start > perm_len - B) : start > (int64_t)INT32_MAX) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((size_t)B * N == 0) return CONV3P_OK;
-    if (!data || !points || !input || !bad_index) return CONV3P_ERR_INVALID_ARGUMENT;
-    const bool sort = (flags & CONV3P_PROVIDER_SORT) != 0;
-    if (sort && N > (wide ? kWideMaxN : kProviderMaxSortN)) return CONV3P_ERR_UNSUPPORTED;
-    const size_t tiles = ((size_t)N + kProviderTile - 1) / kProviderTile;
-    if (K > 65536 || ((!sort || wide) && (size_t)B * tiles > (size_t)INT32_MAX)) return CONV3P_ERR_UNSUPPORTED;
-    const bool morton = (flags & CONV3P_PROVIDER_MORTON) != 0;
-    WidePlan w;
-    if (wide && (!wide_plan(B, N, morton, w) || !wide_grids_ok(B, w))) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes,
-                  wide ? conv3p_provider_wide_workspace_bytes(B, N, flags) : conv3p_provider_workspace_bytes(B, N, flags)));
-    ProviderArgs a;
-    a.data = data; a.labels = labels; a.perm = perm;
-    a.cos_sin = reinterpret_cast<const double2 *>(cos_sin); a.noise = noise;
-    a.start = start;
-    a.S = S; a.Nsrc = Nsrc; a.K = K; a.B = B; a.N = N;
-    a.label_bytes = label_bytes; a.per_point = labels_per_point != 0;
-    a.rotate = (flags & CONV3P_PROVIDER_ROTATE) != 0; a.jitter = (flags & CONV3P_PROVIDER_JITTER) != 0;
-    a.sigma = sigma; a.clip = clip;
-    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
-    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
-    a.points = points; a.input = input; a.labels_out = labels_out;
-    a.cos_sin_out = reinterpret_cast<double2 *>(cos_sin_out); a.noise_out = noise_out; a.order_out = order_out;
-    a.bad_index = bad_index;
-    a.stage = static_cast<float *>(workspace);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!sort) {
-        hipLaunchKernelGGL(provider_flat_kernel, dim3((unsigned)((size_t)B * tiles)), dim3(kProviderTile), 0, s, a, (int)tiles);
-        return hip_ok();
-    }
-    if (wide) {
-        char *ws = static_cast<char *>(workspace);
-        int32_t *order = reinterpret_cast<int32_t *>(ws + up((size_t)B * N * 3 * sizeof(float)));
-        char *sort_ws = reinterpret_cast<char *>(order) + up((size_t)B * N * sizeof(int32_t));
-        const unsigned grid = (unsigned)((size_t)B * tiles);
-        if (morton) {
-            hipLaunchKernelGGL(provider_wide_stage_kernel<true>, dim3(grid), dim3(kProviderTile), 0, s, a, (int)tiles,
-                               reinterpret_cast<float *>(sort_ws + w.keys));
-            wide_sort_launch<true>(a.stage, (size_t)N * 3, 3, B, N, w, sort_ws, true, order, s);
-        } else {
-            hipLaunchKernelGGL(provider_wide_stage_kernel<false>, dim3(grid), dim3(kProviderTile), 0, s, a, (int)tiles,
-                               (float *)nullptr);
-            wide_sort_launch<false>(a.stage, (size_t)N * 3, 3, B, N, w, sort_ws, false, order, s);
-        }
-        hipLaunchKernelGGL(provider_wide_gather_kernel, dim3(grid), dim3(kProviderTile), 0, s, a, (int)tiles,
-                           (const int32_t *)order);
-        return hip_ok();
-    }
-    int npad = 64;
-    while (npad < N) npad <<= 1;
-    const size_t lds = (size_t)npad * (morton ? sizeof(uint64_t) : sizeof(SortKey));
-    const int threads = npad / 2 < 1024 ? (npad / 2 < 64 ? 64 : npad / 2) : 1024;
-    auto kernel = morton ? provider_sort_kernel<true> : provider_sort_kernel<false>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, s, a, npad);
-    return hip_ok();
-}
-}  // namespace
-
-#define PROVIDER_PARAMS                                                                                              \
-    const float *data, const void *labels, int S, int Nsrc, int K, int label_bytes, int labels_per_point,            \
-        const int32_t *perm, int64_t perm_len, int64_t start, int B, int N, int flags, double sigma, double clip,    \
-        uint64_t seed, uint64_t step, const double *cos_sin, const double *noise, float *points, float *input,       \
-        int32_t *labels_out, double *cos_sin_out, double *noise_out, int32_t *order_out, int32_t *bad_index,         \
-        void *workspace, size_t workspace_bytes, void *stream
-#define PROVIDER_ARGS                                                                                                \
-    data, labels, S, Nsrc, K, label_bytes, labels_per_point, perm, perm_len, start, B, N, flags, sigma, clip, seed,  \
-        step, cos_sin, noise, points, input, labels_out, cos_sin_out, noise_out, order_out, bad_index, workspace,    \
-        workspace_bytes, stream
-int conv3p_provider_batch_f32(PROVIDER_PARAMS) { return provider_impl(false, PROVIDER_ARGS); }
-int conv3p_provider_batch_wide_f32(PROVIDER_PARAMS) { return provider_impl(true, PROVIDER_ARGS); }
-#undef PROVIDER_PARAMS
-#undef PROVIDER_ARGS
-
-namespace {
-// The workspace of conv3p_scene_blocks_f32 (conv3p_scene.hpp): a host-side upper bound from the five arguments.
-struct ScenePlan { int records, chunk_rows, chunks, blocks; size_t hdr, rec, count, blk, chunk_count, members, total; };
-bool scene_plan(int64_t N, int num_point, int max_blocks, float block, float stride, ScenePlan &w)
-{
-    if (N <= 0 || N > kSceneMaxN || num_point < 1 || num_point > kSceneMaxP || max_blocks <= 0) return false;
-    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return false;
-    if (block < stride || block > 2.0f * stride) return false;
-    const size_t tiles = ((size_t)N + kSceneThreads - 1) / kSceneThreads;
-    w.records = (int)(tiles < (size_t)kSceneMaxRecords ? tiles : (size_t)kSceneMaxRecords);
-    const size_t even = (((size_t)N + kSceneMaxChunks - 1) / kSceneMaxChunks + kSceneThreads - 1) / kSceneThreads * kSceneThreads;
-    w.chunk_rows = (int)(even > (size_t)kSceneMinChunk ? even : (size_t)kSceneMinChunk);
-    w.chunks = (int)(((size_t)N + w.chunk_rows - 1) / w.chunk_rows);
-    w.blocks = max_blocks < kSceneMaxCells ? max_blocks : kSceneMaxCells;
-    const size_t m = (size_t)std::ceil((double)block / (double)stride) + 1;          // cells a row can be in, an axis
-    w.hdr = up(sizeof(SceneHeader));
-    w.rec = up((size_t)kSceneMaxRecords * 8 * sizeof(float));
-    w.count = up((size_t)kSceneMaxCells * sizeof(int));
-    w.blk = up((size_t)w.blocks * sizeof(int));
-    w.chunk_count = up((size_t)w.blocks * kSceneMaxChunks * sizeof(int));
-    w.members = up((size_t)N * m * m * sizeof(int));
-    w.total = w.hdr + w.rec + w.count + 3 * w.blk + w.chunk_count + w.members;
-    return true;
-}
-inline unsigned scene_grid(size_t work)
-{
-    const size_t g = (work + kSceneThreads - 1) / kSceneThreads;
-    return (unsigned)(g < (size_t)kSceneMaxRecords ? (g ? g : 1) : (size_t)kSceneMaxRecords);
-}
-}  // namespace
-
-size_t conv3p_scene_blocks_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride)
-{
-    ScenePlan w;
-    return scene_plan(N, num_point, max_blocks, block, stride, w) ? w.total : 0;
-}
-
-namespace {
-// The workspace of conv3p_scene_blocks_cover_f32 (conv3p_scene_cover.hpp): the plain call's, with its three per-block
-// arrays and the chunk counts per LISTED cell (at most min(max_blocks, cells)), plus the listed cells' first block
-// numbers and the block table.
-struct SceneCoverPlan { ScenePlan s; size_t table, total; };
-bool scene_cover_plan(int64_t N, int num_point, int max_blocks, float block, float stride, SceneCoverPlan &w)
-{
-    if (!scene_plan(N, num_point, max_blocks, block, stride, w.s)) return false;
-    w.table = up((size_t)max_blocks * sizeof(int4));
-    w.total = w.s.total + w.s.blk + w.table;
-    return true;
-}
-
-// Both modes of the partition.  Every status first, in the order include/conv3p.h gives; then the seven launches (the
-// covering mode: eight), outside the profile bracket (the table of kinds is pinned), as provider_impl.
-int scene_blocks_impl(bool cover, const float *data, const void *labels, int64_t N, int K, int label_bytes, float block,
-                      float stride, int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step,
-                      float *blocks_out, int32_t *labels_out, int32_t *index_out, int32_t *block_cell,
-                      int32_t *block_count, int32_t *stats, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (N < 0 || K < 3 || num_point < 1 || max_blocks < 0) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N == 0 || max_blocks == 0) return CONV3P_OK;
-    if (!data || !blocks_out || !index_out || !block_cell || !block_count || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > kSceneMaxN || num_point > kSceneMaxP || K > 65536 || block < stride || block > 2.0f * stride)
-        return CONV3P_ERR_UNSUPPORTED;
-    SceneCoverPlan cw;
-    if (!scene_cover_plan(N, num_point, max_blocks, block, stride, cw)) return CONV3P_ERR_UNSUPPORTED;
-    const ScenePlan &w = cw.s;
-    TRY(buf_check(workspace, workspace_bytes, cover ? cw.total : w.total));
-    SceneArgs a;
-    a.data = data; a.labels = labels;
-    a.N = (int)N; a.K = K; a.label_bytes = label_bytes; a.P = num_point; a.min_points = min_points; a.max_blocks = max_blocks;
-    a.block = block; a.stride = stride;
-    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
-    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
-    a.blocks_out = blocks_out; a.labels_out = labels_out; a.index_out = index_out;
-    a.block_cell = block_cell; a.block_count = block_count; a.stats = stats;
-    char *ws = static_cast<char *>(workspace);
-    a.hdr = reinterpret_cast<SceneHeader *>(ws); ws += w.hdr;
-    a.records = reinterpret_cast<float *>(ws); ws += w.rec;
-    a.count = reinterpret_cast<int *>(ws); ws += w.count;
-    a.blk_cell = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.blk_count = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.blk_off = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.chunk_count = reinterpret_cast<int *>(ws); ws += w.chunk_count;
-    a.members = reinterpret_cast<int *>(ws); ws += w.members;
-    a.blk_first = cover ? reinterpret_cast<int *>(ws) : nullptr;                   // past the plain call's workspace
-    a.table = cover ? reinterpret_cast<int4 *>(ws + w.blk) : nullptr;
-    a.records_n = w.records; a.chunk_rows = w.chunk_rows; a.chunks = w.chunks;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t items = (size_t)w.blocks * w.chunks;
-    const unsigned igrid = (unsigned)(items < (size_t)kSceneMaxGrid ? items : (size_t)kSceneMaxGrid);
-    const unsigned egrid = (unsigned)(max_blocks < kSceneMaxGrid ? max_blocks : kSceneMaxGrid);
-    hipLaunchKernelGGL(scene_bounds_kernel, dim3((unsigned)w.records), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(scene_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, a);
-    hipLaunchKernelGGL(scene_count_kernel, dim3((unsigned)w.records), dim3(kSceneThreads), 0, s, a);
-    if (cover) {
-        hipLaunchKernelGGL(scene_cover_plan_kernel, dim3(1), dim3(kScenePlanThreads), 0, s, a);
-        hipLaunchKernelGGL(scene_cover_table_kernel, dim3(scene_grid((size_t)max_blocks)), dim3(kSceneThreads), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(scene_plan_kernel, dim3(1), dim3(kScenePlanThreads), 0, s, a);
-    }
-    hipLaunchKernelGGL(scene_fill_count_kernel, dim3(igrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(scene_fill_kernel, dim3(igrid), dim3(kSceneThreads), 0, s, a);
-    if (cover)
-        hipLaunchKernelGGL(scene_cover_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL(scene_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
-    return hip_ok();
-}
-}  // namespace
-
-size_t conv3p_scene_blocks_cover_workspace_bytes(int64_t N, int num_point, int max_blocks, float block, float stride)
-{
-    SceneCoverPlan w;
-    return scene_cover_plan(N, num_point, max_blocks, block, stride, w) ? w.total : 0;
-}
-
-#define SCENE_PARAMS                                                                                                 \
-    const float *data, const void *labels, int64_t N, int K, int label_bytes, float block, float stride,             \
-        int num_point, int min_points, int max_blocks, uint64_t seed, uint64_t step, float *blocks_out,              \
-        int32_t *labels_out, int32_t *index_out, int32_t *block_cell, int32_t *block_count, int32_t *stats,          \
-        void *workspace, size_t workspace_bytes, void *stream
-#define SCENE_ARGS                                                                                                   \
-    data, labels, N, K, label_bytes, block, stride, num_point, min_points, max_blocks, seed, step, blocks_out,       \
-        labels_out, index_out, block_cell, block_count, stats, workspace, workspace_bytes, stream
-int conv3p_scene_blocks_f32(SCENE_PARAMS) { return scene_blocks_impl(false, SCENE_ARGS); }
-int conv3p_scene_blocks_cover_f32(SCENE_PARAMS) { return scene_blocks_impl(true, SCENE_ARGS); }
-#undef SCENE_PARAMS
-#undef SCENE_ARGS
-
-namespace {
-// The workspace of conv3p_scene_blocks_rooms_f32 (conv3p_scene_rooms.hpp): a host-side upper bound from the arguments.
-// The two pair buffers dominate it: N * m^2 pairs of 8 bytes each, m = ceil(block / stride) + 1 the cells a row can be
-// in along an axis -- at m = 3 that is 144 bytes a row.
-struct RoomsPlan {
-    int row_tiles, listed_max, pairs_max, sort_tiles;
-    size_t hdr, room, base, pref, rec, tile, seg, blk, table, blk_room, hist, pairs, total;
-};
-bool rooms_plan(int64_t N, int64_t R, int num_point, int max_blocks, float block, float stride, RoomsPlan &w)
-{
-    if (N <= 0 || N > kRoomsMaxN || R <= 0 || R > kRoomsMaxRooms || num_point < 1 || num_point > kSceneMaxP || max_blocks <= 0)
-        return false;
-    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return false;
-    if (block < stride || block > 2.0f * stride) return false;
-    const size_t m = (size_t)std::ceil((double)block / (double)stride) + 1;
-    w.row_tiles = (int)((N + kRoomsRowTile - 1) / kRoomsRowTile);
-    w.listed_max = max_blocks < kRoomsMaxCells ? max_blocks : kRoomsMaxCells;
-    w.pairs_max = (int)((size_t)N * m * m);                                          // <= 9 * 2^26 < 2^31
-    w.sort_tiles = (w.pairs_max + kRoomsSortTile - 1) / kRoomsSortTile;
-    w.hdr = up(sizeof(RoomsHeader));
-    w.room = up((size_t)R * sizeof(RoomFrame));
-    w.base = up((size_t)(R + 1) * sizeof(int));
-    w.pref = up((size_t)(R + 1) * sizeof(int4));
-    w.rec = up(((size_t)w.row_tiles + (size_t)R) * 8 * sizeof(float));
-    w.tile = up((size_t)w.row_tiles * sizeof(int));
-    w.seg = up((size_t)kRoomsMaxCells * sizeof(int));
-    w.blk = up((size_t)w.listed_max * sizeof(int));
-    w.table = up((size_t)max_blocks * sizeof(int4));
-    w.blk_room = up((size_t)max_blocks * sizeof(int));
-    w.hist = up((size_t)w.sort_tiles * kRoomsDigits * sizeof(int));
-    w.pairs = up((size_t)w.pairs_max * sizeof(unsigned long long));
-    w.total = w.hdr + w.room + w.base + w.pref + w.rec + w.tile + 2 * w.seg + 4 * w.blk + w.table + w.blk_room + w.hist +
-              2 * w.pairs;
-    return true;
-}
-}  // namespace
-
-size_t conv3p_scene_blocks_rooms_workspace_bytes(int64_t N, int64_t R, int num_point, int max_blocks, float block,
-                                                 float stride, int cover)
-{
-    RoomsPlan w;
-    if (cover != 0 && cover != 1) return 0;
-    return rooms_plan(N, R, num_point, max_blocks, block, stride, w) ? w.total : 0;
-}
-
-// Every status first, in the order include/conv3p.h gives; then the launches, their number fixed, outside the profile
-// bracket as scene_blocks_impl's.
-int conv3p_scene_blocks_rooms_f32(const float *data, const void *labels, const int32_t *room_start, int64_t N, int64_t R,
-                                  int K, int label_bytes, float block, float stride, int num_point, int min_points,
-                                  int max_blocks, int cover, uint64_t seed, uint64_t step, float *blocks_out,
-                                  int32_t *labels_out, int32_t *index_out, int32_t *block_cell, int32_t *block_count,
-                                  int32_t *block_room, int32_t *room_blocks, int32_t *room_stats, int32_t *stats,
-                                  void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (N < 0 || R < 0 || K < 3 || num_point < 1 || max_blocks < 0 || (cover != 0 && cover != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(block) || !std::isfinite(stride) || !(block > 0.0f) || !(stride > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (R == 0 || N == 0 || max_blocks == 0) return CONV3P_OK;
-    if (!data || !room_start || !blocks_out || !index_out || !block_cell || !block_count || !block_room || !room_blocks ||
-        !room_stats || !stats)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > kRoomsMaxN || R > kRoomsMaxRooms || num_point > kSceneMaxP || K > 65536 || block < stride || block > 2.0f * stride)
-        return CONV3P_ERR_UNSUPPORTED;
-    RoomsPlan w;
-    if (!rooms_plan(N, R, num_point, max_blocks, block, stride, w)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, w.total));
-    RoomsArgs a;
-    a.data = data; a.labels = labels; a.room_start = room_start;
-    a.N = (int)N; a.R = (int)R; a.K = K; a.label_bytes = label_bytes; a.P = num_point; a.min_points = min_points;
-    a.max_blocks = max_blocks; a.cover = cover;
-    a.block = block; a.stride = stride;
-    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32);
-    a.step_lo = (unsigned)step; a.step_hi = (unsigned)(step >> 32);
-    a.blocks_out = blocks_out; a.labels_out = labels_out; a.index_out = index_out;
-    a.block_cell = block_cell; a.block_count = block_count; a.block_room = block_room;
-    a.room_blocks = room_blocks; a.room_stats = room_stats; a.stats = stats;
-    char *ws = static_cast<char *>(workspace);
-    a.hdr = reinterpret_cast<RoomsHeader *>(ws); ws += w.hdr;
-    a.room = reinterpret_cast<RoomFrame *>(ws); ws += w.room;
-    a.cell_base = reinterpret_cast<int *>(ws); ws += w.base;
-    a.room_pref = reinterpret_cast<int4 *>(ws); ws += w.pref;
-    a.records = reinterpret_cast<float *>(ws); ws += w.rec;
-    a.tile_pairs = reinterpret_cast<int *>(ws); ws += w.tile;
-    a.seg_start = reinterpret_cast<int *>(ws); ws += w.seg;
-    a.seg_end = reinterpret_cast<int *>(ws); ws += w.seg;
-    a.blk_cell = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.blk_count = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.blk_off = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.blk_first = reinterpret_cast<int *>(ws); ws += w.blk;
-    a.table = reinterpret_cast<int4 *>(ws); ws += w.table;
-    a.blk_room = reinterpret_cast<int *>(ws); ws += w.blk_room;
-    a.hist = reinterpret_cast<int *>(ws); ws += w.hist;
-    a.pairs_a = reinterpret_cast<unsigned long long *>(ws); ws += w.pairs;
-    a.pairs_b = reinterpret_cast<unsigned long long *>(ws);
-    a.row_tiles = w.row_tiles; a.listed_max = w.listed_max; a.pairs_max = w.pairs_max;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned rgrid = (unsigned)(R < kSceneMaxRecords ? R : kSceneMaxRecords);
-    const unsigned sgrid = (unsigned)(w.sort_tiles < kSceneMaxGrid ? w.sort_tiles : kSceneMaxGrid);
-    const unsigned egrid = (unsigned)(max_blocks < kSceneMaxGrid ? max_blocks : kSceneMaxGrid);
-    hipLaunchKernelGGL(rooms_check_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_bounds_kernel, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_finish_kernel, dim3(rgrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_base_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_pairs_kernel<false>, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_tile_scan_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_pairs_kernel<true>, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
-    unsigned long long *src = a.pairs_a, *dst = a.pairs_b;
-    for (int pass = 0; pass < kRoomsPasses; ++pass) {
-        const int shift = pass * kRoomsDigitBits;
-        hipLaunchKernelGGL(rooms_sort_hist_kernel, dim3(sgrid), dim3(kSceneThreads), 0, s, a, (const unsigned long long *)src, shift);
-        hipLaunchKernelGGL(rooms_sort_scan_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
-        hipLaunchKernelGGL(rooms_sort_scatter_kernel, dim3(sgrid), dim3(64), 0, s, a, (const unsigned long long *)src, dst, shift);
-        std::swap(src, dst);
-    }
-    // an odd number of passes: the sorted pairs are in pairs_b (= src after the last swap), where the emit reads them
-    hipLaunchKernelGGL(rooms_segments_kernel, dim3(scene_grid((size_t)w.pairs_max)), dim3(kSceneThreads), 0, s, a,
-                       (const unsigned long long *)src);
-    hipLaunchKernelGGL(rooms_plan_kernel, dim3(1), dim3(kRoomsScanThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_table_kernel, dim3(scene_grid((size_t)max_blocks)), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_stats_kernel, dim3(scene_grid((size_t)R + 1)), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(rooms_emit_kernel, dim3(egrid), dim3(kSceneThreads), 0, s, a);
-    return hip_ok();
-}
-
-namespace {
-// The workspace of conv3p_grid_subsample_f32 (conv3p_grid.hpp): a host-side bound from the arguments.  The two pair
-// buffers dominate it, 16 bytes a row; the list starts add 4.
-struct GridPlan {
-    int row_tiles, sort_tiles, voxel_grid;
-    size_t hdr, rec, tile, hist, digits, heads, start, part, pairs, total;
-};
-bool grid_plan(int64_t N, int max_voxels, GridPlan &w)
-{
-    if (N <= 0 || N > kGridMaxN || max_voxels <= 0) return false;
-    w.row_tiles = (int)((N + kGridRowTile - 1) / kGridRowTile);
-    w.sort_tiles = (int)((N + kGridSortTile - 1) / kGridSortTile);
-    const int64_t voxels = N > max_voxels ? N : (int64_t)max_voxels;               // occupied voxels and fillers
-    const int64_t vg = (voxels + kGridVoxelGroups - 1) / kGridVoxelGroups;
-    w.voxel_grid = (int)(vg < kSceneMaxGrid ? vg : kSceneMaxGrid);
-    w.hdr = up(sizeof(GridHeader));
-    w.rec = up((size_t)w.row_tiles * 8 * sizeof(float));
-    w.tile = up((size_t)w.row_tiles * sizeof(int));
-    w.hist = up((size_t)w.sort_tiles * kGridDigits * sizeof(int));
-    w.digits = up((size_t)kGridPasses * kGridDigits * sizeof(int));
-    w.heads = up((size_t)w.sort_tiles * sizeof(int));
-    w.start = up(((size_t)N + 1) * sizeof(int));
-    w.part = up((size_t)kSceneMaxGrid * sizeof(int));
-    w.pairs = up((size_t)N * sizeof(unsigned long long));
-    w.total = w.hdr + w.rec + w.tile + w.hist + w.digits + w.heads + w.start + w.part + 2 * w.pairs;
-    return true;
-}
-}  // namespace
-
-size_t conv3p_grid_subsample_workspace_bytes(int64_t N, int max_voxels)
-{
-    GridPlan w;
-    return grid_plan(N, max_voxels, w) ? w.total : 0;
-}
-
-// Every status first, in the order include/conv3p.h gives; then the launches, their number fixed by the arguments.
-int conv3p_grid_subsample_f32(const float *data, const void *labels, int64_t N, int K, int label_bytes, float voxel,
-                              int mode, int num_class, int max_voxels, float *out, int32_t *labels_out,
-                              int32_t *voxel_row, int32_t *voxel_count, int32_t *voxel_cell, int32_t *inverse,
-                              int32_t *stats, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (N < 0 || K < 3 || max_voxels < 0 || (mode != 0 && mode != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
-    const bool votes = labels && mode == 0;              // num_class is read by the majority only
-    if (votes && num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N == 0 || max_voxels == 0) return CONV3P_OK;
-    if (!data || !out || !voxel_row || !voxel_count || !voxel_cell || !inverse || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > kGridMaxN || K > 65536 || (votes && num_class > kGridMaxClass)) return CONV3P_ERR_UNSUPPORTED;
-    GridPlan w;
-    if (!grid_plan(N, max_voxels, w)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, w.total));
-    GridArgs a;
-    a.data = data; a.labels = labels;
-    a.N = (int)N; a.K = K; a.label_bytes = label_bytes; a.mode = mode; a.num_class = num_class; a.max_voxels = max_voxels;
-    a.voxel = voxel;
-    a.out = out; a.labels_out = labels_out; a.voxel_row = voxel_row; a.voxel_count = voxel_count; a.voxel_cell = voxel_cell;
-    a.inverse = inverse; a.stats = stats;
-    char *ws = static_cast<char *>(workspace);
-    a.hdr = reinterpret_cast<GridHeader *>(ws); ws += w.hdr;
-    a.records = reinterpret_cast<float *>(ws); ws += w.rec;
-    a.tile_off = reinterpret_cast<int *>(ws); ws += w.tile;
-    a.hist = reinterpret_cast<int *>(ws); ws += w.hist;
-    a.digit_total = reinterpret_cast<int *>(ws); ws += w.digits;
-    a.heads = reinterpret_cast<int *>(ws); ws += w.heads;
-    a.start = reinterpret_cast<int *>(ws); ws += w.start;
-    a.part_max = reinterpret_cast<int *>(ws); ws += w.part;
-    a.pairs_a = reinterpret_cast<unsigned long long *>(ws); ws += w.pairs;
-    a.pairs_b = reinterpret_cast<unsigned long long *>(ws);
-    a.row_tiles = w.row_tiles; a.voxel_grid = w.voxel_grid;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned sgrid = (unsigned)(w.sort_tiles < kSceneMaxGrid ? w.sort_tiles : kSceneMaxGrid);
-    hipLaunchKernelGGL(grid_bounds_kernel, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_frame_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_pairs_kernel, dim3((unsigned)w.row_tiles), dim3(kSceneThreads), 0, s, a);
-    for (int pass = 0; pass < kGridPasses; ++pass) {     // a pass above the cell ids' top bit returns at once
-        hipLaunchKernelGGL(grid_sort_hist_kernel, dim3(sgrid), dim3(kSceneThreads), 0, s, a, pass);
-        hipLaunchKernelGGL(grid_sort_scan_kernel, dim3(kGridDigits), dim3(kGridScanThreads), 0, s, a, pass);
-        hipLaunchKernelGGL(grid_sort_scatter_kernel, dim3(sgrid), dim3(64), 0, s, a, pass);
-    }
-    hipLaunchKernelGGL(grid_heads_kernel<false>, dim3(sgrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_heads_scan_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_heads_kernel<true>, dim3(sgrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_voxel_kernel, dim3((unsigned)w.voxel_grid), dim3(kSceneThreads), 0, s, a);
-    if (mode == 0) {
-        const size_t work = ((size_t)max_voxels * (size_t)K + kSceneThreads - 1) / kSceneThreads;
-        hipLaunchKernelGGL(grid_mean_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
-                           dim3(kSceneThreads), 0, s, a);
-    }
-    hipLaunchKernelGGL(grid_stats_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
-    return hip_ok();
-}
-
-int conv3p_grid_project_labels(const int32_t *voxel_labels, const int32_t *inverse, int64_t N, int64_t M, int32_t *out,
-                               void *stream)
-{
-    if (N < 0 || M < 0) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N == 0) return CONV3P_OK;
-    if (!inverse || !out || (M > 0 && !voxel_labels)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX || M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;   // inverse is int32
-    const size_t work = ((size_t)N + kSceneThreads - 1) / kSceneThreads;
-    hipLaunchKernelGGL(grid_project_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
-                       dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream), voxel_labels, inverse, (long long)N,
-                       (long long)M, out);
-    return hip_ok();
-}
-
-int conv3p_grid_neighbors(const int32_t *voxel_cell, const int32_t *voxel_room, const int32_t *voxel_start,
-                          const int32_t *grid_stats, int max_voxels, int64_t num_rooms, int32_t *neigh, void *stream)
-{
-    if (max_voxels < 0 || num_rooms < 0) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((voxel_room == nullptr) != (voxel_start == nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (max_voxels == 0) return CONV3P_OK;
-    if (!voxel_cell || !grid_stats || !neigh) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (num_rooms > kGridRoomsMaxRooms) return CONV3P_ERR_UNSUPPORTED;
-    const size_t work = ((size_t)max_voxels * 9 + kSceneThreads - 1) / kSceneThreads;
-    hipLaunchKernelGGL(grid_neighbors_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
-                       dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream), voxel_cell, voxel_room, voxel_start,
-                       grid_stats, max_voxels, (int)num_rooms, neigh);
-    return hip_ok();
-}
-
-extern "C++" {
-namespace {
-template <typename S>
-int grid_interpolate(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data, int voxel_K,
-                     const int32_t *neigh, const S *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k,
-                     int32_t *out_labels, float *out_scores, int64_t *stats, void *stream)
-{
-    if (N < 0 || M < 0 || K < 3 || voxel_K < 3 || C < 1 || C > kInterpMaxClass || k < 1 || k > kInterpMaxK)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!stats || (N > 0 && (!data || !inverse || !out_labels)) || (N > 0 && M > 0 && (!voxel_data || !neigh || !voxel_scores)))
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX || M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;   // inverse is int32
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(stats, 0, 3 * sizeof(int64_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
-    if (N == 0) return hip_ok();
-    const size_t work = ((size_t)N + kInterpRows - 1) / kInterpRows;
-    hipLaunchKernelGGL((grid_interpolate_kernel<S>), dim3((unsigned)(work < (size_t)kInterpMaxGrid ? work : (size_t)kInterpMaxGrid)),
-                       dim3(kInterpThreads), 0, s, data, (long long)N, K, inverse, voxel_data, voxel_K, neigh, voxel_scores,
-                       (int)M, C, valid_labels, k, out_labels, out_scores, reinterpret_cast<unsigned long long *>(stats));
-    return hip_ok();
-}
-}  // namespace
-}  // extern "C++": a template
-
-int conv3p_grid_interpolate_f32(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
-                                int voxel_K, const int32_t *neigh, const float *voxel_scores, int64_t M, int C,
-                                const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
-                                void *stream)
-{
-    return grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_scores, M, C, valid_labels, k, out_labels,
-                            out_scores, stats, stream);
-}
-
-int conv3p_grid_interpolate_i64(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
-                                int voxel_K, const int32_t *neigh, const int64_t *voxel_scores, int64_t M, int C,
-                                const int32_t *valid_labels, int k, int32_t *out_labels, float *out_scores, int64_t *stats,
-                                void *stream)
-{
-    return grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, reinterpret_cast<const long long *>(voxel_scores),
-                            M, C, valid_labels, k, out_labels, out_scores, stats, stream);
-}
-
-size_t conv3p_grid_interpolate_rings_workspace_bytes(int64_t N)
-{
-    if (N < 0 || N > (int64_t)INT32_MAX) return 0;
-    return kRingHeaderBytes + up((size_t)N * sizeof(int32_t));       // the list's counter, and a place per row
-}
-
-extern "C++" {
-namespace {
-// The plain pass as it stands, then the list of the rows it left without a candidate, then (rings > 1) their ring search.
-template <typename S>
-int grid_interpolate_rings(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data, int voxel_K,
-                           const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
-                           const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats, const S *voxel_scores,
-                           int64_t M, int C, const int32_t *valid_labels, int k, int rings, int32_t *out_labels,
-                           float *out_scores, int32_t *out_ring, int64_t *stats, int64_t *ring_stats, void *workspace,
-                           size_t workspace_bytes, void *stream)
-{
-    if (N < 0 || M < 0 || K < 3 || voxel_K < 3 || C < 1 || C > kInterpMaxClass || k < 1 || k > kInterpMaxK || rings < 1 ||
-        rings > kRingMax || num_rooms < 0)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((voxel_room == nullptr) != (voxel_start == nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!stats || !ring_stats || (N > 0 && (!data || !inverse || !out_labels)) ||
-        (N > 0 && M > 0 && (!voxel_data || !neigh || !voxel_scores || !voxel_cell || !grid_stats)))
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX || M > (int64_t)INT32_MAX || num_rooms > kGridRoomsMaxRooms) return CONV3P_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < conv3p_grid_interpolate_rings_workspace_bytes(N)) return CONV3P_ERR_INVALID_ARGUMENT;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int32_t *counter = static_cast<int32_t *>(workspace);
-    int32_t *list = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + kRingHeaderBytes);
-    if (hipMemsetAsync(ring_stats, 0, (kRingMax + 1) * sizeof(int64_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
-    if (hipMemsetAsync(counter, 0, sizeof(int32_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
-    const int rc = grid_interpolate(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_scores, M, C, valid_labels, k,
-                                    out_labels, out_scores, stats, stream);
-    if (rc != CONV3P_OK || N == 0) return rc;
-    const size_t work = ((size_t)N + kRingListThreads - 1) / kRingListThreads;
-    hipLaunchKernelGGL(grid_ring_list_kernel, dim3((unsigned)(work < (size_t)kRingListMaxGrid ? work : (size_t)kRingListMaxGrid)),
-                       dim3(kRingListThreads), 0, s, inverse, out_labels, (long long)N, (int)M, rings, counter, list, out_ring,
-                       reinterpret_cast<unsigned long long *>(ring_stats));
-    if (rings > 1)
-        hipLaunchKernelGGL((grid_ring_search_kernel<S>), dim3(kRingGrid), dim3(kRingThreads), 0, s, data, (long long)N, K, inverse,
-                           voxel_data, voxel_K, voxel_cell, voxel_room, voxel_start, (int)num_rooms, grid_stats, voxel_scores,
-                           (int)M, C, valid_labels, k, rings, counter, list, out_labels, out_scores, out_ring,
-                           reinterpret_cast<unsigned long long *>(stats), reinterpret_cast<unsigned long long *>(ring_stats));
-    return hip_ok();
-}
-}  // namespace
-}  // extern "C++": a template
-
-int conv3p_grid_interpolate_rings_f32(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
-                                      int voxel_K, const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
-                                      const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats,
-                                      const float *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k, int rings,
-                                      int32_t *out_labels, float *out_scores, int32_t *out_ring, int64_t *stats,
-                                      int64_t *ring_stats, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return grid_interpolate_rings(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_cell, voxel_room, voxel_start, num_rooms,
-                                  grid_stats, voxel_scores, M, C, valid_labels, k, rings, out_labels, out_scores, out_ring, stats,
-                                  ring_stats, workspace, workspace_bytes, stream);
-}
-
-int conv3p_grid_interpolate_rings_i64(const float *data, int64_t N, int K, const int32_t *inverse, const float *voxel_data,
-                                      int voxel_K, const int32_t *neigh, const int32_t *voxel_cell, const int32_t *voxel_room,
-                                      const int32_t *voxel_start, int64_t num_rooms, const int32_t *grid_stats,
-                                      const int64_t *voxel_scores, int64_t M, int C, const int32_t *valid_labels, int k, int rings,
-                                      int32_t *out_labels, float *out_scores, int32_t *out_ring, int64_t *stats,
-                                      int64_t *ring_stats, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return grid_interpolate_rings(data, N, K, inverse, voxel_data, voxel_K, neigh, voxel_cell, voxel_room, voxel_start, num_rooms,
-                                  grid_stats, reinterpret_cast<const long long *>(voxel_scores), M, C, valid_labels, k, rings,
-                                  out_labels, out_scores, out_ring, stats, ring_stats, workspace, workspace_bytes, stream);
-}
-
-int conv3p_grid_normals_f32(const float *voxel_data, int K, const int32_t *neigh, const int32_t *grid_stats,
-                            const int32_t *voxel_room, const float *viewpoint, int64_t V, int64_t M, int min_neighbors,
-                            float *normals, float *curvature, int32_t *samples, int32_t *flags, float *moments,
-                            int32_t *normal_stats, void *stream)
-{
-    if (M < 0 || K < 3 || min_neighbors < kNormalsMinNeighbors || min_neighbors > kInterpNeigh) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (viewpoint && (V < 1 || (V != 1 && !voxel_room))) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M == 0) return CONV3P_OK;
-    if (!voxel_data || !neigh || !grid_stats || !normals || !curvature || !samples || !flags || !normal_stats)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M > (int64_t)INT32_MAX || (viewpoint && V > (int64_t)INT32_MAX)) return CONV3P_ERR_UNSUPPORTED;   // neigh is int32
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(normal_stats, 0, 4 * sizeof(int32_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
-    const size_t work = ((size_t)M + kNormalsThreads - 1) / kNormalsThreads;
-    hipLaunchKernelGGL(grid_normals_kernel, dim3((unsigned)(work < (size_t)kNormalsMaxGrid ? work : (size_t)kNormalsMaxGrid)),
-                       dim3(kNormalsThreads), 0, s, voxel_data, K, neigh, grid_stats, voxel_room, viewpoint,
-                       viewpoint ? (int)V : 0, (int)M, min_neighbors, normals, curvature, samples, flags, moments, normal_stats);
-    return hip_ok();
-}
-
-namespace {
-// The taps of a connectivity as a mask over t = (dx+1)*9 + (dy+1)*3 + (dz+1); 0 for a connectivity that is none.
-unsigned gseg_tapmask(int connectivity)
-{
-    const int reach = connectivity == 6 ? 1 : (connectivity == 18 ? 2 : (connectivity == 26 ? 3 : 0));
-    unsigned mask = 0;
-    for (int t = 0; t < kInterpNeigh; ++t) {
-        const int d = std::abs(t / 9 - 1) + std::abs(t / 3 % 3 - 1) + std::abs(t % 3 - 1);
-        if (d >= 1 && d <= reach) mask |= 1u << t;
-    }
-    return mask;
-}
-size_t gseg_tiles(int64_t M) { return ((size_t)M + kGsegTile - 1) / kGsegTile; }
-unsigned gseg_grid(size_t work) { return (unsigned)(work < (size_t)kGsegMaxGrid ? (work ? work : 1) : (size_t)kGsegMaxGrid); }
-}  // namespace
-
-size_t conv3p_grid_segments_workspace_bytes(int64_t M)
-{
-    if (M <= 0 || M > (int64_t)INT32_MAX) return 0;
-    return up(gseg_tiles(M) * sizeof(int32_t)) + 2 * up((size_t)M * sizeof(int32_t));   // tiles' roots, lab, parent
-}
-
-int conv3p_grid_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *voxel_count,
-                         const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment,
-                         int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label, int32_t *seg_stats,
-                         void *workspace, size_t workspace_bytes, void *stream)
-{
-    const unsigned tapmask = gseg_tapmask(connectivity);
-    if (M < 0 || (voxel_labels && (L < 0 || L > M)) || num_class < 1 || num_class > kGsegMaxClass || !tapmask)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M == 0) return CONV3P_OK;
-    if (!neigh || !voxel_count || !grid_stats || !segment || !seg_root || !seg_size || !seg_rows || !seg_label || !seg_stats)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < conv3p_grid_segments_workspace_bytes(M)) return CONV3P_ERR_INVALID_ARGUMENT;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int m = (int)M, ntiles = (int)gseg_tiles(M);
-    char *ws = static_cast<char *>(workspace);
-    int32_t *tile_count = reinterpret_cast<int32_t *>(ws);
-    int32_t *lab = reinterpret_cast<int32_t *>(ws + up((size_t)ntiles * sizeof(int32_t)));
-    int32_t *parent = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(lab) + up((size_t)M * sizeof(int32_t)));
-    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)ntiles);
-    hipLaunchKernelGGL(gseg_local_kernel, dim3(gseg_grid(((size_t)M + kGsegLocalTile - 1) / kGsegLocalTile)),
-                       dim3(kGsegLocalTile), 0, s, neigh, voxel_labels,
-                       voxel_labels ? (int)L : 0, grid_stats, m, voxel_labels ? num_class : 1, tapmask, lab, parent, seg_root,
-                       seg_size, seg_rows, seg_label, seg_stats);
-    hipLaunchKernelGGL(gseg_link_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, neigh, lab, parent, grid_stats, m, tapmask);
-    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count);
-    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, tile_count, static_cast<int32_t *>(nullptr),
-                       ntiles, seg_stats, static_cast<int32_t *>(nullptr));
-    hipLaunchKernelGGL(gseg_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count, segment,
-                       seg_root, seg_label);
-    // consecutive voxels a wave: more of them where there are waves enough to fill the device anyway
-    const int steps = M >= (1 << 20) ? 16 : (M >= (1 << 16) ? 4 : 1);
-    const size_t per_wave = (size_t)64 * steps * (kGsegThreads / 64);
-    hipLaunchKernelGGL(gseg_assign_kernel, dim3(gseg_grid(((size_t)M + per_wave - 1) / per_wave)), dim3(kGsegThreads), 0, s, lab,
-                       parent, voxel_count, grid_stats, m, steps, segment, seg_size, seg_rows, seg_stats);
-    hipLaunchKernelGGL(gseg_max_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_size, seg_rows, m, seg_stats);
-    return hip_ok();
-}
-
-size_t conv3p_grid_absorb_workspace_bytes(int64_t M)
-{
-    if (M <= 0 || M > (int64_t)INT32_MAX) return 0;
-    // the two counts, two words per tile of segments, and cursor, small_list, small_off, members
-    return kGsegHeaderBytes + 2 * up(gseg_tiles(M) * sizeof(int32_t)) + 4 * up((size_t)M * sizeof(int32_t));
-}
-
-int conv3p_grid_absorb_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *segment,
-                                const int32_t *seg_size, const int32_t *seg_label, const int32_t *seg_stats,
-                                const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int min_size,
-                                int drop_orphans, int32_t *labels_out, int32_t *seg_label_out, int64_t *absorb_stats,
-                                void *workspace, size_t workspace_bytes, void *stream)
-{
-    const unsigned tapmask = gseg_tapmask(connectivity);
-    if (M < 0 || (voxel_labels && (L < 0 || L > M)) || num_class < 1 || num_class > kGsegMaxClass || !tapmask || min_size < 1 ||
-        (drop_orphans != 0 && drop_orphans != 1))
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M == 0) return CONV3P_OK;
-    if (!neigh || !segment || !seg_size || !seg_label || !seg_stats || !grid_stats || !labels_out || !seg_label_out ||
-        !absorb_stats)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < conv3p_grid_absorb_workspace_bytes(M)) return CONV3P_ERR_INVALID_ARGUMENT;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t tile_bytes = up(gseg_tiles(M) * sizeof(int32_t)), row_bytes = up((size_t)M * sizeof(int32_t));
-    char *ws = static_cast<char *>(workspace);
-    AbsorbArgs p{};
-    p.neigh = neigh; p.voxel_labels = voxel_labels; p.segment = segment; p.seg_size = seg_size; p.seg_label = seg_label;
-    p.seg_stats = seg_stats; p.grid_stats = grid_stats;
-    p.L = voxel_labels ? (int)L : 0; p.M = (int)M; p.num_class = voxel_labels ? num_class : 1; p.min_size = min_size;
-    p.drop_orphans = drop_orphans; p.ntiles = (int)gseg_tiles(M); p.tapmask = tapmask;
-    p.labels_out = labels_out; p.seg_label_out = seg_label_out;
-    p.stats = reinterpret_cast<unsigned long long *>(absorb_stats);
-    p.hdr = reinterpret_cast<int32_t *>(ws);
-    p.tile_small = reinterpret_cast<int32_t *>(ws + kGsegHeaderBytes);
-    p.tile_members = reinterpret_cast<int32_t *>(ws + kGsegHeaderBytes + tile_bytes);
-    char *rows = ws + kGsegHeaderBytes + 2 * tile_bytes;
-    p.cursor = reinterpret_cast<int32_t *>(rows);
-    p.small_list = reinterpret_cast<int32_t *>(rows + row_bytes);
-    p.small_off = reinterpret_cast<int32_t *>(rows + 2 * row_bytes);
-    p.members = reinterpret_cast<int32_t *>(rows + 3 * row_bytes);
-    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)p.ntiles);
-    hipLaunchKernelGGL(absorb_count_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
-    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, p.tile_small, p.tile_members, p.ntiles, p.hdr,
-                       p.hdr + 1);
-    hipLaunchKernelGGL(absorb_plan_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
-    hipLaunchKernelGGL(absorb_scatter_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
-    hipLaunchKernelGGL(absorb_vote_kernel, dim3(gseg_grid(((size_t)M + kGsegThreads / 64 - 1) / (kGsegThreads / 64))),
-                       dim3(kGsegThreads), 0, s, p);      // a wave per small segment, and there are at most M
-    hipLaunchKernelGGL(absorb_labels_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
-    return hip_ok();
-}
-
-namespace {
-// The workspace of conv3p_grid_subsample_rooms_f32 (conv3p_grid_rooms.hpp): the single call's words -- the records grown
-// by one per room, the tiles' pair offsets giving way to the voxel tiles' maxima -- and per room a frame and two prefixes.
-struct GridRoomsPlan {
-    GridPlan g;
-    size_t xhdr, room, cbase, pbase, rec, total;
-};
-bool grid_rooms_plan(int64_t N, int64_t R, int max_voxels, GridRoomsPlan &w)
-{
-    if (R <= 0 || R > kGridRoomsMaxRooms || !grid_plan(N, max_voxels, w.g)) return false;
-    w.xhdr = up(sizeof(GridRoomsHeader));
-    w.room = up((size_t)R * sizeof(GridRoomFrame));
-    w.cbase = up(((size_t)R + 1) * sizeof(long long));
-    w.pbase = up(((size_t)R + 1) * sizeof(int));
-    w.rec = up(((size_t)w.g.row_tiles + (size_t)R) * 8 * sizeof(float));
-    w.total = w.g.hdr + w.xhdr + w.room + w.cbase + w.pbase + w.rec + w.g.tile + w.g.hist + w.g.digits + w.g.heads +
-              w.g.start + w.g.part + 2 * w.g.pairs;
-    return true;
-}
-}  // namespace
-
-size_t conv3p_grid_subsample_rooms_workspace_bytes(int64_t N, int64_t R, int max_voxels)
-{
-    GridRoomsPlan w;
-    return grid_rooms_plan(N, R, max_voxels, w) ? w.total : 0;
-}
-
-// Every status first, in the order include/conv3p.h gives; then the launches, their number fixed by mode alone.
-int conv3p_grid_subsample_rooms_f32(const float *data, const void *labels, const int32_t *room_start, int64_t N, int64_t R,
-                                    int K, int label_bytes, float voxel, int mode, int num_class, int max_voxels,
-                                    float *out, int32_t *labels_out, int32_t *voxel_row, int32_t *voxel_count,
-                                    int32_t *voxel_cell, int32_t *voxel_room, int32_t *voxel_start, int32_t *inverse,
-                                    int32_t *room_stats, int32_t *stats, void *workspace, size_t workspace_bytes,
-                                    void *stream)
-{
-    if (N < 0 || R < 0 || K < 3 || max_voxels < 0 || (mode != 0 && mode != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((labels != nullptr) != (labels_out != nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (labels && label_bytes != 1 && label_bytes != 4 && label_bytes != 8) return CONV3P_ERR_INVALID_ARGUMENT;
-    const bool votes = labels && mode == 0;              // num_class is read by the majority only
-    if (votes && num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (R == 0 || N == 0 || max_voxels == 0) return CONV3P_OK;
-    if (!data || !room_start || !out || !voxel_row || !voxel_count || !voxel_cell || !voxel_room || !voxel_start ||
-        !inverse || !room_stats || !stats)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > kGridMaxN || R > kGridRoomsMaxRooms || K > 65536 || (votes && num_class > kGridMaxClass))
-        return CONV3P_ERR_UNSUPPORTED;
-    GridRoomsPlan w;
-    if (!grid_rooms_plan(N, R, max_voxels, w)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, w.total));
-    GridRoomsArgs a;
-    GridArgs &g = a.g;
-    g.data = data; g.labels = labels;
-    g.N = (int)N; g.K = K; g.label_bytes = label_bytes; g.mode = mode; g.num_class = num_class; g.max_voxels = max_voxels;
-    g.voxel = voxel;
-    g.out = out; g.labels_out = labels_out; g.voxel_row = voxel_row; g.voxel_count = voxel_count; g.voxel_cell = voxel_cell;
-    g.inverse = inverse; g.stats = stats;
-    a.room_start = room_start; a.R = (int)R;
-    a.voxel_room = voxel_room; a.voxel_start = voxel_start; a.room_stats = room_stats;
-    char *ws = static_cast<char *>(workspace);
-    g.hdr = reinterpret_cast<GridHeader *>(ws); ws += w.g.hdr;
-    a.xh = reinterpret_cast<GridRoomsHeader *>(ws); ws += w.xhdr;
-    a.room = reinterpret_cast<GridRoomFrame *>(ws); ws += w.room;
-    a.cell_base = reinterpret_cast<long long *>(ws); ws += w.cbase;
-    a.pair_base = reinterpret_cast<int *>(ws); ws += w.pbase;
-    g.records = reinterpret_cast<float *>(ws); ws += w.rec;
-    a.tile_max = reinterpret_cast<int *>(ws); ws += w.g.tile;
-    g.tile_off = nullptr;
-    g.hist = reinterpret_cast<int *>(ws); ws += w.g.hist;
-    g.digit_total = reinterpret_cast<int *>(ws); ws += w.g.digits;
-    g.heads = reinterpret_cast<int *>(ws); ws += w.g.heads;
-    g.start = reinterpret_cast<int *>(ws); ws += w.g.start;
-    g.part_max = reinterpret_cast<int *>(ws); ws += w.g.part;
-    g.pairs_a = reinterpret_cast<unsigned long long *>(ws); ws += w.g.pairs;
-    g.pairs_b = reinterpret_cast<unsigned long long *>(ws);
-    g.row_tiles = w.g.row_tiles; g.voxel_grid = w.g.voxel_grid;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned tgrid = (unsigned)w.g.row_tiles;
-    const unsigned rgrid = (unsigned)(R < kSceneMaxGrid ? R : kSceneMaxGrid);
-    const unsigned sgrid = (unsigned)(w.g.sort_tiles < kSceneMaxGrid ? w.g.sort_tiles : kSceneMaxGrid);
-    hipLaunchKernelGGL(grid_rooms_check_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_rooms_bounds_kernel, dim3(tgrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_rooms_frame_kernel, dim3(rgrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_rooms_base_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_rooms_pairs_kernel, dim3(tgrid), dim3(kSceneThreads), 0, s, a);
-    for (int pass = 0; pass < kGridPasses; ++pass) {     // a pass above the global cell ids' top bit returns at once
-        hipLaunchKernelGGL(grid_sort_hist_kernel, dim3(sgrid), dim3(kSceneThreads), 0, s, g, pass);
-        hipLaunchKernelGGL(grid_sort_scan_kernel, dim3(kGridDigits), dim3(kGridScanThreads), 0, s, g, pass);
-        hipLaunchKernelGGL(grid_sort_scatter_kernel, dim3(sgrid), dim3(64), 0, s, g, pass);
-    }
-    hipLaunchKernelGGL(grid_heads_kernel<false>, dim3(sgrid), dim3(kSceneThreads), 0, s, g);
-    hipLaunchKernelGGL(grid_heads_scan_kernel, dim3(1), dim3(kGridScanThreads), 0, s, g);
-    hipLaunchKernelGGL(grid_heads_kernel<true>, dim3(sgrid), dim3(kSceneThreads), 0, s, g);
-    hipLaunchKernelGGL(grid_rooms_voxel_kernel, dim3((unsigned)w.g.voxel_grid), dim3(kSceneThreads), 0, s, a);
-    if (mode == 0) {
-        const size_t work = ((size_t)max_voxels * (size_t)K + kSceneThreads - 1) / kSceneThreads;
-        hipLaunchKernelGGL(grid_mean_kernel, dim3((unsigned)(work < (size_t)kSceneMaxGrid ? work : (size_t)kSceneMaxGrid)),
-                           dim3(kSceneThreads), 0, s, g);
-    }
-    hipLaunchKernelGGL(grid_rooms_count_max_kernel, dim3(tgrid), dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_rooms_out_kernel, dim3((unsigned)((R + 3) / 4 < kSceneMaxGrid ? (R + 3) / 4 : kSceneMaxGrid)),
-                       dim3(kSceneThreads), 0, s, a);
-    hipLaunchKernelGGL(grid_rooms_stats_kernel, dim3(1), dim3(kGridScanThreads), 0, s, a);
-    return hip_ok();
-}
-
-int conv3p_scene_vote(const int32_t *pred, const int32_t *index, size_t rows, int64_t N, int num_class, int32_t *votes,
-                      void *stream)
-{
-    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (rows == 0 || N == 0) return CONV3P_OK;
-    if (!pred || !index || !votes) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;              // index is int32
-    hipLaunchKernelGGL(scene_vote_kernel, dim3(scene_grid(rows)), dim3(kSceneThreads), 0, static_cast<hipStream_t>(stream),
-                       pred, index, rows, (long long)N, num_class, votes);
-    return hip_ok();
-}
-
-size_t conv3p_scene_vote_labels_workspace_bytes(int64_t N, int num_class)
-{
-    if (N <= 0 || N > (int64_t)INT32_MAX || num_class < 1) return 0;
-    return up((size_t)kSceneMaxRecords * sizeof(long long));
-}
-
-int conv3p_scene_vote_labels(const int32_t *votes, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
-                             void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N == 0) return CONV3P_OK;
-    if (!votes || !label_out || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, conv3p_scene_vote_labels_workspace_bytes(N, num_class)));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned grid = scene_grid((size_t)N);
-    long long *partial = static_cast<long long *>(workspace);
-    hipLaunchKernelGGL(scene_vote_labels_kernel, dim3(grid), dim3(kSceneThreads), 0, s, votes, (long long)N, num_class,
-                       label_out, partial);
-    hipLaunchKernelGGL(scene_vote_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, (const long long *)partial, (int)grid,
-                       (long long)N, reinterpret_cast<long long *>(stats));
-    return hip_ok();
-}
-
-// Waves per workgroup of conv3p_scene_vote_scores_f32: four while their tiles fit 48 KB of LDS, then two, then one (128
-// classes: 33.6 KB a wave).
-int conv3p_scene_vote_scores_f32(const float *logits, const int32_t *index, size_t rows, int64_t N, int num_class,
-                                 int64_t *scores, int64_t *stats, void *stream)
-{
-    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (rows == 0 || N == 0) return CONV3P_OK;
-    if (!logits || !index || !scores || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX || num_class > kScoreMaxClass) return CONV3P_ERR_UNSUPPORTED;
-    const int nw = score_lds_bytes(4, num_class) <= 48 * 1024 ? 4 : score_lds_bytes(2, num_class) <= 48 * 1024 ? 2 : 1;
-    const size_t lds = score_lds_bytes(nw, num_class);
-    const size_t tiles = (rows + 63) / 64, wgs = (tiles + nw - 1) / nw;
-    const unsigned grid = (unsigned)(wgs < (size_t)kSceneMaxRecords ? wgs : (size_t)kSceneMaxRecords);
-    hipLaunchKernelGGL(scene_vote_scores_kernel, dim3(grid), dim3(64 * nw), lds, static_cast<hipStream_t>(stream), logits,
-                       index, rows, (long long)N, num_class, reinterpret_cast<long long *>(scores),
-                       reinterpret_cast<long long *>(stats));
-    return hip_ok();
-}
-
-size_t conv3p_scene_score_labels_workspace_bytes(int64_t N, int num_class)
-{
-    if (N <= 0 || N > (int64_t)INT32_MAX || num_class < 1 || num_class > kScoreMaxClass) return 0;
-    return up((size_t)kSceneMaxRecords * sizeof(long long));
-}
-
-int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, int32_t *label_out, int64_t *stats,
-                              void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (N < 0 || num_class < 1) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N == 0) return CONV3P_OK;
-    if (!scores || !label_out || !stats) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (N > (int64_t)INT32_MAX || num_class > kScoreMaxClass) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, conv3p_scene_score_labels_workspace_bytes(N, num_class)));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned grid = scene_grid((size_t)N);
-    long long *partial = static_cast<long long *>(workspace);
-    hipLaunchKernelGGL(scene_score_labels_kernel, dim3(grid), dim3(kSceneThreads), 0, s,
-                       reinterpret_cast<const long long *>(scores), (long long)N, num_class, label_out, partial);
-    hipLaunchKernelGGL(scene_vote_finish_kernel, dim3(1), dim3(kSceneMaxRecords), 0, s, (const long long *)partial, (int)grid,
-                       (long long)N, reinterpret_cast<long long *>(stats));
-    return hip_ok();
-}
-
-namespace {
-struct FcPlan { int kc, chunks, mblocks, nblocks; size_t part_bytes, dz_bytes; };
-bool fc_plan(int M, int K, int N, FcPlan &p)
-{
-    if (M < 1 || K < 1 || N < 1 || (N % 8) != 0 || N > 1024 || M > 128) return false;
-    int kc = (K + 255) / 256;                     // ~256 workgroups along K ...
-    kc = (kc + 1) & ~1;
-    if (kc < 32) kc = 32;
-    if (kc > 480) kc = 480;                       // ... with the x chunk [32][kc + 1] within 64 KiB of LDS
-    p.kc = kc;
-    p.chunks = (K + kc - 1) / kc;
-    p.mblocks = (M + 31) / 32;
-    p.nblocks = (N + kFcCols - 1) / kFcCols;
-    p.part_bytes = up((size_t)p.chunks * p.mblocks * 32 * N * 4);
-    p.dz_bytes = up((size_t)M * N * 4);
-    return true;
-}
-}  // namespace
-
-size_t conv3p_fc_workspace_bytes(int M, int K, int N)
-{
-    FcPlan p;
-    if (!fc_plan(M, K, N, p)) return 0;
-    return p.part_bytes > p.dz_bytes ? p.part_bytes : p.dz_bytes;
-}
-
-int conv3p_fc_forward_f32(const float *x, const float *W, const float *b, int M, int K, int N, int act, float *y,
-                          void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (M < 0 || K < 0 || N < 0 || (act != 0 && act != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((size_t)M * N == 0) return CONV3P_OK;
-    if (!x || !W || !y || K == 0) return CONV3P_ERR_INVALID_ARGUMENT;
-    FcPlan p;
-    if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, p.part_bytes));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *part = static_cast<float *>(workspace);
-    {
-        Scope sc(K_FC_FWD, s);
-        const int psteps = ((p.kc + 1) / 2 + kFcDepth - 1) / kFcDepth * kFcDepth;
-        const size_t lds = (size_t)32 * (2 * psteps + 1) * 4;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fc_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(fc_forward_kernel, dim3((unsigned)p.chunks, (unsigned)p.mblocks, (unsigned)p.nblocks), dim3(256), lds, s,
-                           x, W, M, K, N, p.kc, part);
-        const size_t n = (size_t)M * N;
-        hipLaunchKernelGGL(fc_finish_kernel, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, s, part, b, M, N, p.chunks,
-                           p.mblocks, act, y);
-    }
-    return hip_ok();
-}
-
-int conv3p_fc_backward_f32(const float *x, const float *W, const float *y, const float *dy, int M, int K, int N,
-                           int act, float *dx, float *dW, float *db, void *workspace, size_t workspace_bytes,
-                           void *stream)
-{
-    if (M < 0 || K < 0 || N < 0 || (act != 0 && act != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((size_t)K * N == 0) return CONV3P_OK;
-    if (M == 0) return zero_async(dW, (size_t)K * N * 4, static_cast<hipStream_t>(stream));
-    if (!x || !W || !dy || !dW || (act && !y)) return CONV3P_ERR_INVALID_ARGUMENT;
-    FcPlan p;
-    if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, p.dz_bytes));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *dz = static_cast<float *>(workspace);
-    const int dw_steps = M <= 32 ? 16 : M <= 64 ? 32 : 64;
-    if ((size_t)2 * dw_steps * (N + 1) * 4 > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // before anything is launched
-    hipLaunchKernelGGL(fc_dz_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, y, dy, M, N, act, dz, db);
-    TRY(hip_ok());
-    // waves per workgroup of the two streaming kernels: 32 rows of W per wave, the whole grid in ONE resident round
-    // (two workgroups of ~66 KiB of LDS per CU: 512 slots) -- the model's fc1 (73 728 rows): 5 waves, 461 workgroups
-    auto waves_for = [&](int slots) {
-        const int tiles = (K + 31) / 32;
-        int nw = (tiles + slots - 1) / slots;
-        return nw < 4 ? 4 : (nw > 8 ? 8 : nw);
-    };
-    {
-        Scope sc(K_FC_DW, s);
-        auto launch = [&](auto kern, int steps) {
-            const size_t lds = (size_t)2 * steps * (N + 1) * 4;
-            const int nw = waves_for(lds <= 80 * 1024 ? 512 : 256);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)((K + 32 * nw - 1) / (32 * nw))), dim3(64 * nw), lds, s, x, dz, M, K, N, dW);
-        };
-        if (M <= 32) launch(fc_dw_kernel<16>, 16);
-        else if (M <= 64) launch(fc_dw_kernel<32>, 32);
-        else launch(fc_dw_kernel<64>, 64);
-    }
-    TRY(hip_ok());
-    if (dx != nullptr) {
-        Scope sc(K_FC_DX, s);
-        const int psteps = (N / 8 + 7) / 8 * 8;                            // (fc_dx_kernel's kD)
-        size_t lds = (size_t)32 * (8 * psteps + 4) * 4;                   // the dz tile; the transpose tiles reuse it
-        const int nw = waves_for(lds <= 80 * 1024 ? 512 : 256);
-        if (lds < (size_t)nw * 32 * 33 * 4) lds = (size_t)nw * 32 * 33 * 4;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fc_dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(fc_dx_kernel, dim3((unsigned)((K + 32 * nw - 1) / (32 * nw)), (unsigned)p.mblocks), dim3(64 * nw), lds, s, dz, W,
-                           M, K, N, dx);
-    }
-    return hip_ok();
-}
-
-size_t conv3p_seg_head_workspace_bytes(size_t rows, int num_class)
-{
-    if (rows == 0 || num_class < 2 || num_class > kSegMaxClass) return 0;
-    const size_t tiles = (rows + 63) / 64;   // (one-wave workgroups, the most records either element type takes)
-    return up((tiles < (size_t)kSegMaxGrid ? tiles : (size_t)kSegMaxGrid) * seg_record_bytes(num_class));
-}
-int conv3p_seg_head_f32(const float *act, const int32_t *labels, size_t rows, int num_class, float grad_scale,
-                        float *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
-                        size_t workspace_bytes, void *stream)
-{
-    return seg_head_impl<float>(act, labels, rows, num_class, grad_scale, grad_act, pred, loss_sum, counts, workspace,
-                                workspace_bytes, stream);
-}
-int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, int num_class, double grad_scale,
-                        double *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
-                        size_t workspace_bytes, void *stream)
-{
-    return seg_head_impl<double>(act, labels, rows, num_class, grad_scale, grad_act, pred, loss_sum, counts, workspace,
-                                 workspace_bytes, stream);
-}
-
-size_t conv3p_seg_head_weighted_workspace_bytes(size_t rows, int num_class)
-{
-    const size_t head = conv3p_seg_head_workspace_bytes(rows, num_class);
-    if (head == 0) return 0;
-    const size_t total = seg_total_bytes(rows);
-    return head > total ? head : total;
-}
-int conv3p_seg_weight_total_f32(const int32_t *labels, size_t rows, int num_class, const float *class_weight,
-                                const float *point_weight, double *total, void *workspace, size_t workspace_bytes,
-                                void *stream)
-{
-    return seg_weight_total_impl<float>(labels, rows, num_class, class_weight, point_weight, total, workspace,
-                                        workspace_bytes, stream);
-}
-int conv3p_seg_weight_total_f64(const int32_t *labels, size_t rows, int num_class, const double *class_weight,
-                                const double *point_weight, double *total, void *workspace, size_t workspace_bytes,
-                                void *stream)
-{
-    return seg_weight_total_impl<double>(labels, rows, num_class, class_weight, point_weight, total, workspace,
-                                         workspace_bytes, stream);
-}
-int conv3p_seg_head_weighted_f32(const float *act, const int32_t *labels, size_t rows, int num_class,
-                                 const float *class_weight, const float *point_weight, double label_smoothing,
-                                 float grad_scale, const double *denominator, float *grad_act, int32_t *pred,
-                                 double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return seg_head_weighted_impl<float>(act, labels, rows, num_class, class_weight, point_weight, label_smoothing,
-                                         grad_scale, denominator, grad_act, pred, loss_sum, counts, workspace,
-                                         workspace_bytes, stream);
-}
-int conv3p_seg_head_weighted_f64(const double *act, const int32_t *labels, size_t rows, int num_class,
-                                 const double *class_weight, const double *point_weight, double label_smoothing,
-                                 double grad_scale, const double *denominator, double *grad_act, int32_t *pred,
-                                 double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return seg_head_weighted_impl<double>(act, labels, rows, num_class, class_weight, point_weight, label_smoothing,
-                                          grad_scale, denominator, grad_act, pred, loss_sum, counts, workspace,
-                                          workspace_bytes, stream);
-}
-
-size_t conv3p_seg_confusion_workspace_bytes(size_t rows, int num_class)
-{
-    if (rows == 0 || num_class < 2 || num_class > kSegMaxClass) return 0;
-    return up((size_t)seg_conf_grid(rows) * num_class * num_class * sizeof(int));
-}
-int conv3p_seg_confusion(const int32_t *labels, const int32_t *pred, size_t rows, int num_class, int64_t *confusion,
-                         void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (rows == 0 || num_class < 2 || !labels || !pred || !confusion) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (num_class > kSegMaxClass || rows > ((size_t)1 << 36)) return CONV3P_ERR_UNSUPPORTED;   // (int32 partial counters)
-    TRY(buf_check(workspace, workspace_bytes, conv3p_seg_confusion_workspace_bytes(rows, num_class)));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int *part = static_cast<int *>(workspace);
-    const unsigned grid = seg_conf_grid(rows);
-    const int cells = num_class * num_class;
-    const size_t lds = (size_t)cells * sizeof(int);
-    {
-        Scope sc(K_SEG_HEAD, s);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(seg_confusion_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(seg_confusion_kernel, dim3(grid), dim3(kSegConfThreads), lds, s, labels, pred, rows, num_class,
-                           part);
-        hipLaunchKernelGGL(seg_confusion_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, part,
-                           (int)grid, cells, reinterpret_cast<long long *>(confusion));
-    }
-    return hip_ok();
-}
-
-int conv3p_momentum_step_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
-                             const size_t *numels, float lr, float momentum, void *stream)
-{
-    return momentum_step_impl<float>(n_tensors, params, grads, accums, numels, lr, momentum, stream);
-}
-int conv3p_momentum_step_f64(int n_tensors, double *const *params, const double *const *grads, double *const *accums,
-                             const size_t *numels, double lr, double momentum, void *stream)
-{
-    return momentum_step_impl<double>(n_tensors, params, grads, accums, numels, lr, momentum, stream);
-}
-
-size_t conv3p_grad_norm_workspace_bytes(void) { return grad_norm_bytes(); }
-int conv3p_grad_norm_f32(int n_tensors, const float *const *grads, const size_t *numels, double *stats, int accumulate,
-                         void *workspace, size_t workspace_bytes, void *stream)
-{
-    return grad_norm_impl<float>(n_tensors, grads, numels, stats, accumulate, workspace, workspace_bytes, stream);
-}
-int conv3p_grad_norm_f64(int n_tensors, const double *const *grads, const size_t *numels, double *stats, int accumulate,
-                         void *workspace, size_t workspace_bytes, void *stream)
-{
-    return grad_norm_impl<double>(n_tensors, grads, numels, stats, accumulate, workspace, workspace_bytes, stream);
-}
-int conv3p_momentum_step_guarded_f32(int n_tensors, float *const *params, const float *const *grads, float *const *accums,
-                                     const size_t *numels, float lr, float momentum, int nesterov, float clip_norm,
-                                     int skip_nonfinite, const double *stats, void *stream)
-{
-    return momentum_step_guarded_impl<float>(n_tensors, params, grads, accums, numels, lr, momentum, nesterov, clip_norm,
-                                             skip_nonfinite, stats, stream);
-}
-int conv3p_momentum_step_guarded_f64(int n_tensors, double *const *params, const double *const *grads,
-                                     double *const *accums, const size_t *numels, double lr, double momentum, int nesterov,
-                                     double clip_norm, int skip_nonfinite, const double *stats, void *stream)
-{
-    return momentum_step_guarded_impl<double>(n_tensors, params, grads, accums, numels, lr, momentum, nesterov, clip_norm,
-                                              skip_nonfinite, stats, stream);
-}
-int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float *y, const float *dy, int M, int K, int N,
-                                int act, float *dx, float *accum_W, float *accum_b, float lr, float momentum,
-                                void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (M < 0 || K < 0 || N < 0 || (act != 0 && act != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((b == nullptr) != (accum_b == nullptr)) return CONV3P_ERR_INVALID_ARGUMENT;
-    if ((size_t)K * N == 0) return CONV3P_OK;
-    if (M == 0) return CONV3P_ERR_INVALID_ARGUMENT;
-    if (!x || !W || !dy || !accum_W || (act && !y)) return CONV3P_ERR_INVALID_ARGUMENT;
-    FcPlan p;
-    if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, p.dz_bytes));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *dz = static_cast<float *>(workspace);
-    const int dw_steps = M <= 32 ? 16 : M <= 64 ? 32 : 64;
-    if ((size_t)2 * dw_steps * (N + 1) * 4 > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // before anything is launched
-    hipLaunchKernelGGL(fc_dz_step_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, y, dy, M, N, act, dz, b, accum_b,
-                       lr, momentum);
-    TRY(hip_ok());
-    auto waves_for = [&](int slots) {                                      // as conv3p_fc_backward_f32
-        const int tiles = (K + 31) / 32;
-        int nw = (tiles + slots - 1) / slots;
-        return nw < 4 ? 4 : (nw > 8 ? 8 : nw);
-    };
-    if (dx != nullptr) {                                                   // FIRST: dx = dz . W^T needs the old W
-        Scope sc(K_FC_DX, s);
-        const int psteps = (N / 8 + 7) / 8 * 8;
-        size_t lds = (size_t)32 * (8 * psteps + 4) * 4;
-        const int nw = waves_for(lds <= 80 * 1024 ? 512 : 256);
-        if (lds < (size_t)nw * 32 * 33 * 4) lds = (size_t)nw * 32 * 33 * 4;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fc_dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(fc_dx_kernel, dim3((unsigned)((K + 32 * nw - 1) / (32 * nw)), (unsigned)p.mblocks), dim3(64 * nw), lds, s, dz, W,
-                           M, K, N, dx);
-    }
-    TRY(hip_ok());
-    {
-        Scope sc(K_FC_DW, s);                                              // (no profile kind of its own: the table is pinned)
-        auto launch = [&](auto kern, int steps) {
-            const size_t lds = (size_t)2 * steps * (N + 1) * 4;
-            const int nw = waves_for(lds <= 80 * 1024 ? 512 : 256);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)((K + 32 * nw - 1) / (32 * nw))), dim3(64 * nw), lds, s, x, dz, M, K, N, W,
-                               accum_W, lr, momentum);
-        };
-        if (M <= 32) launch(fc_dw_step_kernel<16>, 16);
-        else if (M <= 64) launch(fc_dw_step_kernel<32>, 32);
-        else launch(fc_dw_step_kernel<64>, 64);
-    }
-    return hip_ok();
-}
-
-size_t conv3p_cls_tail_workspace_bytes(int M, int H, int C)
-{
-    ClsPlan p;
-    return cls_plan(M, H, C, p) ? p.total : 0;
-}
-int conv3p_cls_tail_f32(const float *fc1, const float *W2, const float *b2, const int32_t *labels, int M, int H, int C,
-                        int training, double rate, const float *keep_mask, uint64_t seed, uint64_t step, float grad_scale,
-                        float *logits, int32_t *pred, float *dfc1, float *dW2, float *db2, uint8_t *keep_out,
-                        double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return cls_tail_impl(fc1, const_cast<float *>(W2), const_cast<float *>(b2), labels, M, H, C, training, rate, keep_mask,
-                         seed, step, grad_scale, logits, pred, dfc1, dW2, db2, nullptr, nullptr, 0.0f, 0.0f, keep_out,
-                         loss_sum, counts, workspace, workspace_bytes, stream);
-}
-int conv3p_cls_tail_step_f32(const float *fc1, float *W2, float *b2, const int32_t *labels, int M, int H, int C,
-                             int training, double rate, const float *keep_mask, uint64_t seed, uint64_t step,
-                             float grad_scale, float *logits, int32_t *pred, float *dfc1, float *accum_W2, float *accum_b2,
-                             float lr, float momentum, uint8_t *keep_out, double *loss_sum, int64_t *counts,
-                             void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!accum_W2 || !accum_b2 || !dfc1) return CONV3P_ERR_INVALID_ARGUMENT;
-    return cls_tail_impl(fc1, W2, b2, labels, M, H, C, training, rate, keep_mask, seed, step, grad_scale, logits, pred, dfc1,
-                         nullptr, nullptr, accum_W2, accum_b2, lr, momentum, keep_out, loss_sum, counts, workspace,
-                         workspace_bytes, stream);
-}
-
 int conv3p_profile_enable(int on)
 {
     std::lock_guard<std::mutex> lk(g_prof.mu);
@@ -4744,3 +3105,8 @@ const char *conv3p_status_string(int status)
 int conv3p_abi_version(void) { return CONV3P_ABI_VERSION; }
 
 }  // extern "C"
+
+#include "conv3p_abi_heads.hpp"
+#include "conv3p_abi_prestep.hpp"
+#include "conv3p_abi_scene.hpp"
+#include "conv3p_abi_grid.hpp"
