@@ -905,6 +905,58 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   the data; no host read: ne, S and the number of small segments stay on the device.  The union-find is lock-free: its
  *   entries only ever decrease, so every retry follows another thread's progress and no loop waits for a thread to arrive.
  *   The only atomics are int32 CAS / min / max / add and the int64 adds of absorb_stats; bitwise reproducible.
+ *
+ * conv3p_grid_segment_geometry:  where every segment is, how large it is in space and how it is oriented -- the step from
+ *   a segmentation to a list of objects (pointwise_amd/csrc/conv3p_grid_geometry.hpp; tests/grid_geometry_ref.py restates it
+ *   in numpy).  voxel_data (M, K) with row stride K, xyz first; voxel_cell int32 (M, 3) and voxel_count int32 (M) as the
+ *   subsampling writes them; segment int32 (M) and seg_stats as conv3p_grid_segments writes them; grid_stats the
+ *   subsampling's stats; weight 0 (every voxel counts once) or 1 (every voxel counts as its raw rows).  The voxels sit on
+ *   an integer lattice that is isotropic: lattice units become metres by one scale, the subsampling's voxel, and one shift,
+ *   the cloud's (in the many-clouds result: the room's) minimum corner.
+ *    G1. ne = min(max(grid_stats[0], 0), M) and S = min(max(seg_stats[0], 0), M), both read ON THE DEVICE.  The MEMBERS of
+ *        segment s < S are the v < ne with segment[v] == s.  A word of segment outside [0, S) makes v a member of nothing.
+ *    G2. cell_box int32 (M, 6) = {min i_x, min i_y, min i_z, max i_x, max i_y, max i_z} over the members' voxel_cell.  In the
+ *        many-clouds result these are the room's own lattice coordinates, and the room is voxel_room[seg_root[s]].  Every
+ *        raw row of a member lies in its voxel's cell, so the cell box bounds the raw rows.
+ *    G3. box float32 (M, 6) = the minimum and the maximum of voxel_data[v][0..2] over the members, in the total order on
+ *        the BITS b of a float: key(b) = b ^ 0x80000000 for a clear sign bit, ~b otherwise, compared as unsigned.  So -0.0
+ *        is below +0.0, and a NaN or an infinity in a representative has a defined place (a NaN with a clear sign bit
+ *        above +inf, one with the sign bit set below -inf).  Integer minima and maxima of keys: independent of any order.
+ *    G4. moments int64 (M, 10) = {W, sum w dx, sum w dy, sum w dz, sum w dx^2, sum w dx dy, sum w dx dz, sum w dy^2,
+ *        sum w dy dz, sum w dz^2} over the members, with d = voxel_cell - (the low corner of cell_box), so 0 <= d_a < 2^20,
+ *        and w = 1 (weight 0) or w = voxel_count[v] (weight 1).  The sums are unsigned 64-bit, taken modulo 2^64, and
+ *        stored as their bits.  For everything this library produces they are exact: a subsampling has at most 2^24 rows
+ *        and as many voxels, so sum w <= 2^24, an axis has at most 2^20 cells, and (2^20 - 1)^2 * 2^24 < 2^64.
+ *    G5. centroid float64 (M, 3), in lattice coordinates: c_a = (double)lo_a + (double)m1_a / (double)W -- one division and
+ *        one addition, so bit-defined.  The centre of a cell in space is origin_a + (c_a + 0.5) * voxel.
+ *    G6. The covariance C_ab = (double)m2_ab / (double)W - ((double)m1_a / (double)W) * ((double)m1_b / (double)W), every
+ *        operation one float64 operation.  eigenvalues float64 (M, 3) are the eigenvalues of C in DESCENDING order, negative
+ *        round-off held to 0; axes float64 (M, 3, 3): row k is the unit eigenvector of eigenvalues[k].  These two are
+ *        defined TO A TOLERANCE, not to the bit: with u = 2^-53, t = 128 u and n = max(trace C, 1), C rebuilt from the
+ *        integer moments in exact arithmetic and rounded once:  (i) |A A^T - I| <= t,  (ii) |A^T diag(l) A - C| <= t n,
+ *        (iii) l descends and is >= 0,  (iv) |l_k - l_ref,k| <= t n against a float64 eigen-decomposition of C; all four
+ *        entrywise and without a condition on a gap, so lines, planes and cubes are covered.  The solver is the cyclic
+ *        Jacobi iteration of conv3p_grid_normals_f32, six sweeps, every rotation taken: two calls give the same bits.
+ *    G7. Sign, an exact rule on the stored vector: each axis is turned so that its component of largest magnitude is
+ *        positive, the lowest index of a tie.  The frame may be left-handed: no axis is turned to make a determinant +1.
+ *    G8. extent float64 (M, 6) = {min p_0, min p_1, min p_2, max p_0, max p_1, max p_2} over the members, with
+ *        p_k = (((double)i_x - c_x) * a_k0 + ((double)i_y - c_y) * a_k1) + ((double)i_z - c_z) * a_k2 computed from the STORED
+ *        centroid and axes, every operation one float64 operation, uncontracted, in that order; minimum and maximum by the
+ *        64-bit form of G3's key.  Given the stored frame this is bit-defined.  It is the oriented box of the cell
+ *        CENTRES; half a cell of padding is the caller's.
+ *   Filler: a row s >= S holds cell_box {0, 0, 0, -1, -1, -1} and 0 everywhere else; so does a row s < S whose W is 0, which
+ *   no segmentation of this library has.  geometry_stats int32 (4) = {S, segments of one voxel (cell_box low == high),
+ *   segments whose stored eigenvalues[2] is 0 (flat or thinner; filler rows are not counted), 0}, overwritten by every
+ *   call.  Every output word is written by every call.
+ *   Status, in this order, all before any launch: M < 0, K < 3, weight not 0 or 1: CONV3P_ERR_INVALID_ARGUMENT; M == 0:
+ *   CONV3P_OK, nothing launched and nothing written; any pointer NULL: CONV3P_ERR_INVALID_ARGUMENT; M > 2^31 - 1 or
+ *   K > 65536: CONV3P_ERR_UNSUPPORTED.  There is NO workspace: the sums, minima and maxima are accumulated in the output
+ *   words themselves, box and extent as ordered keys that the last launch turns back into floats.  Six launches whatever
+ *   the data (identities; the two boxes; the moments, which need the low corner; a thread per segment for G5-G7; the
+ *   extents; keys to floats, filler, stats); no host read; the only atomics are integer min / max on 32- and 64-bit words
+ *   and 64-bit integer adds, one set per run of equal segment among the consecutive voxels of a wave; no float atomics;
+ *   everything but G6 is bitwise independent of the launch geometry and of thread order, and G6 is a function of the exact
+ *   moments alone.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_GRID_MEAN 0
 #define CONV3P_GRID_CENTER 1
@@ -960,6 +1012,12 @@ int conv3p_grid_absorb_segments(const int32_t *neigh, const int32_t *voxel_label
                                 const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int min_size,
                                 int drop_orphans, int32_t *labels_out, int32_t *seg_label_out, int64_t *absorb_stats,
                                 void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_grid_segment_geometry(const float *voxel_data, int K, const int32_t *voxel_cell, const int32_t *voxel_count,
+                                 const int32_t *segment, const int32_t *seg_stats, const int32_t *grid_stats,
+                                 int64_t M, int weight,
+                                 int32_t *cell_box, float *box, int64_t *moments,
+                                 double *centroid, double *eigenvalues, double *axes, double *extent,
+                                 int32_t *geometry_stats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

@@ -35,6 +35,7 @@
 #include "conv3p_grid_interp_rings.hpp"
 #include "conv3p_grid_normals.hpp"
 #include "conv3p_grid_segments.hpp"
+#include "conv3p_grid_geometry.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>

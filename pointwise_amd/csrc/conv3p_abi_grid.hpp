@@ -1,5 +1,5 @@
 // conv3p_abi_grid.hpp -- host side of the voxel grid: subsample (single, rooms), project, neighbours, interpolate (plain,
-// rings), normals, segments, absorb.  Included by conv3p_abi.hip.
+// rings), normals, segments, absorb, segment geometry.  Included by conv3p_abi.hip.
 namespace {
 
 // The workspace of conv3p_grid_subsample_f32 (conv3p_grid.hpp): a host-side bound from the arguments.  The two pair
@@ -413,6 +413,43 @@ int conv3p_grid_absorb_segments(const int32_t *neigh, const int32_t *voxel_label
     hipLaunchKernelGGL(absorb_vote_kernel, dim3(gseg_grid(((size_t)M + kGsegThreads / 64 - 1) / (kGsegThreads / 64))),
                        dim3(kGsegThreads), 0, s, p);      // a wave per small segment, and there are at most M
     hipLaunchKernelGGL(absorb_labels_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    return hip_ok();
+}
+
+// Every status first, in the order include/conv3p.h gives; then six launches whatever the data, and no workspace: the
+// accumulators are the output words (conv3p_grid_geometry.hpp).
+int conv3p_grid_segment_geometry(const float *voxel_data, int K, const int32_t *voxel_cell, const int32_t *voxel_count,
+                                 const int32_t *segment, const int32_t *seg_stats, const int32_t *grid_stats, int64_t M,
+                                 int weight, int32_t *cell_box, float *box, int64_t *moments, double *centroid,
+                                 double *eigenvalues, double *axes, double *extent, int32_t *geometry_stats, void *stream)
+{
+    if (M < 0 || K < 3 || (weight != 0 && weight != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!voxel_data || !voxel_cell || !voxel_count || !segment || !seg_stats || !grid_stats || !cell_box || !box || !moments ||
+        !centroid || !eigenvalues || !axes || !extent || !geometry_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX || K > 65536) return CONV3P_ERR_UNSUPPORTED;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int m = (int)M;
+    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads);
+    // consecutive voxels a wave, as the segments' size adds take them
+    const int steps = M >= (1 << 20) ? 16 : (M >= (1 << 16) ? 4 : 1);
+    const size_t per_wave = (size_t)64 * steps * (kGsegThreads / 64);
+    const unsigned per_chunk = gseg_grid(((size_t)M + per_wave - 1) / per_wave);
+    int32_t *box_key = reinterpret_cast<int32_t *>(box);
+    long long *mom = reinterpret_cast<long long *>(moments), *extent_key = reinterpret_cast<long long *>(extent);
+    hipLaunchKernelGGL(geom_init_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, m, cell_box, box_key,
+                       reinterpret_cast<unsigned long long *>(moments), extent_key, geometry_stats);
+    hipLaunchKernelGGL(geom_box_kernel, dim3(per_chunk), dim3(kGsegThreads), 0, s, voxel_data, K, voxel_cell, segment, seg_stats,
+                       grid_stats, m, steps, cell_box, box_key);
+    hipLaunchKernelGGL(geom_moments_kernel, dim3(per_chunk), dim3(kGsegThreads), 0, s, voxel_cell, voxel_count, segment,
+                       seg_stats, grid_stats, m, weight, steps, cell_box, reinterpret_cast<unsigned long long *>(moments));
+    hipLaunchKernelGGL(geom_frame_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_stats, m, cell_box, mom, centroid,
+                       eigenvalues, axes, geometry_stats);
+    hipLaunchKernelGGL(geom_extent_kernel, dim3(per_chunk), dim3(kGsegThreads), 0, s, voxel_cell, segment, seg_stats, grid_stats,
+                       m, steps, centroid, axes, extent_key);
+    hipLaunchKernelGGL(geom_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_stats, m, cell_box, box_key, mom,
+                       extent_key, geometry_stats);
     return hip_ok();
 }
 

@@ -1,8 +1,9 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
 conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64,
-conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32, conv3p_grid_segments, conv3p_grid_absorb_segments;
-kernels in csrc/conv3p_grid.hpp, csrc/conv3p_grid_interp.hpp, csrc/conv3p_grid_interp_rings.hpp,
-csrc/conv3p_grid_normals.hpp and csrc/conv3p_grid_segments.hpp).
+conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32, conv3p_grid_segments, conv3p_grid_absorb_segments,
+conv3p_grid_segment_geometry; kernels in csrc/conv3p_grid.hpp, csrc/conv3p_grid_interp.hpp,
+csrc/conv3p_grid_interp_rings.hpp, csrc/conv3p_grid_normals.hpp, csrc/conv3p_grid_segments.hpp and
+csrc/conv3p_grid_geometry.hpp).
 
 A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
 first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
@@ -23,6 +24,9 @@ tests/grid_ref.py restates it in numpy.
     GridSubsample.segments      voxel labels -> GridSegments: the connected pieces of one class over the 27-cell table (a
                      lock-free union-find), their root, size, rows and label (tests/grid_segments_ref.py);
                      GridSegments.absorb / GridSubsample.clean_labels: pieces below a size take the label around them
+    GridSegments.geometry       -> SegmentGeometry: per segment the box of its cells and of its representatives, the exact
+                     integer moments of its cells, the centroid, the principal axes and the oriented extents
+                     (tests/grid_geometry_ref.py): a list of objects from a labelled scan
     grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
                      voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
@@ -502,6 +506,95 @@ class GridSegments:
                   self.absorb_stats.data_ptr(), self._absorb_workspace.data_ptr(), self._absorb_workspace.numel(),
                   torch.cuda.current_stream(dev).cuda_stream)
         return out
+
+    def geometry(self, weight="voxels", out=None):
+        """Where every segment is, how large and how oriented -> SegmentGeometry, a row per segment (include/conv3p.h:
+        conv3p_grid_segment_geometry, rules G1-G8; tests/grid_geometry_ref.py): cell_box, the box of the members' cells;
+        box, the box of their representatives (data[:, :3]); moments, the exact integer zeroth, first and second moments
+        of the cells about the cell box's low corner; centroid in lattice coordinates; eigenvalues (descending) and axes
+        (row k the unit eigenvector of eigenvalues[k], largest component positive) of the cells' covariance; extent, the
+        minima and maxima of the cell centres along those axes about the centroid -- the oriented box.
+
+        weight "voxels": every member voxel counts once; "rows": as its voxel_count raw rows, so moments[:, 0] is size or
+        rows.  Lattice to metres: the lattice is isotropic, one scale and one shift.  With lo the minimum corner of the
+        cloud the subsampling was given (in the many-clouds result: of the room voxel_room[root]) and voxel its step, cell
+        i spans [lo + i * voxel, lo + (i + 1) * voxel), a centroid c is the point lo + (c + 0.5) * voxel, an eigenvalue l
+        is l * voxel^2 square metres, the axes are directions as they stand, and an extent e is e * voxel metres about the
+        centroid (the box of the cell CENTRES: add half a cell on every side to cover the cells).
+
+        Works on the object segments() returned: on the many-clouds result (boxes in each room's own lattice) and on a
+        trimmed GridSubsample as they stand, and after absorb() it still describes the segmentation as segmented.
+        g.project(seg.segment) gives, for every raw row, the row of these tensors that describes it (-1: none).  out: a
+        SegmentGeometry of an earlier call with the same number of rows.  Rows past the last segment hold cell_box
+        {0, 0, 0, -1, -1, -1} and 0.  Six launches whatever the data, no workspace, nothing synchronised on."""
+        _require(isinstance(weight, str) and weight in _GEOMETRY_WEIGHTS, "weight must be \"voxels\" or \"rows\"")
+        _require(self._source is not None, "geometry works on the object segments() returned, not on its trim()")
+        grid = self._source[0]
+        dev = self.segment.device
+        M = self.shape[0]
+        _require(isinstance(grid.data, torch.Tensor) and grid.data.dtype == torch.float32 and grid.data.dim() == 2
+                 and grid.data.shape[0] == M and 3 <= grid.data.shape[1] <= 65536 and grid.data.is_contiguous()
+                 and grid.data.device == dev,
+                 "the subsampling's data must be a contiguous float32 (M, 3 <= K <= 65536) tensor on the segments' device")
+        for name, t, shape in (("voxel_cell", grid.voxel_cell, (M, 3)), ("voxel_count", grid.voxel_count, (M,)),
+                               ("stats", grid.stats, (8,)), ("segment", self.segment, (M,)), ("stats", self.stats, (8,))):
+            _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()
+                     and tuple(t.shape) == shape,
+                     "%s must be a contiguous int32 tensor of the subsampling's shape on its device" % name)
+        if out is not None:
+            _require(isinstance(out, SegmentGeometry) and out.shape == (M,) and out.cell_box.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        if out is None:
+            out = SegmentGeometry(M, dev)
+        if M == 0:
+            out.stats.zero_()
+            return out
+        with torch.cuda.device(dev):
+            _call(_lib.load().conv3p_grid_segment_geometry, grid.data.data_ptr(), grid.data.shape[1],
+                  grid.voxel_cell.data_ptr(), grid.voxel_count.data_ptr(), self.segment.data_ptr(), self.stats.data_ptr(),
+                  grid.stats.data_ptr(), M, _GEOMETRY_WEIGHTS[weight], out.cell_box.data_ptr(), out.box.data_ptr(),
+                  out.moments.data_ptr(), out.centroid.data_ptr(), out.eigenvalues.data_ptr(), out.axes.data_ptr(),
+                  out.extent.data_ptr(), out.stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+
+_GEOMETRY_WEIGHTS = {"voxels": 0, "rows": 1}
+
+
+class SegmentGeometry:
+    """The outputs of GridSegments.geometry, a row per segment: cell_box int32 (M, 6) = {low i_x, i_y, i_z, high i_x, i_y,
+    i_z} of the members' cells; box float32 (M, 6), the same of their representatives' xyz; moments int64 (M, 10) = {W, m1
+    x y z, m2 xx xy xz yy yz zz} of the cells about cell_box's low corner; centroid float64 (M, 3) in lattice
+    coordinates; eigenvalues float64 (M, 3), descending; axes float64 (M, 3, 3), row k the unit eigenvector of
+    eigenvalues[k]; extent float64 (M, 6) = {low p_0, p_1, p_2, high p_0, p_1, p_2}, the cell centres along the axes about
+    the centroid; stats int32 (4) on the device = {segments, segments of one voxel, segments whose smallest eigenvalue
+    is 0 (flat or thinner), 0}.  Rows past the last segment hold cell_box {0, 0, 0, -1, -1, -1} and 0."""
+
+    def __init__(self, num_voxels, device):
+        M = int(num_voxels)
+        self.shape = (M,)
+        self.cell_box = torch.empty((M, 6), dtype=torch.int32, device=device)
+        self.box = torch.empty((M, 6), dtype=torch.float32, device=device)
+        self.moments = torch.empty((M, 10), dtype=torch.int64, device=device)
+        self.centroid = torch.empty((M, 3), dtype=torch.float64, device=device)
+        self.eigenvalues = torch.empty((M, 3), dtype=torch.float64, device=device)
+        self.axes = torch.empty((M, 3, 3), dtype=torch.float64, device=device)
+        self.extent = torch.empty((M, 6), dtype=torch.float64, device=device)
+        self.stats = torch.zeros((4,), dtype=torch.int32, device=device)
+
+    def num_segments(self):
+        """The number of segments: the one host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def trim(self):
+        """Views of the first num_segments() rows, as a SegmentGeometry (stats shared)."""
+        S = self.num_segments()
+        t = object.__new__(SegmentGeometry)
+        t.shape = (S,)
+        t.cell_box, t.box, t.moments, t.centroid = self.cell_box[:S], self.box[:S], self.moments[:S], self.centroid[:S]
+        t.eigenvalues, t.axes, t.extent, t.stats = self.eigenvalues[:S], self.axes[:S], self.extent[:S], self.stats
+        return t
 
 
 class GridNormals:
