@@ -19,30 +19,12 @@ import ctypes
 import torch
 
 from . import _lib
+from ._host import (_SFX, Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _require,   # noqa: F401
+                    _workspace)                                                                        # (re-exported)
 
-
-class Conv3pInvalidArgument(ValueError):
-    """Analogue of tf.errors.InvalidArgumentError raised by the op's OP_REQUIRES checks."""
-
-
-class Conv3pRuntimeError(RuntimeError):
-    pass
-
-
-_SFX = {torch.float32: ("f32", ctypes.c_float, 4), torch.float64: ("f64", ctypes.c_double, 8)}
-
-# one growing scratch buffer per (device, stream): the caller-owned workspace of the C ABI
+# one growing scratch buffer per (device, stream): the caller-owned workspace of the C ABI.  The stateless calls leave
+# validity marks in it, so it is this module's own pool
 _WORKSPACES = {}
-
-
-def _workspace(device, nbytes):
-    stream = torch.cuda.current_stream(device)
-    key = (device.index, stream.cuda_stream)
-    buf = _WORKSPACES.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _WORKSPACES[key] = buf
-    return buf, stream
 
 
 _MATMUL_BITS = {"highest": 0, "medium": _lib.CACHE_MATMUL_BF16}
@@ -148,11 +130,6 @@ class NeighborCache:
             pass
 
 
-def _require(cond, msg):
-    if not cond:
-        raise Conv3pInvalidArgument(msg)
-
-
 def _stride_list(stride):
     if isinstance(stride, torch.Tensor):
         _require(stride.dim() >= 1 and stride.shape[0] == 3, "Conv3p expects stride tensor to have size 3.")
@@ -172,16 +149,6 @@ def _voxel_value(voxel_size):
     return float(voxel_size)
 
 
-def _check_device(*tensors):
-    dev = tensors[0].device
-    if dev.type != "cuda":
-        raise Conv3pRuntimeError("conv3p: tensors must live on a HIP device (no CPU path in pointwise_amd)")
-    for t in tensors:
-        if t.device != dev:
-            raise Conv3pRuntimeError("conv3p: all tensors must be on the same device")
-    return dev
-
-
 def _common_checks(points, input, filter):
     _require(points.dim() == 3, "Conv3p expects (batch_size, num_points, 3) points shape")
     _require(points.shape[2] == 3, "Conv3p expects (batch_size, num_points, 3) points shape")
@@ -195,16 +162,6 @@ def _common_checks(points, input, filter):
     if dt not in _SFX:
         raise Conv3pInvalidArgument("Conv3p: T must be float32 or float64")   # Attr T: {float, double}
     _require(input.dtype == dt and filter.dtype == dt, "Conv3p: points, input and filter must share dtype T")
-
-
-def _call(fn, *args):
-    rc = fn(*args)
-    if rc == _lib.OK:
-        return
-    msg = "conv3p: %s (status %d)" % (_lib.status_string(rc), rc)
-    if rc == _lib.ERR_INVALID_ARGUMENT:
-        raise Conv3pInvalidArgument(msg)
-    raise Conv3pRuntimeError(msg)
 
 
 def conv3p(points, input, filter, stride, voxel_size, cache=None, points_unchanged=False, _fused_selu=False):
@@ -234,10 +191,10 @@ def conv3p(points, input, filter, stride, voxel_size, cache=None, points_unchang
             if _fused_selu:
                 raise Conv3pInvalidArgument("conv3p_layer needs a NeighborCache that fits these clouds")
             need = lib.conv3p_workspace_bytes(_lib.PASS_FORWARD, esz, B, N, Cin, Cout, fz, fy, fx)
-            ws, stream = _workspace(dev, need)
+            ws = _workspace(dev, need, _WORKSPACES)
             _call(getattr(lib, "conv3p_forward_" + sfx), points.data_ptr(), input.data_ptr(), filter.data_ptr(),
                   ctypes.cast(s3, ctypes.c_void_p), creal(vox), B, N, Cin, Cout, fz, fy, fx, out.data_ptr(),
-                  ws.data_ptr(), ws.numel(), stream.cuda_stream)
+                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
     return out
 
 
@@ -294,10 +251,11 @@ def conv3p_grad(grad_from_next, points, input, filter, stride, voxel_size, grad_
             if _fused_selu:
                 raise Conv3pInvalidArgument("conv3p_layer_grad needs a NeighborCache that fits these clouds")
             need = lib.conv3p_workspace_bytes(_lib.PASS_BACKWARD, esz, B, N, Cin, Cout, fz, fy, fx)
-            ws, stream = _workspace(dev, need)
+            ws = _workspace(dev, need, _WORKSPACES)
             _call(getattr(lib, "conv3p_backward_" + sfx), grad_from_next.data_ptr(), points.data_ptr(),
                   input.data_ptr(), filter.data_ptr(), ctypes.cast(s3, ctypes.c_void_p), creal(vox), B, N, Cin,
-                  Cout, fz, fy, fx, dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), stream.cuda_stream)
+                  Cout, fz, fy, fx, dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                  torch.cuda.current_stream(dev).cuda_stream)
     return dx, dw
 
 
@@ -384,9 +342,10 @@ def neighbor_count(points, filter_zyx, stride, voxel_size):
     cnt = torch.zeros((B, N, fz * fy * fx), dtype=torch.int32, device=dev)
     need = lib.conv3p_workspace_bytes(_lib.PASS_NEIGHBOR_COUNT, esz, B, N, 0, 0, fz, fy, fx)
     with torch.cuda.device(dev):
-        ws, stream = _workspace(dev, need)
+        ws = _workspace(dev, need, _WORKSPACES)
         _call(getattr(lib, "conv3p_neighbor_count_" + sfx), points.data_ptr(), ctypes.cast(s3, ctypes.c_void_p),
-              creal(vox), B, N, fz, fy, fx, cnt.data_ptr(), ws.data_ptr(), ws.numel(), stream.cuda_stream)
+              creal(vox), B, N, fz, fy, fx, cnt.data_ptr(), ws.data_ptr(), ws.numel(),
+              torch.cuda.current_stream(dev).cuda_stream)
     return cnt
 
 

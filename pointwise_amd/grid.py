@@ -65,10 +65,21 @@ import numpy as np
 import torch
 
 from . import _lib
-from .conv3p_op import _call, _require
-from .scene import _LABEL_DTYPES
+from ._host import (_LABEL_DTYPES, _call, _fill_empty, _grow, _is_int, _is_tensor, _ptr, _require, _require_int,
+                    _require_tensor, _stream, _view)
 
+_VIEWPOINT = "viewpoint must be None, three finite numbers, or a float32 (1, 3) or (R, 3) tensor on the cloud's device"
 _MODES = {"mean": _lib.GRID_MEAN, "center": _lib.GRID_CENTER}
+_NO_CPU = "the cloud must live on a HIP device (there is no CPU path)"
+_TABLE_MESSAGE = "%s must be a contiguous int32 tensor of the subsampling's shape on its device"
+
+
+def _require_table(dev, entries, vector=True):
+    """The int32 tensors a call reads beside its arguments, (name, tensor, shape) each, are contiguous, on `dev` and of
+    that shape; shape None: a vector of at least one entry, or with vector=False of any shape."""
+    for name, t, shape in entries:
+        _require(_is_tensor(t, torch.int32, shape, dev) and (shape is not None or not vector or (t.dim() == 1 and t.numel() >= 1)),
+                 _TABLE_MESSAGE % name)
 
 
 class GridSubsample:
@@ -77,6 +88,10 @@ class GridSubsample:
     voxel_row (mean: the lowest member row; center: the representative), voxel_count, voxel_cell (max_voxels, 3), stats
     int32 (8) = {emitted voxels, occupied voxels, n_x, n_y, n_z, non-finite rows, largest member count, error}.  Voxels
     past the emitted ones hold data 0, labels -1, voxel_row -1, voxel_count 0, voxel_cell -1."""
+
+    _ROWS = ("data", "labels", "voxel_row", "voxel_count", "voxel_cell")         # per voxel: what a view cuts; it shares the rest
+    _SLICED, _SHARED = _ROWS + ("_neigh",), ("inverse", "stats")
+    _FILL = (("data", 0), ("labels", -1), ("inverse", -1), ("voxel_row", -1), ("voxel_count", 0), ("voxel_cell", -1), ("stats", 0))
 
     def __init__(self, num_rows, max_voxels, K, with_labels, device, workspace_bytes=0):
         N, M = int(num_rows), int(max_voxels)
@@ -97,35 +112,34 @@ class GridSubsample:
     def trim(self):
         """Views of the first num_voxels() voxels, as a GridSubsample (inverse and stats shared)."""
         nv = self.num_voxels()
-        t = object.__new__(GridSubsample)
-        t.shape = (self.shape[0], nv) + self.shape[2:]
-        t.data = self.data[:nv]
-        t.labels = self.labels[:nv] if self.labels is not None else None
-        t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[:nv], self.voxel_count[:nv], self.voxel_cell[:nv]
-        t.inverse, t.stats, t.workspace = self.inverse, self.stats, None
-        if getattr(self, "_neigh", None) is not None:
-            t._neigh = self._neigh[:nv]
-        return t
+        return _view(self, GridSubsample, slice(nv), self._SLICED, self._SHARED, shape=(self.shape[0], nv) + self.shape[2:],
+                     workspace=None)
 
     def project(self, voxel_labels, out=None):
         """voxel_labels int32 (M), a label per voxel (the model's, SceneVotes.labels(), ...) -> (N) int32, the label of
         every raw row's voxel; -1 for a row whose inverse is -1 or not below M.  One launch, nothing synchronised on."""
         dev = self.inverse.device
-        _require(isinstance(voxel_labels, torch.Tensor) and voxel_labels.dtype == torch.int32 and voxel_labels.dim() == 1
-                 and voxel_labels.device == dev and voxel_labels.is_contiguous(),
-                 "voxel_labels must be a contiguous int32 (M,) tensor on the cloud's device")
+        _require_tensor(voxel_labels, "voxel_labels must be a contiguous int32 (M,) tensor on the cloud's device", torch.int32,
+                        dev=dev, ndim=1)
         N, M = self.inverse.numel(), voxel_labels.numel()
         if out is None:
             out = torch.empty((N,), dtype=torch.int32, device=dev)
-        _require(isinstance(out, torch.Tensor) and out.dtype == torch.int32 and tuple(out.shape) == (N,) and out.device == dev
-                 and out.is_contiguous(), "out must be a contiguous int32 (N,) tensor on the cloud's device")
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        _require_tensor(out, "out must be a contiguous int32 (N,) tensor on the cloud's device", torch.int32, (N,), dev)
+        _require(dev.type == "cuda", _NO_CPU)
         if N == 0:
             return out
         with torch.cuda.device(dev):
-            _call(_lib.load().conv3p_grid_project_labels, voxel_labels.data_ptr() if M else None, self.inverse.data_ptr(), N,
-                  M, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            _call(_lib.load().conv3p_grid_project_labels, _ptr(voxel_labels), self.inverse.data_ptr(), N, M, out.data_ptr(),
+                  _stream(dev))
         return out
+
+    def _table(self, dev, M, vector):
+        """The check of the tensors the neighbour table is built from and the ring search reads (_require_table) -> the
+        many-clouds result's (voxel_room, voxel_start), (None, None) from one cloud."""
+        room, start = getattr(self, "voxel_room", None), getattr(self, "voxel_start", None)
+        _require_table(dev, (("voxel_cell", self.voxel_cell, (M, 3)), ("stats", self.stats, (8,))) + (
+            (("voxel_room", room, (M,)), ("voxel_start", start, None)) if room is not None else ()), vector)
+        return room, start
 
     def neighbors(self):
         """int32 (max_voxels, 27): neigh[v][(dx+1)*9 + (dy+1)*3 + (dz+1)] is the emitted voxel of the cell (i+dx, j+dy,
@@ -136,20 +150,13 @@ class GridSubsample:
             return neigh
         dev = self.voxel_cell.device
         M = self.voxel_cell.shape[0]
-        room, start = getattr(self, "voxel_room", None), getattr(self, "voxel_start", None)
-        for name, t, shape in (("voxel_cell", self.voxel_cell, (M, 3)), ("stats", self.stats, (8,))) + (
-                (("voxel_room", room, (M,)), ("voxel_start", start, None)) if room is not None else ()):
-            _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()
-                     and (shape is None or tuple(t.shape) == shape),
-                     "%s must be a contiguous int32 tensor of the subsampling's shape on its device" % name)
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        room, start = self._table(dev, M, vector=False)
+        _require(dev.type == "cuda", _NO_CPU)
         neigh = torch.empty((M, 27), dtype=torch.int32, device=dev)
         if M:
             with torch.cuda.device(dev):
-                _call(_lib.load().conv3p_grid_neighbors, self.voxel_cell.data_ptr(),
-                      room.data_ptr() if room is not None else None, start.data_ptr() if room is not None else None,
-                      self.stats.data_ptr(), M, start.numel() - 1 if room is not None else 0, neigh.data_ptr(),
-                      torch.cuda.current_stream(dev).cuda_stream)
+                _call(_lib.load().conv3p_grid_neighbors, self.voxel_cell.data_ptr(), _ptr(room), _ptr(start, room is not None),
+                      self.stats.data_ptr(), M, start.numel() - 1 if room is not None else 0, neigh.data_ptr(), _stream(dev))
         self._neigh = neigh
         return neigh
 
@@ -180,27 +187,25 @@ class GridSubsample:
         from .scene import SceneScores
         dev = self.inverse.device
         N = self.inverse.numel()
-        _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
+        _require(_is_tensor(data, torch.float32, ndim=2, contiguous=False) and data.shape[1] >= 3,
                  "data must be a float32 (N, K >= 3) tensor, xyz first")
         _require(data.is_contiguous() and data.device == dev, "data must be contiguous and on the cloud's device")
         _require(data.shape[0] == N, "data must have the rows the subsampling was given (inverse has %d)" % N)
-        _require(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= 8, "k must be an integer in [1, 8]")
+        _require_int(k, "k must be an integer in [1, 8]", 1, 8)
         if isinstance(voxel_scores, SceneScores):
             _require(voxel_scores.device == dev, "voxel_scores must live on the cloud's device")
-            scores, entry = voxel_scores.scores, "conv3p_grid_interpolate_i64"
+            scores, entry = voxel_scores.scores, "conv3p_grid_interpolate%s_i64"
         else:
-            _require(isinstance(voxel_scores, torch.Tensor) and voxel_scores.dtype == torch.float32 and voxel_scores.dim() == 2
-                     and voxel_scores.is_contiguous() and voxel_scores.device == dev,
-                     "voxel_scores must be a contiguous float32 (M, C) tensor on the cloud's device, or a SceneScores")
-            scores, entry = voxel_scores, "conv3p_grid_interpolate_f32"
+            _require_tensor(voxel_scores, "voxel_scores must be a contiguous float32 (M, C) tensor on the cloud's device, or a "
+                            "SceneScores", torch.float32, dev=dev, ndim=2)
+            scores, entry = voxel_scores, "conv3p_grid_interpolate%s_f32"
         M, C = scores.shape
         _require(1 <= C <= 128, "at most 128 classes (and at least one)")
         _require(M <= self.data.shape[0], "voxel_scores has more rows than the subsampling has voxels")
         if valid_labels is not None:
-            _require(isinstance(valid_labels, torch.Tensor) and valid_labels.dtype == torch.int32 and valid_labels.device == dev
-                     and tuple(valid_labels.shape) == (M,) and valid_labels.is_contiguous(),
-                     "valid_labels must be a contiguous int32 (M,) tensor on the cloud's device")
-        _require(isinstance(rings, int) and not isinstance(rings, bool) and 1 <= rings <= 8, "rings must be an integer in [1, 8]")
+            _require_tensor(valid_labels, "valid_labels must be a contiguous int32 (M,) tensor on the cloud's device",
+                            torch.int32, (M,), dev)
+        _require_int(rings, "rings must be an integer in [1, 8]", 1, 8)
         _require(isinstance(return_ring, bool), "return_ring must be a bool")
         parts = 1 + bool(return_scores) + return_ring
         _require(out is None or parts == 1 or (isinstance(out, (tuple, list)) and len(out) == parts),
@@ -211,25 +216,15 @@ class GridSubsample:
             lab = out if parts == 1 else out[0]
             sc = out[1] if return_scores else None
             rg = out[parts - 1] if return_ring else None
-            _require(isinstance(lab, torch.Tensor) and lab.dtype == torch.int32 and tuple(lab.shape) == (N,)
-                     and lab.device == dev and lab.is_contiguous(),
-                     "out labels must be a contiguous int32 (N,) tensor on the cloud's device")
-            _require(not return_scores or (isinstance(sc, torch.Tensor) and sc.dtype == torch.float32
-                                           and tuple(sc.shape) == (N, C) and sc.device == dev and sc.is_contiguous()),
+            _require_tensor(lab, "out labels must be a contiguous int32 (N,) tensor on the cloud's device", torch.int32, (N,), dev)
+            _require(not return_scores or _is_tensor(sc, torch.float32, (N, C), dev),
                      "out scores must be a contiguous float32 (N, C) tensor on the cloud's device")
-            _require(not return_ring or (isinstance(rg, torch.Tensor) and rg.dtype == torch.int32 and tuple(rg.shape) == (N,)
-                                         and rg.device == dev and rg.is_contiguous()),
+            _require(not return_ring or _is_tensor(rg, torch.int32, (N,), dev),
                      "out ring must be a contiguous int32 (N,) tensor on the cloud's device")
         ringed = rings > 1 or return_ring
         if ringed:
-            room, start = getattr(self, "voxel_room", None), getattr(self, "voxel_start", None)
-            Mv = self.data.shape[0]
-            for name, t, shape in (("voxel_cell", self.voxel_cell, (Mv, 3)), ("stats", self.stats, (8,))) + (
-                    (("voxel_room", room, (Mv,)), ("voxel_start", start, None)) if room is not None else ()):
-                _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()
-                         and (tuple(t.shape) == shape if shape is not None else t.dim() == 1 and t.numel() >= 1),
-                         "%s must be a contiguous int32 tensor of the subsampling's shape on its device" % name)
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+            room, start = self._table(dev, self.data.shape[0], vector=True)
+        _require(dev.type == "cuda", _NO_CPU)
         if valid_labels is None and isinstance(voxel_scores, SceneScores):
             valid_labels = voxel_scores.labels()
         if lab is None:
@@ -240,33 +235,22 @@ class GridSubsample:
             self.interp_stats = torch.zeros((3,), dtype=torch.int64, device=dev)
         neigh = self.neighbors()
         lib = _lib.load()
+        cloud = (_ptr(data), N, data.shape[1], _ptr(self.inverse), _ptr(self.data, M), self.data.shape[1], _ptr(neigh, M))
+        votes = (_ptr(scores), M, C, _ptr(valid_labels, M), k)
         if not ringed:
             with torch.cuda.device(dev):
-                _call(getattr(lib, entry), data.data_ptr() if N else None, N, data.shape[1],
-                      self.inverse.data_ptr() if N else None, self.data.data_ptr() if M else None, self.data.shape[1],
-                      neigh.data_ptr() if M else None, scores.data_ptr() if M else None, M, C,
-                      valid_labels.data_ptr() if valid_labels is not None and M else None, k, lab.data_ptr() if N else None,
-                      sc.data_ptr() if sc is not None and N else None, self.interp_stats.data_ptr(),
-                      torch.cuda.current_stream(dev).cuda_stream)
+                _call(getattr(lib, entry % ""), *cloud, *votes, _ptr(lab), _ptr(sc), self.interp_stats.data_ptr(), _stream(dev))
             return (lab, sc) if return_scores else lab
         rooms = room is not None and M > 0               # without voxels no row has one: the rooms are not read
         if return_ring and rg is None:
             rg = torch.empty((N,), dtype=torch.int32, device=dev)
         if getattr(self, "ring_stats", None) is None:
             self.ring_stats = torch.zeros((9,), dtype=torch.int64, device=dev)
-        need = int(lib.conv3p_grid_interpolate_rings_workspace_bytes(N))
-        if getattr(self, "_ring_workspace", None) is None or self._ring_workspace.numel() < need:
-            self._ring_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _grow(self, "_ring_workspace", int(lib.conv3p_grid_interpolate_rings_workspace_bytes(N)), dev)
         with torch.cuda.device(dev):
-            _call(getattr(lib, entry.replace("interpolate", "interpolate_rings")), data.data_ptr() if N else None, N,
-                  data.shape[1], self.inverse.data_ptr() if N else None, self.data.data_ptr() if M else None,
-                  self.data.shape[1], neigh.data_ptr() if M else None, self.voxel_cell.data_ptr() if M else None,
-                  room.data_ptr() if rooms else None, start.data_ptr() if rooms else None,
-                  start.numel() - 1 if rooms else 0, self.stats.data_ptr(), scores.data_ptr() if M else None, M, C,
-                  valid_labels.data_ptr() if valid_labels is not None and M else None, k, rings,
-                  lab.data_ptr() if N else None, sc.data_ptr() if sc is not None and N else None,
-                  rg.data_ptr() if rg is not None and N else None, self.interp_stats.data_ptr(), self.ring_stats.data_ptr(),
-                  self._ring_workspace.data_ptr(), self._ring_workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
+            _call(getattr(lib, entry % "_rings"), *cloud, _ptr(self.voxel_cell, M), _ptr(room, rooms), _ptr(start, rooms),
+                  start.numel() - 1 if rooms else 0, self.stats.data_ptr(), *votes, rings, _ptr(lab), _ptr(sc), _ptr(rg),
+                  self.interp_stats.data_ptr(), self.ring_stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
         return tuple(t for t in (lab, sc, rg) if t is not None) if parts > 1 else lab
 
     def normals(self, viewpoint=None, min_neighbors=6, return_moments=False, out=None):
@@ -286,8 +270,7 @@ class GridSubsample:
         dev = self.data.device
         M, K = self.data.shape
         rooms = getattr(self, "voxel_room", None)
-        _require(isinstance(min_neighbors, int) and not isinstance(min_neighbors, bool) and 3 <= min_neighbors <= 27,
-                 "min_neighbors must be an integer in [3, 27]")
+        _require_int(min_neighbors, "min_neighbors must be an integer in [3, 27]", 3, 27)
         _require(isinstance(return_moments, bool), "return_moments must be a bool")
         upload = None
         if viewpoint is not None and not isinstance(viewpoint, torch.Tensor):
@@ -296,26 +279,21 @@ class GridSubsample:
             except (TypeError, ValueError):
                 upload = None
             _require(upload is not None and len(upload) == 3 and all(math.isfinite(x) for x in upload)
-                     and all(abs(x) <= float(np.finfo(np.float32).max) for x in upload),
-                     "viewpoint must be None, three finite numbers, or a float32 (1, 3) or (R, 3) tensor on the cloud's device")
+                     and all(abs(x) <= float(np.finfo(np.float32).max) for x in upload), _VIEWPOINT)
         elif viewpoint is not None:
-            _require(viewpoint.dtype == torch.float32 and viewpoint.dim() == 2 and viewpoint.shape[1] == 3
-                     and viewpoint.shape[0] >= 1 and viewpoint.is_contiguous() and viewpoint.device == dev,
-                     "viewpoint must be None, three finite numbers, or a float32 (1, 3) or (R, 3) tensor on the cloud's device")
+            _require(_is_tensor(viewpoint, torch.float32, dev=dev, ndim=2) and viewpoint.shape[1] == 3 and viewpoint.shape[0] >= 1,
+                     _VIEWPOINT)
             if viewpoint.shape[0] != 1:
                 _require(rooms is not None, "a viewpoint per room needs a GridRoomSubsample")
                 _require(viewpoint.shape[0] == self.voxel_start.numel() - 1,
                          "viewpoint must have one row, or one per room (%d)" % (self.voxel_start.numel() - 1))
-        _require(isinstance(self.data, torch.Tensor) and self.data.dtype == torch.float32 and self.data.is_contiguous()
-                 and K >= 3, "data must be a contiguous float32 (M, K >= 3) tensor")
+        _require(_is_tensor(self.data, torch.float32) and K >= 3, "data must be a contiguous float32 (M, K >= 3) tensor")
         if rooms is not None:
-            _require(isinstance(rooms, torch.Tensor) and rooms.dtype == torch.int32 and tuple(rooms.shape) == (M,)
-                     and rooms.device == dev and rooms.is_contiguous(),
-                     "voxel_room must be a contiguous int32 (M,) tensor on the cloud's device")
+            _require_tensor(rooms, "voxel_room must be a contiguous int32 (M,) tensor on the cloud's device", torch.int32, (M,), dev)
         if out is not None:
             _require(isinstance(out, GridNormals) and out.shape == (M, return_moments) and out.normals.device == dev,
                      "out was made for another shape")
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        _require(dev.type == "cuda", _NO_CPU)
         if out is None:
             out = GridNormals(M, return_moments, dev)
         if M == 0:
@@ -326,11 +304,9 @@ class GridSubsample:
         neigh = self.neighbors()
         with torch.cuda.device(dev):
             _call(_lib.load().conv3p_grid_normals_f32, self.data.data_ptr(), K, neigh.data_ptr(), self.stats.data_ptr(),
-                  rooms.data_ptr() if rooms is not None else None, viewpoint.data_ptr() if viewpoint is not None else None,
-                  viewpoint.shape[0] if viewpoint is not None else 0, M, min_neighbors, out.normals.data_ptr(),
-                  out.curvature.data_ptr(), out.samples.data_ptr(), out.flags.data_ptr(),
-                  out.moments.data_ptr() if return_moments else None, out.stats.data_ptr(),
-                  torch.cuda.current_stream(dev).cuda_stream)
+                  _ptr(rooms), _ptr(viewpoint), viewpoint.shape[0] if viewpoint is not None else 0, M, min_neighbors,
+                  out.normals.data_ptr(), out.curvature.data_ptr(), out.samples.data_ptr(), out.flags.data_ptr(),
+                  _ptr(out.moments), out.stats.data_ptr(), _stream(dev))
         return out
 
     def with_normals(self, nrm, curvature=False):
@@ -363,13 +339,12 @@ class GridSubsample:
         dev = self.voxel_count.device
         M = self.voxel_count.shape[0]
         L = _check_segment_arguments(voxel_labels, num_class, connectivity, M, dev)
-        _require(isinstance(self.voxel_count, torch.Tensor) and self.voxel_count.dtype == torch.int32
-                 and self.voxel_count.is_contiguous() and tuple(self.voxel_cell.shape) == (M, 3),
+        _require(_is_tensor(self.voxel_count, torch.int32) and tuple(self.voxel_cell.shape) == (M, 3),
                  "voxel_count must be a contiguous int32 (M,) tensor beside voxel_cell (M, 3)")
         if out is not None:
             _require(isinstance(out, GridSegments) and out.shape == (M,) and out.segment.device == dev,
                      "out was made for another shape")
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        _require(dev.type == "cuda", _NO_CPU)
         if out is None:
             out = GridSegments(M, dev)
         out._source = (self, voxel_labels, L, 1 if voxel_labels is None else num_class, connectivity)
@@ -377,24 +352,20 @@ class GridSubsample:
             out.stats.zero_()
             return out
         lib = _lib.load()
-        need = int(lib.conv3p_grid_segments_workspace_bytes(M))
-        if out.workspace is None or out.workspace.numel() < need:
-            out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _grow(out, "workspace", int(lib.conv3p_grid_segments_workspace_bytes(M)), dev)
         neigh = self.neighbors()
         with torch.cuda.device(dev):
             _call(lib.conv3p_grid_segments, neigh.data_ptr(), _labels_pointer(voxel_labels, L, out.segment), L,
-                  self.voxel_count.data_ptr(),
-                  self.stats.data_ptr(), M, out._source[3], connectivity, out.segment.data_ptr(), out.root.data_ptr(),
-                  out.size.data_ptr(), out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr(),
-                  out.workspace.data_ptr(), out.workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
+                  self.voxel_count.data_ptr(), self.stats.data_ptr(), M, out._source[3], connectivity, out.segment.data_ptr(),
+                  out.root.data_ptr(), out.size.data_ptr(), out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _stream(dev))
         return out
 
     def clean_labels(self, voxel_labels, num_class, min_size, connectivity=26, drop_orphans=False):
         """voxel_labels with every segment of fewer than min_size voxels given the label that surrounds it -> int32 (M):
         segments(voxel_labels, num_class, connectivity).absorb(min_size, drop_orphans).  One pass; run it again on the
         result to absorb what the first pass left (GridSegments.absorb)."""
-        _require(isinstance(min_size, int) and not isinstance(min_size, bool) and 1 <= min_size < 2 ** 31,
-                 "min_size must be a positive integer")
+        _require_int(min_size, "min_size must be a positive integer", 1, 2 ** 31 - 1)
         _require(isinstance(drop_orphans, bool), "drop_orphans must be a bool")
         return self.segments(voxel_labels, num_class, connectivity).absorb(min_size, drop_orphans)
 
@@ -403,19 +374,16 @@ def _check_segment_arguments(voxel_labels, num_class, connectivity, M, dev):
     """The argument checks of GridSubsample.segments -> L, the number of label words (0 without labels)."""
     L = 0
     if voxel_labels is not None:
-        _require(isinstance(voxel_labels, torch.Tensor) and voxel_labels.dtype == torch.int32 and voxel_labels.dim() == 1
-                 and voxel_labels.device == dev and voxel_labels.is_contiguous(),
-                 "voxel_labels must be a contiguous int32 (L,) tensor on the cloud's device, or None")
+        _require_tensor(voxel_labels, "voxel_labels must be a contiguous int32 (L,) tensor on the cloud's device, or None",
+                        torch.int32, dev=dev, ndim=1)
         L = voxel_labels.numel()
         _require(L <= M, "voxel_labels has more rows than the subsampling has voxels (%d)" % M)
-        _require(isinstance(num_class, int) and not isinstance(num_class, bool) and 1 <= num_class <= _lib.GRID_MAX_CLASS,
-                 "num_class must be an integer in [1, %d] with voxel_labels" % _lib.GRID_MAX_CLASS)
+        _require_int(num_class, "num_class must be an integer in [1, %d] with voxel_labels" % _lib.GRID_MAX_CLASS, 1,
+                     _lib.GRID_MAX_CLASS)
     else:
-        _require(num_class is None or (isinstance(num_class, int) and not isinstance(num_class, bool)
-                                       and 1 <= num_class <= _lib.GRID_MAX_CLASS),
+        _require(num_class is None or _is_int(num_class, 1, _lib.GRID_MAX_CLASS),
                  "num_class must be None or an integer in [1, %d]" % _lib.GRID_MAX_CLASS)
-    _require(isinstance(connectivity, int) and not isinstance(connectivity, bool) and connectivity in (6, 18, 26),
-             "connectivity must be 6, 18 or 26")
+    _require(_is_int(connectivity, 6, 26) and connectivity in (6, 18, 26), "connectivity must be 6, 18 or 26")
     return L
 
 
@@ -456,14 +424,8 @@ class GridSegments:
     def trim(self):
         """Views of the first num_segments() segment rows, as a GridSegments (segment and stats shared)."""
         S = self.num_segments()
-        t = object.__new__(GridSegments)
-        t.shape = self.shape
-        t.segment, t.stats = self.segment, self.stats
-        t.root, t.size, t.rows, t.label = self.root[:S], self.size[:S], self.rows[:S], self.label[:S]
-        t.absorbed_label = self.absorbed_label[:S] if self.absorbed_label is not None else None
-        t.absorb_stats = self.absorb_stats
-        t.workspace = t._absorb_workspace = t._source = None
-        return t
+        return _view(self, GridSegments, slice(S), ("root", "size", "rows", "label", "absorbed_label"),
+                     ("segment", "stats", "absorb_stats"), shape=self.shape, workspace=None, _absorb_workspace=None, _source=None)
 
     def absorb(self, min_size, drop_orphans=False, out=None):
         """One clean-up pass -> labels int32 (M): every segment of fewer than min_size voxels takes the label most of the
@@ -474,17 +436,15 @@ class GridSegments:
         iterated: a small segment among small segments is an orphan; segment the result and absorb again for more.  Sets
         absorbed_label and absorb_stats.  out: a contiguous int32 (M,) tensor.  Six launches whatever the data, nothing
         synchronised on."""
-        _require(isinstance(min_size, int) and not isinstance(min_size, bool) and 1 <= min_size < 2 ** 31,
-                 "min_size must be a positive integer")
+        _require_int(min_size, "min_size must be a positive integer", 1, 2 ** 31 - 1)
         _require(isinstance(drop_orphans, bool), "drop_orphans must be a bool")
         _require(self._source is not None, "absorb works on the object segments() returned, not on its trim()")
         grid, voxel_labels, L, num_class, connectivity = self._source
         dev = self.segment.device
         M = self.shape[0]
-        _require(out is None or (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and tuple(out.shape) == (M,)
-                                 and out.device == dev and out.is_contiguous()),
+        _require(out is None or _is_tensor(out, torch.int32, (M,), dev),
                  "out must be a contiguous int32 (M,) tensor on the cloud's device")
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        _require(dev.type == "cuda", _NO_CPU)
         if out is None:
             out = torch.empty((M,), dtype=torch.int32, device=dev)
         if self.absorbed_label is None:
@@ -494,17 +454,13 @@ class GridSegments:
             self.absorb_stats.zero_()
             return out
         lib = _lib.load()
-        need = int(lib.conv3p_grid_absorb_workspace_bytes(M))
-        if self._absorb_workspace is None or self._absorb_workspace.numel() < need:
-            self._absorb_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _grow(self, "_absorb_workspace", int(lib.conv3p_grid_absorb_workspace_bytes(M)), dev)
         neigh = grid.neighbors()
         with torch.cuda.device(dev):
             _call(lib.conv3p_grid_absorb_segments, neigh.data_ptr(), _labels_pointer(voxel_labels, L, self.segment), L,
-                  self.segment.data_ptr(),
-                  self.size.data_ptr(), self.label.data_ptr(), self.stats.data_ptr(), grid.stats.data_ptr(), M, num_class,
-                  connectivity, min_size, int(drop_orphans), out.data_ptr(), self.absorbed_label.data_ptr(),
-                  self.absorb_stats.data_ptr(), self._absorb_workspace.data_ptr(), self._absorb_workspace.numel(),
-                  torch.cuda.current_stream(dev).cuda_stream)
+                  self.segment.data_ptr(), self.size.data_ptr(), self.label.data_ptr(), self.stats.data_ptr(),
+                  grid.stats.data_ptr(), M, num_class, connectivity, min_size, int(drop_orphans), out.data_ptr(),
+                  self.absorbed_label.data_ptr(), self.absorb_stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
         return out
 
     def geometry(self, weight="voxels", out=None):
@@ -532,19 +488,15 @@ class GridSegments:
         grid = self._source[0]
         dev = self.segment.device
         M = self.shape[0]
-        _require(isinstance(grid.data, torch.Tensor) and grid.data.dtype == torch.float32 and grid.data.dim() == 2
-                 and grid.data.shape[0] == M and 3 <= grid.data.shape[1] <= 65536 and grid.data.is_contiguous()
-                 and grid.data.device == dev,
+        _require(_is_tensor(grid.data, torch.float32, dev=dev, ndim=2) and grid.data.shape[0] == M
+                 and 3 <= grid.data.shape[1] <= 65536,
                  "the subsampling's data must be a contiguous float32 (M, 3 <= K <= 65536) tensor on the segments' device")
-        for name, t, shape in (("voxel_cell", grid.voxel_cell, (M, 3)), ("voxel_count", grid.voxel_count, (M,)),
-                               ("stats", grid.stats, (8,)), ("segment", self.segment, (M,)), ("stats", self.stats, (8,))):
-            _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()
-                     and tuple(t.shape) == shape,
-                     "%s must be a contiguous int32 tensor of the subsampling's shape on its device" % name)
+        _require_table(dev, (("voxel_cell", grid.voxel_cell, (M, 3)), ("voxel_count", grid.voxel_count, (M,)),
+                             ("stats", grid.stats, (8,)), ("segment", self.segment, (M,)), ("stats", self.stats, (8,))))
         if out is not None:
             _require(isinstance(out, SegmentGeometry) and out.shape == (M,) and out.cell_box.device == dev,
                      "out was made for another shape")
-        _require(dev.type == "cuda", "the cloud must live on a HIP device (there is no CPU path)")
+        _require(dev.type == "cuda", _NO_CPU)
         if out is None:
             out = SegmentGeometry(M, dev)
         if M == 0:
@@ -555,7 +507,7 @@ class GridSegments:
                   grid.voxel_cell.data_ptr(), grid.voxel_count.data_ptr(), self.segment.data_ptr(), self.stats.data_ptr(),
                   grid.stats.data_ptr(), M, _GEOMETRY_WEIGHTS[weight], out.cell_box.data_ptr(), out.box.data_ptr(),
                   out.moments.data_ptr(), out.centroid.data_ptr(), out.eigenvalues.data_ptr(), out.axes.data_ptr(),
-                  out.extent.data_ptr(), out.stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                  out.extent.data_ptr(), out.stats.data_ptr(), _stream(dev))
         return out
 
 
@@ -590,11 +542,8 @@ class SegmentGeometry:
     def trim(self):
         """Views of the first num_segments() rows, as a SegmentGeometry (stats shared)."""
         S = self.num_segments()
-        t = object.__new__(SegmentGeometry)
-        t.shape = (S,)
-        t.cell_box, t.box, t.moments, t.centroid = self.cell_box[:S], self.box[:S], self.moments[:S], self.centroid[:S]
-        t.eigenvalues, t.axes, t.extent, t.stats = self.eigenvalues[:S], self.axes[:S], self.extent[:S], self.stats
-        return t
+        return _view(self, SegmentGeometry, slice(S), ("cell_box", "box", "moments", "centroid", "eigenvalues", "axes", "extent"),
+                     ("stats",), shape=(S,))
 
 
 class GridNormals:
@@ -618,29 +567,62 @@ class GridNormals:
         return int(self.stats[0])
 
 
-def _check_arguments(data, labels, voxel, mode, num_class):
-    """The argument checks grid_subsample and grid_subsample_rooms share, in grid_subsample's order -> voxel as float32."""
-    _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
+def _subsample(many, data, room_start, labels, voxel, mode, num_class, max_voxels, out):
+    """The body of grid_subsample and, with `many`, of grid_subsample_rooms: every check in the order the calls have always
+    made them, the max_voxels default, out reuse, the workspace, the nothing-to-launch fill and the launch.  The rooms
+    contribute their room_start, its checks, and their extra outputs and arguments."""
+    _require(_is_tensor(data, torch.float32, ndim=2, contiguous=False) and data.shape[1] >= 3,
              "data must be a float32 (N, K >= 3) tensor, xyz first")
     dev = data.device
     N, K = data.shape
     _require(data.is_contiguous(), "data must be contiguous")
     if labels is not None:
         _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
-        _require(labels.device == dev and tuple(labels.shape) == (N,) and labels.is_contiguous(),
-                 "labels must be a contiguous (N,) tensor on the data's device")
+        _require_tensor(labels, "labels must be a contiguous (N,) tensor on the data's device", _LABEL_DTYPES, (N,), dev)
     _require(isinstance(voxel, (int, float)) and not isinstance(voxel, bool) and math.isfinite(voxel)
              and math.isfinite(float(np.float32(voxel))) and float(np.float32(voxel)) > 0, "voxel must be finite and positive")
+    voxel = float(np.float32(voxel))
     _require(isinstance(mode, str) and mode in _MODES, "mode must be \"mean\" or \"center\"")
     if labels is not None and mode == "mean":
-        _require(isinstance(num_class, int) and not isinstance(num_class, bool) and 1 <= num_class <= _lib.GRID_MAX_CLASS,
-                 "num_class must be an integer in [1, %d] for the majority label" % _lib.GRID_MAX_CLASS)
+        _require_int(num_class, "num_class must be an integer in [1, %d] for the majority label" % _lib.GRID_MAX_CLASS, 1,
+                     _lib.GRID_MAX_CLASS)
     else:
-        _require(num_class is None or (isinstance(num_class, int) and not isinstance(num_class, bool)),
-                 "num_class must be an integer or None")
+        _require(num_class is None or _is_int(num_class, -math.inf, math.inf), "num_class must be an integer or None")
     _require(N <= _lib.GRID_MAX_ROWS, "at most 2^24 rows")
     _require(K <= 65536, "at most 65536 channels")
-    return float(np.float32(voxel))
+    if max_voxels is None:
+        max_voxels = N
+    _require_int(max_voxels, "max_voxels must be a non-negative integer", 0, 2 ** 31 - 1)
+    cls, shape = GridSubsample, (N, max_voxels, K, labels is not None)
+    if many:
+        _require(_is_tensor(room_start, torch.int32, dev=dev, ndim=1) and room_start.numel() >= 1,
+                 "room_start must be a contiguous int32 (R + 1,) tensor on the data's device")
+        R = room_start.numel() - 1
+        _require(R <= _lib.GRID_ROOMS_MAX_ROOMS, "at most 65536 rooms")
+        cls, shape = GridRoomSubsample, shape + (R,)
+    if out is not None:
+        _require(isinstance(out, cls) and out.shape == shape and out.data.device == dev, "out was made for another shape")
+    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
+    lib = _lib.load()
+    need = (lib.conv3p_grid_subsample_rooms_workspace_bytes(N, R, max_voxels) if many else
+            lib.conv3p_grid_subsample_workspace_bytes(N, max_voxels))
+    if out is None:
+        out = GridRoomSubsample(N, R, *shape[1:4], dev, need) if many else GridSubsample(*shape, dev, need)
+    elif need:
+        _grow(out, "workspace", need, dev)
+    out._neigh = None                        # the neighbour table of an earlier call's voxels
+    if N == 0 or max_voxels == 0 or (many and R == 0):   # nothing is launched, so nothing is written
+        _fill_empty(out)
+        return out
+    ws = out.workspace
+    with torch.cuda.device(dev):
+        _call(lib.conv3p_grid_subsample_rooms_f32 if many else lib.conv3p_grid_subsample_f32, data.data_ptr(), _ptr(labels),
+              *((room_start.data_ptr(), N, R) if many else (N,)), K, _LABEL_DTYPES[labels.dtype] if labels is not None else 0,
+              voxel, _MODES[mode], num_class if num_class is not None else 0, max_voxels, out.data.data_ptr(), _ptr(out.labels),
+              out.voxel_row.data_ptr(), out.voxel_count.data_ptr(), out.voxel_cell.data_ptr(),
+              *((out.voxel_room.data_ptr(), out.voxel_start.data_ptr()) if many else ()), out.inverse.data_ptr(),
+              *((out.room_stats.data_ptr(),) if many else ()), out.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+    return out
 
 
 class GridRoomSubsample(GridSubsample):
@@ -651,6 +633,9 @@ class GridRoomSubsample(GridSubsample):
     {emitted voxels, occupied voxels, R, rooms with an emitted voxel, rooms with an error of their own, non-finite rows
     inside the rooms, largest member count, error bits: 1 a room's lattice too large, 2 room_start malformed, 4 too
     many cells in all}.  project is GridSubsample's: one call serves every room."""
+
+    _SLICED, _SHARED = GridSubsample._SLICED + ("voxel_room",), GridSubsample._SHARED + ("voxel_start", "room_stats")
+    _FILL = GridSubsample._FILL + (("voxel_room", -1), ("voxel_start", 0), ("room_stats", 0))
 
     def __init__(self, num_rows, num_rooms, max_voxels, K, with_labels, device, workspace_bytes=0):
         GridSubsample.__init__(self, num_rows, max_voxels, K, with_labels, device, workspace_bytes)
@@ -664,32 +649,18 @@ class GridRoomSubsample(GridSubsample):
         """Views of the first num_voxels() voxels, as a GridRoomSubsample (inverse, stats, voxel_start and room_stats
         shared)."""
         nv = self.num_voxels()
-        t = object.__new__(GridRoomSubsample)
-        t.shape = (self.shape[0], nv) + self.shape[2:]
-        t.data = self.data[:nv]
-        t.labels = self.labels[:nv] if self.labels is not None else None
-        t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[:nv], self.voxel_count[:nv], self.voxel_cell[:nv]
-        t.voxel_room = self.voxel_room[:nv]
-        t.inverse, t.stats, t.workspace = self.inverse, self.stats, None
-        t.voxel_start, t.room_stats = self.voxel_start, self.room_stats
-        if getattr(self, "_neigh", None) is not None:
-            t._neigh = self._neigh[:nv]
-        return t
+        return _view(self, GridRoomSubsample, slice(nv), self._SLICED, self._SHARED,
+                     shape=(self.shape[0], nv) + self.shape[2:], workspace=None)
 
     def room(self, r):
         """Views of room r's emitted voxels, as a GridSubsample whose stats is room_stats[r].  Reads voxel_start on the
         host (a synchronisation).  inverse is shared: it holds global voxel numbers, so subtract voxel_start[r] to index
         the view."""
         R = self.voxel_start.numel() - 1
-        _require(isinstance(r, int) and not isinstance(r, bool) and 0 <= r < R, "r must be a room number in [0, R)")
+        _require_int(r, "r must be a room number in [0, R)", 0, R - 1)
         a, b = (int(x) for x in self.voxel_start[r:r + 2].cpu())
-        t = object.__new__(GridSubsample)
-        t.shape = (self.shape[0], b - a) + self.shape[2:4]
-        t.data = self.data[a:b]
-        t.labels = self.labels[a:b] if self.labels is not None else None
-        t.voxel_row, t.voxel_count, t.voxel_cell = self.voxel_row[a:b], self.voxel_count[a:b], self.voxel_cell[a:b]
-        t.inverse, t.stats, t.workspace = self.inverse, self.room_stats[r], None
-        return t
+        return _view(self, GridSubsample, slice(a, b), GridSubsample._ROWS, ("inverse",),        # _neigh holds global numbers: not the view's
+                     shape=(self.shape[0], b - a) + self.shape[2:4], stats=self.room_stats[r], workspace=None)
 
 
 def grid_subsample_rooms(data, room_start, labels=None, voxel=0.05, mode="mean", num_class=None, max_voxels=None, out=None):
@@ -714,52 +685,7 @@ def grid_subsample_rooms(data, room_start, labels=None, voxel=0.05, mode="mean",
         ...
         labels = g.project(scores.labels())                            # (N) int32 over the raw rows of every room
     """
-    voxel = _check_arguments(data, labels, voxel, mode, num_class)
-    dev = data.device
-    N, K = data.shape
-    if max_voxels is None:
-        max_voxels = N
-    _require(isinstance(max_voxels, int) and not isinstance(max_voxels, bool) and 0 <= max_voxels < 2 ** 31,
-             "max_voxels must be a non-negative integer")
-    _require(isinstance(room_start, torch.Tensor) and room_start.dtype == torch.int32 and room_start.dim() == 1
-             and room_start.numel() >= 1 and room_start.is_contiguous() and room_start.device == dev,
-             "room_start must be a contiguous int32 (R + 1,) tensor on the data's device")
-    R = room_start.numel() - 1
-    _require(R <= _lib.GRID_ROOMS_MAX_ROOMS, "at most 65536 rooms")
-    if out is not None:
-        _require(isinstance(out, GridRoomSubsample) and out.shape == (N, max_voxels, K, labels is not None, R)
-                 and out.data.device == dev, "out was made for another shape")
-    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
-    lib = _lib.load()
-    need = lib.conv3p_grid_subsample_rooms_workspace_bytes(N, R, max_voxels)
-    if out is None:
-        out = GridRoomSubsample(N, R, max_voxels, K, labels is not None, dev, need)
-    elif need and (out.workspace is None or out.workspace.numel() < need):
-        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    out._neigh = None                        # the neighbour table of an earlier call's voxels
-    if N == 0 or R == 0 or max_voxels == 0:   # nothing is launched, so nothing is written
-        out.data.zero_()
-        out.inverse.fill_(-1)
-        out.voxel_row.fill_(-1)
-        out.voxel_count.zero_()
-        out.voxel_cell.fill_(-1)
-        out.voxel_room.fill_(-1)
-        out.voxel_start.zero_()
-        out.room_stats.zero_()
-        out.stats.zero_()
-        if out.labels is not None:
-            out.labels.fill_(-1)
-        return out
-    ws = out.workspace
-    with torch.cuda.device(dev):
-        _call(lib.conv3p_grid_subsample_rooms_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None,
-              room_start.data_ptr(), N, R, K, _LABEL_DTYPES[labels.dtype] if labels is not None else 0, voxel, _MODES[mode],
-              num_class if num_class is not None else 0, max_voxels, out.data.data_ptr(),
-              out.labels.data_ptr() if labels is not None else None, out.voxel_row.data_ptr(), out.voxel_count.data_ptr(),
-              out.voxel_cell.data_ptr(), out.voxel_room.data_ptr(), out.voxel_start.data_ptr(), out.inverse.data_ptr(),
-              out.room_stats.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
-              torch.cuda.current_stream(dev).cuda_stream)
-    return out
+    return _subsample(True, data, room_start, labels, voxel, mode, num_class, max_voxels, out)
 
 
 def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, max_voxels=None, out=None):
@@ -771,40 +697,4 @@ def grid_subsample(data, labels=None, voxel=0.05, mode="mean", num_class=None, m
     voxel's centre, copied with its label (num_class is not used).  max_voxels=None means N, which never cuts.  out: a
     GridSubsample of an earlier call with the same shapes, written into.  Nothing is synchronised on; stats[7] != 0
     reports a lattice of more than 2^20 cells along an axis or 2^40 in all (nothing emitted, inverse all -1)."""
-    voxel = _check_arguments(data, labels, voxel, mode, num_class)
-    dev = data.device
-    N, K = data.shape
-    if max_voxels is None:
-        max_voxels = N
-    _require(isinstance(max_voxels, int) and not isinstance(max_voxels, bool) and 0 <= max_voxels < 2 ** 31,
-             "max_voxels must be a non-negative integer")
-    if out is not None:
-        _require(isinstance(out, GridSubsample) and out.shape == (N, max_voxels, K, labels is not None)
-                 and out.data.device == dev, "out was made for another shape")
-    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
-    lib = _lib.load()
-    need = lib.conv3p_grid_subsample_workspace_bytes(N, max_voxels)
-    if out is None:
-        out = GridSubsample(N, max_voxels, K, labels is not None, dev, need)
-    elif need and (out.workspace is None or out.workspace.numel() < need):
-        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    out._neigh = None                        # the neighbour table of an earlier call's voxels
-    if N == 0 or max_voxels == 0:            # nothing is launched, so nothing is written
-        out.data.zero_()
-        out.inverse.fill_(-1)
-        out.voxel_row.fill_(-1)
-        out.voxel_count.zero_()
-        out.voxel_cell.fill_(-1)
-        out.stats.zero_()
-        if out.labels is not None:
-            out.labels.fill_(-1)
-        return out
-    ws = out.workspace
-    with torch.cuda.device(dev):
-        _call(lib.conv3p_grid_subsample_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None, N, K,
-              _LABEL_DTYPES[labels.dtype] if labels is not None else 0, voxel, _MODES[mode],
-              num_class if num_class is not None else 0, max_voxels, out.data.data_ptr(),
-              out.labels.data_ptr() if labels is not None else None, out.voxel_row.data_ptr(), out.voxel_count.data_ptr(),
-              out.voxel_cell.data_ptr(), out.inverse.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
-              torch.cuda.current_stream(dev).cuda_stream)
-    return out
+    return _subsample(False, data, None, labels, voxel, mode, num_class, max_voxels, out)

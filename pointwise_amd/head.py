@@ -31,22 +31,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .conv3p_op import Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _require
+from ._host import (_HEADS, Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _ptr, _require, _stream,
+                    _workspace)
 
 SELU_ALPHA = 1.6732632423543772848170429916717
 SELU_SCALE = 1.0507009873554804934193349852946
-
-_WS = {}
-
-
-def _workspace(dev, nbytes):
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _WS[key] = buf
-    return buf
-
 
 def _check_fc(x, W, b):
     if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[0]:
@@ -69,9 +58,9 @@ def fully_connected(x, W, b=None, selu=True):
     y = torch.empty((M, N), dtype=torch.float32, device=dev)
     need = lib.conv3p_fc_workspace_bytes(M, K, N)
     with torch.cuda.device(dev):
-        ws = _workspace(dev, need)
-        _call(lib.conv3p_fc_forward_f32, x.data_ptr(), W.data_ptr(), b.data_ptr() if b is not None else None, M, K, N,
-              1 if selu else 0, y.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        ws = _workspace(dev, need, _HEADS)
+        _call(lib.conv3p_fc_forward_f32, x.data_ptr(), W.data_ptr(), _ptr(b), M, K, N, 1 if selu else 0, y.data_ptr(),
+              ws.data_ptr(), ws.numel(), _stream(dev))
     return y
 
 
@@ -90,10 +79,9 @@ def fully_connected_grad(x, W, y, dy, selu=True, need_dx=True, dW_out=None, db_o
         raise Conv3pInvalidArgument("dW_out must be a contiguous (K, N) tensor")
     need = lib.conv3p_fc_workspace_bytes(M, K, N)
     with torch.cuda.device(dev):
-        ws = _workspace(dev, need)
+        ws = _workspace(dev, need, _HEADS)
         _call(lib.conv3p_fc_backward_f32, x.data_ptr(), W.data_ptr(), y.data_ptr(), dy.data_ptr(), M, K, N,
-              1 if selu else 0, dx.data_ptr() if dx is not None else None, dW.data_ptr(), db.data_ptr(),
-              ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+              1 if selu else 0, _ptr(dx), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
     return dx, dW, db
 
 
@@ -179,21 +167,19 @@ def classification_tail(fc1, W2, b2, labels, rate=0.5, training=True, keep_mask=
                  and dW2.dtype == torch.float32 and db2.dtype == torch.float32,
                  "classification_tail: dW2_out / db2_out must be contiguous float32 (H, C) / (C)")
     keep = torch.empty((M, H), dtype=torch.uint8, device=dev) if need_keep and dropout else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
     scale = float(grad_scale) if grad_scale is not None else 1.0 / M
     lib = _lib.load()
     need = lib.conv3p_cls_tail_workspace_bytes(M, H, C)
     with torch.cuda.device(dev):
-        ws = _workspace(dev, need)
+        ws = _workspace(dev, need, _HEADS)
         head = (fc1.data_ptr(), W2.data_ptr(), b2.data_ptr(), labels.data_ptr(), M, H, C, 1 if training else 0, float(rate),
-                ptr(keep_mask), int(seed), int(step), scale, logits.data_ptr(), pred.data_ptr(), ptr(dfc1))
-        tail = (ptr(keep), loss_sum.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                torch.cuda.current_stream(dev).cuda_stream)
+                _ptr(keep_mask), int(seed), int(step), scale, logits.data_ptr(), pred.data_ptr(), _ptr(dfc1))
+        tail = (_ptr(keep), loss_sum.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
         if stepping:
             _call(lib.conv3p_cls_tail_step_f32, *head, accum_W2.data_ptr(), accum_b2.data_ptr(), float(lr), float(momentum),
                   *tail)
         else:
-            _call(lib.conv3p_cls_tail_f32, *head, ptr(dW2), ptr(db2), *tail)
+            _call(lib.conv3p_cls_tail_f32, *head, _ptr(dW2), _ptr(db2), *tail)
     return {"logits": logits, "pred": pred, "loss_sum": loss_sum, "counts": counts, "dfc1": dfc1, "dW2": dW2, "db2": db2,
             "keep": keep}
 

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, distributed
-from .conv3p_op import _SFX, Conv3pInvalidArgument, _call, _require
+from ._host import _HEADS, _SFX, Conv3pInvalidArgument, _call, _check_device, _require, _workspace
 
 MAX_TENSORS = _lib.OPT_MAX_TENSORS
 
@@ -95,7 +95,6 @@ def grad_sumsq(grads, out=None, accumulate=False):
     if out is not None:
         _check_stats(out, todo[0][0].device if todo else None)
         _require(out.device.type == "cuda", "MomentumOptimizer: tensors must live on a HIP device (no CPU path in pointwise_amd)")
-    from .head import _workspace
     lib = _lib.load()
     dev = out.device if out is not None else todo[0][0].device
     if out is None:
@@ -103,7 +102,7 @@ def grad_sumsq(grads, out=None, accumulate=False):
     need = lib.conv3p_grad_norm_workspace_bytes()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _workspace(dev, need)
+        ws = _workspace(dev, need, _HEADS)
         acc = 1 if accumulate else 0
         calls = 0
         for dt, (sfx, _, _) in _SFX.items():
@@ -301,8 +300,7 @@ class MomentumOptimizer:
         """fully_connected_grad and this optimizer's update of W (and b) as one pass (conv3p_fc_backward_step_f32): W, b
         and their accumulators are updated in place, dW and db are never written; returns dx (from the OLD W) or None.
         Bit-equal to head.fully_connected_grad followed by step().  Does not advance the global step."""
-        from .head import _check_fc, _workspace
-        from .conv3p_op import _check_device
+        from .head import _check_fc
         _require(self.fusable, "MomentumOptimizer: fused_fc_step applies the plain rule inside the gradient pass; with "
                  "use_nesterov, clip_norm or skip_nonfinite use fully_connected_grad and step()")
         lib = _lib.load()
@@ -318,7 +316,7 @@ class MomentumOptimizer:
         dx = torch.empty_like(x) if need_dx else None
         need = lib.conv3p_fc_workspace_bytes(M, K, N)
         with torch.cuda.device(dev):
-            ws = _workspace(dev, need)
+            ws = _workspace(dev, need, _HEADS)
             _call(lib.conv3p_fc_backward_step_f32, x.data_ptr(), W.data_ptr(), b.data_ptr() if b is not None else None,
                   y.data_ptr(), dy.data_ptr(), M, K, N, 1 if selu else 0, dx.data_ptr() if dx is not None else None,
                   self.accums[iw].data_ptr(), self.accums[ib].data_ptr() if ib is not None else None,

@@ -23,11 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .conv3p_op import Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+from ._host import Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _ptr, _stream
 
 
 def _augment(batch_data, cos_sin, noise, sigma, clip):
@@ -48,8 +44,8 @@ def _augment(batch_data, cos_sin, noise, sigma, clip):
             raise Conv3pInvalidArgument("noise must be a float64 BxNx3 tensor on the batch's device")
         noise = noise.contiguous()
     with torch.cuda.device(dev):
-        _call(lib.conv3p_augment_f32, x.data_ptr(), cs.data_ptr() if cs is not None else None,
-              noise.data_ptr() if noise is not None else None, float(sigma), float(clip), B, N, out.data_ptr(), _stream(dev))
+        _call(lib.conv3p_augment_f32, x.data_ptr(), _ptr(cs), _ptr(noise), float(sigma), float(clip), B, N, out.data_ptr(),
+              _stream(dev))
     return out
 
 
@@ -155,9 +151,10 @@ def sort_point_cloud_morton2(batch_data, batch_attributes):
 SORT_METHODS = {"xyz": _lib.SORT_XYZ, "morton": _lib.SORT_MORTON}
 
 
-def _check_sort_method(sort_method):
-    """An unknown method is an error raised before anything touches the device, as in the provider."""
-    if sort_method not in SORT_METHODS:
+def _check_sort_method(sort_method, known=SORT_METHODS):
+    """An unknown method is an error raised before anything touches the device, here and in the provider (which looks the
+    method up in a tuple of the names, where a method that cannot be hashed is unknown like any other) -> its C value."""
+    if sort_method not in known:
         raise ValueError("sort_method must be one of %s, not %r" % (", ".join(map(repr, SORT_METHODS)), sort_method))
     return SORT_METHODS[sort_method]
 
@@ -181,7 +178,7 @@ def sort_order(batch_data, sort_method="xyz", workspace=None):
         raise Conv3pInvalidArgument("workspace must be a contiguous uint8 tensor on the batch's device")
     with torch.cuda.device(dev):
         _call(lib.conv3p_sort_order_f32, x.data_ptr(), B, N, K, method, order.data_ptr(),
-              workspace.data_ptr() if workspace.numel() else None, workspace.numel(), _stream(dev))
+              _ptr(workspace), workspace.numel(), _stream(dev))
     return order
 
 

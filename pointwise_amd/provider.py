@@ -26,17 +26,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from .conv3p_op import Conv3pInvalidArgument, _call, _require
-
-_LABEL_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
-SORT_METHODS = ("xyz", "morton")
+from . import prestep
+from ._host import _LABEL_DTYPES, Conv3pInvalidArgument, _call, _ptr, _require, _require_tensor, _stream
+from .prestep import SORT_METHODS
 
 
 def _check_sort_method(sort_method):
     """The reference prints a message and feeds unsorted clouds when it does not know the method; here it is an error,
-    raised before anything touches the device."""
-    if sort_method not in SORT_METHODS:
-        raise ValueError("sort_method must be one of %s, not %r" % (", ".join(map(repr, SORT_METHODS)), sort_method))
+    raised before anything touches the device (prestep's check) -> the method."""
+    prestep._check_sort_method(sort_method, tuple(SORT_METHODS))
     return sort_method
 
 
@@ -69,10 +67,6 @@ class BatchBuffers:
             self.cos_sin = torch.empty((B, 2), dtype=torch.float64, device=device)
             self.noise = torch.empty((B, N, 3), dtype=torch.float64, device=device)
             self.order = torch.empty((B, N), dtype=torch.int32, device=device)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
 
 
 def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0, rotate=False, jitter=False, sigma=0.01,
@@ -108,8 +102,7 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
     start = int(start)
     _require(start >= 0, "start must not be negative")
     if perm is not None:
-        _require(isinstance(perm, torch.Tensor) and perm.dtype == torch.int32 and perm.dim() == 1 and perm.device == dev
-                 and perm.is_contiguous(), "perm must be a contiguous int32 vector on the data's device")
+        _require_tensor(perm, "perm must be a contiguous int32 vector on the data's device", torch.int32, dev=dev, ndim=1)
         _require(start + B <= perm.numel(), "batch_size + start reaches past perm")
     else:
         _require(start + B <= 2 ** 31 - 1, "start out of range")
@@ -121,8 +114,8 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
         if t is None:
             continue
         _require(on, "%s given without the augmentation it belongs to" % name)
-        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev and tuple(t.shape) == shape
-                 and t.is_contiguous(), "%s must be a contiguous float64 %s tensor on the data's device" % (name, shape))
+        _require_tensor(t, "%s must be a contiguous float64 %s tensor on the data's device" % (name, shape), torch.float64,
+                        shape, dev)
     _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
     if out is None:
         out = BatchBuffers(B, N, K, per_point, dev, sort_cloud, return_randoms, sort_method, wide_sort)
@@ -146,12 +139,12 @@ def assemble_batch(data, labels, batch_size, num_points=None, perm=None, start=0
     with torch.cuda.device(dev):
         _call(lib.conv3p_provider_batch_wide_f32 if wide else lib.conv3p_provider_batch_f32,
               _ptr(data), _ptr(labels), S, Nsrc, K, _LABEL_DTYPES[labels.dtype],
-              int(per_point), perm.data_ptr() if perm is not None else None, perm.numel() if perm is not None else 0,
+              int(per_point), _ptr(perm), perm.numel() if perm is not None else 0,
               start, B, N, flags, float(sigma), float(clip), int(seed), int(step), _ptr(cos_sin), _ptr(noise),
               _ptr(out.points), _ptr(out.input), _ptr(out.labels),
               _ptr(out.cos_sin) if rnd else None, _ptr(out.noise) if rnd else None, _ptr(out.order) if rnd else None,
-              out.bad_index.data_ptr(), ws.data_ptr() if need else None, ws.numel() if need else 0,
-              torch.cuda.current_stream(dev).cuda_stream)
+              out.bad_index.data_ptr(), _ptr(ws, need), ws.numel() if need else 0,
+              _stream(dev))
     res = (out.points, out.input, out.labels, out.bad_index)
     if return_randoms:
         res += ({"cos_sin": out.cos_sin, "noise": out.noise, "order": out.order},)

@@ -52,9 +52,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .conv3p_op import _call, _require
-
-_LABEL_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+from ._host import (_LABEL_DTYPES, _call, _fill_empty, _grow, _is_tensor, _ptr, _require, _require_int, _require_tensor,
+                    _stream, _view)
 
 
 def default_max_blocks(num_rows, block=1.0, stride=1.0, min_points=100, num_point=None):
@@ -77,6 +76,9 @@ class SceneBlocks:
     {emitted blocks, kept cells, nbx, nby, non-finite rows, cells with 0 < count < min_points, 0, error}.  Blocks past
     the emitted ones hold data 0, labels -1, index -1, block_cell -1, block_count 0.  In the covering mode a block is a
     part of its cell, block_count its distinct members (the first slots) and stats[6] the blocks the room needs."""
+
+    _SLICED, _SHARED = ("data", "labels", "index", "block_cell", "block_count"), ("stats",)     # what a view cuts / shares
+    _FILL = (("data", 0), ("labels", -1), ("index", -1), ("block_cell", -1), ("block_count", 0), ("stats", 0))
 
     def __init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes=0):
         B, P = int(max_blocks), int(num_point)
@@ -105,17 +107,103 @@ class SceneBlocks:
     def trim(self):
         """Views of the first num_blocks() blocks, as a SceneBlocks (stats shared)."""
         nb = self.num_blocks()
-        t = object.__new__(SceneBlocks)
-        t.shape = (nb,) + self.shape[1:]
-        t.data, t.index = self.data[:nb], self.index[:nb]
-        t.labels = self.labels[:nb] if self.labels is not None else None
-        t.block_cell, t.block_count = self.block_cell[:nb], self.block_count[:nb]
-        t.stats, t.workspace = self.stats, None
-        return t
+        return _view(self, SceneBlocks, slice(nb), self._SLICED, self._SHARED, shape=(nb,) + self.shape[1:], workspace=None)
 
 
 def _as_f32(x):
     return float(np.float32(x))
+
+
+def _host_room_start(room_start, N):
+    """The checks of a room_start the host can read (a Python sequence, numpy array or CPU tensor) -> it as int64."""
+    if isinstance(room_start, torch.Tensor):
+        _require(room_start.dtype in (torch.int32, torch.int64), "room_start must hold integers (int32 or int64)")
+        rs = room_start.numpy()
+    else:
+        try:
+            rs = np.asarray(room_start)
+        except Exception:
+            rs = None
+        _require(rs is not None and rs.dtype.kind in "iu", "room_start must hold integers")
+    _require(rs.ndim == 1 and rs.size >= 1, "room_start must have R + 1 >= 1 entries")
+    rs = rs.astype(np.int64)
+    _require(int(rs[0]) >= 0 and int(rs[-1]) <= N and bool(np.all(np.diff(rs) >= 0)), "room_start must ascend inside [0, N]")
+    _require(rs.size < 2 or int(np.diff(rs).max()) <= _lib.SCENE_MAX_ROWS, "at most 2^24 rows a room")
+    return rs
+
+
+def _blocks(many, data, room_start, labels, num_point, block, stride, min_points, max_blocks, seed, step, out, cover):
+    """The body of scene_blocks and, with `many`, of scene_blocks_rooms: every check in the order the calls have always
+    made them, the max_blocks default, out reuse, the workspace, the nothing-to-launch fill and the launch.  The rooms
+    contribute their room_start, their limits and messages, and their extra outputs and arguments."""
+    _require(_is_tensor(data, torch.float32, ndim=2, contiguous=False) and data.shape[1] >= 3,
+             "data must be a float32 (N, K >= 3) tensor, xyz first")
+    dev = data.device
+    N, K = data.shape
+    _require(data.is_contiguous(), "data must be contiguous")
+    R, rs = None, None
+    if many and isinstance(room_start, torch.Tensor) and room_start.device.type != "cpu":
+        _require(room_start.dtype == torch.int32 and room_start.dim() == 1 and room_start.numel() >= 1
+                 and room_start.is_contiguous() and room_start.device == dev,
+                 "a device room_start must be a contiguous int32 (R + 1,) tensor on the data's device")
+        R = room_start.numel() - 1
+    elif many:
+        rs = _host_room_start(room_start, N)
+        R = rs.size - 1
+    _require(not many or R <= _lib.SCENE_ROOMS_MAX_ROOMS, "at most 65536 rooms")
+    if labels is not None:
+        _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
+        _require_tensor(labels, "labels must be a contiguous (N,) tensor on the data's device", _LABEL_DTYPES, (N,), dev)
+    _require_int(num_point, "num_point must be an integer in [1, %d]" % _lib.SCENE_MAX_NUM_POINT, 1, _lib.SCENE_MAX_NUM_POINT,
+                 allow_bool=True)
+    for name, v in (("block", block), ("stride", stride)):
+        _require(isinstance(v, (int, float)) and math.isfinite(v) and _as_f32(v) > 0, "%s must be finite and positive" % name)
+    block, stride = _as_f32(block), _as_f32(stride)
+    _require(stride <= block <= _as_f32(np.float32(2) * np.float32(stride)), "block must lie in [stride, 2 stride]")
+    if many:
+        _require(N <= _lib.SCENE_ROOMS_MAX_ROWS, "at most 2^26 rows")
+    else:
+        _require(N <= _lib.SCENE_MAX_ROWS, "at most 2^24 room rows")
+    _require(K <= 65536, "at most 65536 channels")
+    _require_int(min_points, "min_points must be an int32", -2 ** 31, 2 ** 31 - 1, allow_bool=True)
+    _require(isinstance(cover, bool), "cover must be a bool")
+    if max_blocks is None:
+        bound = (block, stride, min_points, num_point if cover else None)
+        max_blocks = (default_max_blocks(N, *bound) if not many else _rooms_bound(N, R, *bound) if rs is None else
+                      default_max_blocks_rooms(np.diff(rs).tolist(), *bound))
+    _require_int(max_blocks, "max_blocks must be a non-negative integer", 0, 2 ** 31 - 1, allow_bool=True)
+    _require(0 <= int(seed) < 2 ** 64 and 0 <= int(step) < 2 ** 64, "seed and step must fit 64 unsigned bits")
+    cls, shape = SceneRoomBlocks if many else SceneBlocks, (max_blocks, num_point, K, labels is not None) + ((R,) if many else ())
+    if out is not None:
+        _require(isinstance(out, cls) and out.shape == shape and out.data.device == dev, "out was made for another shape")
+    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
+    lib = _lib.load()
+    if many:
+        need = lib.conv3p_scene_blocks_rooms_workspace_bytes(N, R, num_point, max_blocks, block, stride, int(cover))
+        call = lib.conv3p_scene_blocks_rooms_f32
+    else:
+        nbytes, call = ((lib.conv3p_scene_blocks_cover_workspace_bytes, lib.conv3p_scene_blocks_cover_f32) if cover else
+                        (lib.conv3p_scene_blocks_workspace_bytes, lib.conv3p_scene_blocks_f32))
+        need = nbytes(N, num_point, max_blocks, block, stride)
+    if out is None:
+        out = cls(*shape[:4], dev, need, *shape[4:])
+    elif need:
+        _grow(out, "workspace", need, dev)
+    if many:
+        out._room_blocks_host = None
+        out.room_start = torch.from_numpy(rs.astype(np.int32)).to(dev) if rs is not None else room_start
+    if N == 0 or max_blocks == 0 or R == 0:  # nothing is launched, so nothing is written
+        _fill_empty(out)
+        return out
+    ws = out.workspace
+    with torch.cuda.device(dev):
+        _call(call, data.data_ptr(), _ptr(labels), *((out.room_start.data_ptr(), N, R) if many else (N,)), K,
+              _LABEL_DTYPES[labels.dtype] if labels is not None else 0, block, stride, num_point, min_points, max_blocks,
+              *((int(cover),) if many else ()), int(seed), int(step), out.data.data_ptr(), _ptr(out.labels),
+              out.index.data_ptr(), out.block_cell.data_ptr(), out.block_count.data_ptr(),
+              *((out.block_room.data_ptr(), out.room_blocks.data_ptr(), out.room_stats.data_ptr()) if many else ()),
+              out.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+    return out
 
 
 def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_points=100, max_blocks=None, seed=0,
@@ -129,58 +217,7 @@ def scene_blocks(data, labels=None, num_point=4096, block=1.0, stride=1.0, min_p
     bound from the shape alone.  (seed, step) select the draws.  out: a SceneBlocks of an earlier call with the same
     shapes, written into.  Nothing is synchronised on; stats[7] != 0 reports a tiling of more than SCENE_MAX_CELLS
     cells (nothing emitted)."""
-    _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
-             "data must be a float32 (N, K >= 3) tensor, xyz first")
-    dev = data.device
-    N, K = data.shape
-    _require(data.is_contiguous(), "data must be contiguous")
-    if labels is not None:
-        _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
-        _require(labels.device == dev and tuple(labels.shape) == (N,) and labels.is_contiguous(),
-                 "labels must be a contiguous (N,) tensor on the data's device")
-    _require(isinstance(num_point, int) and 1 <= num_point <= _lib.SCENE_MAX_NUM_POINT,
-             "num_point must be an integer in [1, %d]" % _lib.SCENE_MAX_NUM_POINT)
-    for name, v in (("block", block), ("stride", stride)):
-        _require(isinstance(v, (int, float)) and math.isfinite(v) and _as_f32(v) > 0, "%s must be finite and positive" % name)
-    block, stride = _as_f32(block), _as_f32(stride)
-    _require(stride <= block <= _as_f32(np.float32(2) * np.float32(stride)), "block must lie in [stride, 2 stride]")
-    _require(N <= _lib.SCENE_MAX_ROWS, "at most 2^24 room rows")
-    _require(K <= 65536, "at most 65536 channels")
-    _require(isinstance(min_points, int) and -2 ** 31 <= min_points < 2 ** 31, "min_points must be an int32")
-    _require(isinstance(cover, bool), "cover must be a bool")
-    if max_blocks is None:
-        max_blocks = default_max_blocks(N, block, stride, min_points, num_point if cover else None)
-    _require(isinstance(max_blocks, int) and 0 <= max_blocks < 2 ** 31, "max_blocks must be a non-negative integer")
-    _require(0 <= int(seed) < 2 ** 64 and 0 <= int(step) < 2 ** 64, "seed and step must fit 64 unsigned bits")
-    if out is not None:
-        _require(isinstance(out, SceneBlocks) and out.shape == (max_blocks, num_point, K, labels is not None)
-                 and out.data.device == dev, "out was made for another shape")
-    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
-    lib = _lib.load()
-    nbytes, call = ((lib.conv3p_scene_blocks_cover_workspace_bytes, lib.conv3p_scene_blocks_cover_f32) if cover else
-                    (lib.conv3p_scene_blocks_workspace_bytes, lib.conv3p_scene_blocks_f32))
-    need = nbytes(N, num_point, max_blocks, block, stride)
-    if out is None:
-        out = SceneBlocks(max_blocks, num_point, K, labels is not None, dev, need)
-    elif need and (out.workspace is None or out.workspace.numel() < need):
-        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    if N == 0 or max_blocks == 0:            # nothing is launched, so nothing is written
-        out.data.zero_()
-        out.index.fill_(-1)
-        out.block_cell.fill_(-1)
-        out.block_count.zero_()
-        out.stats.zero_()
-        if out.labels is not None:
-            out.labels.fill_(-1)
-        return out
-    ws = out.workspace
-    with torch.cuda.device(dev):
-        _call(call, data.data_ptr(), labels.data_ptr() if labels is not None else None, N, K,
-              _LABEL_DTYPES[labels.dtype] if labels is not None else 0, block, stride, num_point, min_points, max_blocks,
-              int(seed), int(step), out.data.data_ptr(), out.labels.data_ptr() if labels is not None else None,
-              out.index.data_ptr(), out.block_cell.data_ptr(), out.block_count.data_ptr(), out.stats.data_ptr(),
-              ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    return out
+    return _blocks(False, data, None, labels, num_point, block, stride, min_points, max_blocks, seed, step, out, cover)
 
 
 class SceneRoomBlocks(SceneBlocks):
@@ -191,6 +228,10 @@ class SceneRoomBlocks(SceneBlocks):
     blocks, kept cells, R, total cells, non-finite rows, small cells, blocks needed (covering), error bits: 1 a room of
     too many cells, 2 room_start malformed, 4 too many cells in all, 8 an internal error (more member pairs than the
     workspace bound: the result is not to be used)}."""
+
+    _SLICED = SceneBlocks._SLICED + ("block_room",)
+    _SHARED = SceneBlocks._SHARED + ("room_blocks", "room_stats", "room_start", "_room_blocks_host")
+    _FILL = SceneBlocks._FILL + (("block_room", -1), ("room_blocks", 0), ("room_stats", 0))
 
     def __init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes=0, num_rooms=0):
         SceneBlocks.__init__(self, max_blocks, num_point, K, with_labels, device, workspace_bytes)
@@ -205,14 +246,7 @@ class SceneRoomBlocks(SceneBlocks):
     def trim(self):
         """Views of the first num_blocks() blocks, as a SceneRoomBlocks (stats and the per-room tensors shared)."""
         nb = self.num_blocks()
-        t = object.__new__(SceneRoomBlocks)
-        t.shape = (nb,) + self.shape[1:]
-        t.data, t.index = self.data[:nb], self.index[:nb]
-        t.labels = self.labels[:nb] if self.labels is not None else None
-        t.block_cell, t.block_count, t.block_room = self.block_cell[:nb], self.block_count[:nb], self.block_room[:nb]
-        t.room_blocks, t.room_stats, t.room_start = self.room_blocks, self.room_stats, self.room_start
-        t.stats, t.workspace, t._room_blocks_host = self.stats, None, self._room_blocks_host
-        return t
+        return _view(self, SceneRoomBlocks, slice(nb), self._SLICED, self._SHARED, shape=(nb,) + self.shape[1:], workspace=None)
 
     def room(self, r):
         """Views of room r's blocks, as a SceneBlocks whose stats is room_stats[r]; index stays global.  The first call
@@ -222,13 +256,8 @@ class SceneRoomBlocks(SceneBlocks):
         if self._room_blocks_host is None:
             self._room_blocks_host = self.room_blocks.tolist()
         b0, b1 = self._room_blocks_host[r], self._room_blocks_host[r + 1]
-        t = object.__new__(SceneBlocks)
-        t.shape = (b1 - b0,) + self.shape[1:4]
-        t.data, t.index = self.data[b0:b1], self.index[b0:b1]
-        t.labels = self.labels[b0:b1] if self.labels is not None else None
-        t.block_cell, t.block_count = self.block_cell[b0:b1], self.block_count[b0:b1]
-        t.stats, t.workspace = self.room_stats[r], None
-        return t
+        return _view(self, SceneBlocks, slice(b0, b1), SceneBlocks._SLICED, (), shape=(b1 - b0,) + self.shape[1:4],
+                     stats=self.room_stats[r], workspace=None)
 
 
 def default_max_blocks_rooms(room_rows, block=1.0, stride=1.0, min_points=100, num_point=None):
@@ -259,140 +288,38 @@ def scene_blocks_rooms(data, room_start, labels=None, num_point=4096, block=1.0,
     // num_point blocks, and the outputs are allocated for it: 4 M rows at stride 0.5 ask for tens of GB -- so a caller
     with a device room_start should pass max_blocks (from the rooms' extents, or from a first call with max_blocks=1
     and blocks_needed()).  The other arguments are scene_blocks'.  Nothing is synchronised on."""
-    _require(isinstance(data, torch.Tensor) and data.dim() == 2 and data.dtype == torch.float32 and data.shape[1] >= 3,
-             "data must be a float32 (N, K >= 3) tensor, xyz first")
-    dev = data.device
-    N, K = data.shape
-    _require(data.is_contiguous(), "data must be contiguous")
-    host_rooms = None
-    if isinstance(room_start, torch.Tensor) and room_start.device.type != "cpu":
-        _require(room_start.dtype == torch.int32 and room_start.dim() == 1 and room_start.numel() >= 1
-                 and room_start.is_contiguous() and room_start.device == dev,
-                 "a device room_start must be a contiguous int32 (R + 1,) tensor on the data's device")
-        R = room_start.numel() - 1
-    else:
-        if isinstance(room_start, torch.Tensor):
-            _require(room_start.dtype in (torch.int32, torch.int64), "room_start must hold integers (int32 or int64)")
-            rs = room_start.numpy()
-        else:
-            try:
-                rs = np.asarray(room_start)
-            except Exception:
-                rs = None
-            _require(rs is not None and rs.dtype.kind in "iu", "room_start must hold integers")
-        _require(rs.ndim == 1 and rs.size >= 1, "room_start must have R + 1 >= 1 entries")
-        rs = rs.astype(np.int64)
-        _require(int(rs[0]) >= 0 and int(rs[-1]) <= N and bool(np.all(np.diff(rs) >= 0)),
-                 "room_start must ascend inside [0, N]")
-        _require(rs.size < 2 or int(np.diff(rs).max()) <= _lib.SCENE_MAX_ROWS, "at most 2^24 rows a room")
-        host_rooms = np.diff(rs).tolist()
-        R = rs.size - 1
-    _require(R <= _lib.SCENE_ROOMS_MAX_ROOMS, "at most 65536 rooms")
-    if labels is not None:
-        _require(isinstance(labels, torch.Tensor) and labels.dtype in _LABEL_DTYPES, "labels must be uint8, int32 or int64")
-        _require(labels.device == dev and tuple(labels.shape) == (N,) and labels.is_contiguous(),
-                 "labels must be a contiguous (N,) tensor on the data's device")
-    _require(isinstance(num_point, int) and 1 <= num_point <= _lib.SCENE_MAX_NUM_POINT,
-             "num_point must be an integer in [1, %d]" % _lib.SCENE_MAX_NUM_POINT)
-    for name, v in (("block", block), ("stride", stride)):
-        _require(isinstance(v, (int, float)) and math.isfinite(v) and _as_f32(v) > 0, "%s must be finite and positive" % name)
-    block, stride = _as_f32(block), _as_f32(stride)
-    _require(stride <= block <= _as_f32(np.float32(2) * np.float32(stride)), "block must lie in [stride, 2 stride]")
-    _require(N <= _lib.SCENE_ROOMS_MAX_ROWS, "at most 2^26 rows")
-    _require(K <= 65536, "at most 65536 channels")
-    _require(isinstance(min_points, int) and -2 ** 31 <= min_points < 2 ** 31, "min_points must be an int32")
-    _require(isinstance(cover, bool), "cover must be a bool")
-    if max_blocks is None:
-        if host_rooms is not None:
-            max_blocks = default_max_blocks_rooms(host_rooms, block, stride, min_points, num_point if cover else None)
-        else:
-            max_blocks = _rooms_bound(N, R, block, stride, min_points, num_point if cover else None)
-    _require(isinstance(max_blocks, int) and 0 <= max_blocks < 2 ** 31, "max_blocks must be a non-negative integer")
-    _require(0 <= int(seed) < 2 ** 64 and 0 <= int(step) < 2 ** 64, "seed and step must fit 64 unsigned bits")
-    if out is not None:
-        _require(isinstance(out, SceneRoomBlocks) and out.shape == (max_blocks, num_point, K, labels is not None, R)
-                 and out.data.device == dev, "out was made for another shape")
-    _require(dev.type == "cuda", "data must live on a HIP device (there is no CPU path)")   # after every other check
-    lib = _lib.load()
-    need = lib.conv3p_scene_blocks_rooms_workspace_bytes(N, R, num_point, max_blocks, block, stride, int(cover))
-    if out is None:
-        out = SceneRoomBlocks(max_blocks, num_point, K, labels is not None, dev, need, R)
-    elif need and (out.workspace is None or out.workspace.numel() < need):
-        out.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    out._room_blocks_host = None
-    if host_rooms is not None:
-        out.room_start = torch.from_numpy(rs.astype(np.int32)).to(dev)
-    else:
-        out.room_start = room_start
-    if R == 0 or N == 0 or max_blocks == 0:  # nothing is launched, so nothing is written
-        out.data.zero_()
-        out.index.fill_(-1)
-        out.block_cell.fill_(-1)
-        out.block_count.zero_()
-        out.block_room.fill_(-1)
-        out.room_blocks.zero_()
-        out.room_stats.zero_()
-        out.stats.zero_()
-        if out.labels is not None:
-            out.labels.fill_(-1)
-        return out
-    ws = out.workspace
-    with torch.cuda.device(dev):
-        _call(lib.conv3p_scene_blocks_rooms_f32, data.data_ptr(), labels.data_ptr() if labels is not None else None,
-              out.room_start.data_ptr(), N, R, K, _LABEL_DTYPES[labels.dtype] if labels is not None else 0, block, stride,
-              num_point, min_points, max_blocks, int(cover), int(seed), int(step), out.data.data_ptr(),
-              out.labels.data_ptr() if labels is not None else None, out.index.data_ptr(), out.block_cell.data_ptr(),
-              out.block_count.data_ptr(), out.block_room.data_ptr(), out.room_blocks.data_ptr(),
-              out.room_stats.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
-              torch.cuda.current_stream(dev).cuda_stream)
-    return out
+    return _blocks(True, data, room_start, labels, num_point, block, stride, min_points, max_blocks, seed, step, out, cover)
 
 
-class SceneVotes:
-    """Votes of block predictions for the rows of one room: votes int32 (num_rows, num_class) on the device.
-
-    add(pred, index): every element with 0 <= index < num_rows and 0 <= pred < num_class adds one vote -- each emitted
-    row votes, so a room row drawn twice votes twice; index -1 (filler blocks) and out-of-range predictions are
-    ignored.  Votes accumulate over calls (other steps, overlapping strides) until reset().  labels() -> (num_rows)
-    int32, the class with the most votes, the lowest on a tie, -1 without votes; counts() -> int64 device tensor
-    {voted rows, unvoted rows} of the last labels() (computed if there was none)."""
+class _RowTable:
+    """What SceneVotes and SceneScores share: a (num_rows, num_class) table on the device that add() accumulates into,
+    the labels and counts computed from it on demand (and kept until the table changes), and their workspace.  A subclass
+    names its table, the table's dtype, its class limit with the messages, and the two entry points of labels()."""
 
     def __init__(self, num_rows, num_class, device="cuda:0"):
-        _require(isinstance(num_rows, int) and 0 <= num_rows < 2 ** 31, "num_rows must be an integer in [0, 2^31)")
-        _require(isinstance(num_class, int) and num_class >= 1, "num_class must be a positive integer")
+        _require_int(num_rows, "num_rows must be an integer in [0, 2^31)", 0, 2 ** 31 - 1, allow_bool=True)
+        _require_int(num_class, self._CLASS_MESSAGE, 1, self._MAX_CLASS, allow_bool=True)
         self.device = torch.device(device)
-        _require(self.device.type == "cuda", "votes live on a HIP device (there is no CPU path)")
+        _require(self.device.type == "cuda", self._DEVICE_MESSAGE)
         self.num_rows, self.num_class = num_rows, num_class
-        self.votes = torch.zeros((num_rows, num_class), dtype=torch.int32, device=self.device)
+        setattr(self, self._TABLE, torch.zeros((num_rows, num_class), dtype=self._DTYPE, device=self.device))
         self._labels = torch.empty((num_rows,), dtype=torch.int32, device=self.device)
         self._counts = torch.zeros((2,), dtype=torch.int64, device=self.device)
-        nbytes = _lib.load().conv3p_scene_vote_labels_workspace_bytes(num_rows, num_class)
+        nbytes = getattr(_lib.load(), self._LABELS_ENTRY + "_workspace_bytes")(num_rows, num_class)
         self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if nbytes else None
         self._fresh = False
 
     def reset(self):
-        self.votes.zero_()
+        getattr(self, self._TABLE).zero_()
         self._fresh = False
-
-    def add(self, pred, index):
-        for name, t in (("pred", pred), ("index", index)):
-            _require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == self.device
-                     and t.is_contiguous(), "%s must be a contiguous int32 tensor on the votes' device" % name)
-        _require(pred.numel() == index.numel(), "pred and index must have as many elements")
-        self._fresh = False
-        if pred.numel() == 0 or self.num_rows == 0:
-            return
-        with torch.cuda.device(self.device):
-            _call(_lib.load().conv3p_scene_vote, pred.data_ptr(), index.data_ptr(), pred.numel(), self.num_rows,
-                  self.num_class, self.votes.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
 
     def labels(self):
         if self.num_rows and not self._fresh:
             ws = self._workspace
             with torch.cuda.device(self.device):
-                _call(_lib.load().conv3p_scene_vote_labels, self.votes.data_ptr(), self.num_rows, self.num_class,
-                      self._labels.data_ptr(), self._counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                      torch.cuda.current_stream(self.device).cuda_stream)
+                _call(getattr(_lib.load(), self._LABELS_ENTRY), getattr(self, self._TABLE).data_ptr(), self.num_rows,
+                      self.num_class, self._labels.data_ptr(), self._counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                      _stream(self.device))
             self._fresh = True
         return self._labels
 
@@ -401,7 +328,32 @@ class SceneVotes:
         return self._counts
 
 
-class SceneScores:
+class SceneVotes(_RowTable):
+    """Votes of block predictions for the rows of one room: votes int32 (num_rows, num_class) on the device.
+
+    add(pred, index): every element with 0 <= index < num_rows and 0 <= pred < num_class adds one vote -- each emitted
+    row votes, so a room row drawn twice votes twice; index -1 (filler blocks) and out-of-range predictions are
+    ignored.  Votes accumulate over calls (other steps, overlapping strides) until reset().  labels() -> (num_rows)
+    int32, the class with the most votes, the lowest on a tie, -1 without votes; counts() -> int64 device tensor
+    {voted rows, unvoted rows} of the last labels() (computed if there was none)."""
+
+    _TABLE, _DTYPE, _MAX_CLASS, _LABELS_ENTRY = "votes", torch.int32, float("inf"), "conv3p_scene_vote_labels"
+    _CLASS_MESSAGE = "num_class must be a positive integer"
+    _DEVICE_MESSAGE = "votes live on a HIP device (there is no CPU path)"
+
+    def add(self, pred, index):
+        for name, t in (("pred", pred), ("index", index)):
+            _require_tensor(t, "%s must be a contiguous int32 tensor on the votes' device" % name, torch.int32, dev=self.device)
+        _require(pred.numel() == index.numel(), "pred and index must have as many elements")
+        self._fresh = False
+        if pred.numel() == 0 or self.num_rows == 0:
+            return
+        with torch.cuda.device(self.device):
+            _call(_lib.load().conv3p_scene_vote, pred.data_ptr(), index.data_ptr(), pred.numel(), self.num_rows,
+                  self.num_class, self.votes.data_ptr(), _stream(self.device))
+
+
+class SceneScores(_RowTable):
     """Summed class probabilities of block predictions for the rows of one room: scores int64 (num_rows, num_class) on
     the device, in fixed point -- a vote adds llrintf(softmax(logits)[c] * SCALE) to its room row's class c, so the
     sums are exact and do not depend on the order of the rows or of the calls.
@@ -414,51 +366,26 @@ class SceneScores:
     sum of the probabilities."""
 
     SCALE = 1 << 30
+    _TABLE, _DTYPE, _MAX_CLASS, _LABELS_ENTRY = "scores", torch.int64, 128, "conv3p_scene_score_labels"
+    _CLASS_MESSAGE = "num_class must be an integer in [1, 128]"
+    _DEVICE_MESSAGE = "scores live on a HIP device (there is no CPU path)"
 
     def __init__(self, num_rows, num_class, device="cuda:0"):
-        _require(isinstance(num_rows, int) and 0 <= num_rows < 2 ** 31, "num_rows must be an integer in [0, 2^31)")
-        _require(isinstance(num_class, int) and 1 <= num_class <= 128, "num_class must be an integer in [1, 128]")
-        self.device = torch.device(device)
-        _require(self.device.type == "cuda", "scores live on a HIP device (there is no CPU path)")
-        self.num_rows, self.num_class = num_rows, num_class
-        self.scores = torch.zeros((num_rows, num_class), dtype=torch.int64, device=self.device)
+        _RowTable.__init__(self, num_rows, num_class, device)
         self.vote_stats = torch.zeros((2,), dtype=torch.int64, device=self.device)
-        self._labels = torch.empty((num_rows,), dtype=torch.int32, device=self.device)
-        self._counts = torch.zeros((2,), dtype=torch.int64, device=self.device)
-        nbytes = _lib.load().conv3p_scene_score_labels_workspace_bytes(num_rows, num_class)
-        self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if nbytes else None
-        self._fresh = False
 
     def reset(self):
-        self.scores.zero_()
+        _RowTable.reset(self)
         self.vote_stats.zero_()
-        self._fresh = False
 
     def add(self, logits, index):
-        _require(isinstance(logits, torch.Tensor) and logits.dtype == torch.float32 and logits.device == self.device
-                 and logits.is_contiguous() and logits.dim() >= 1 and logits.shape[-1] == self.num_class,
+        _require(_is_tensor(logits, torch.float32, dev=self.device, min_dim=1) and logits.shape[-1] == self.num_class,
                  "logits must be a contiguous float32 (..., num_class) tensor on the scores' device")
-        _require(isinstance(index, torch.Tensor) and index.dtype == torch.int32 and index.device == self.device
-                 and index.is_contiguous(), "index must be a contiguous int32 tensor on the scores' device")
+        _require_tensor(index, "index must be a contiguous int32 tensor on the scores' device", torch.int32, dev=self.device)
         _require(logits.numel() == index.numel() * self.num_class, "logits and index must have as many rows")
         self._fresh = False
         if index.numel() == 0 or self.num_rows == 0:
             return
         with torch.cuda.device(self.device):
             _call(_lib.load().conv3p_scene_vote_scores_f32, logits.data_ptr(), index.data_ptr(), index.numel(),
-                  self.num_rows, self.num_class, self.scores.data_ptr(), self.vote_stats.data_ptr(),
-                  torch.cuda.current_stream(self.device).cuda_stream)
-
-    def labels(self):
-        if self.num_rows and not self._fresh:
-            ws = self._workspace
-            with torch.cuda.device(self.device):
-                _call(_lib.load().conv3p_scene_score_labels, self.scores.data_ptr(), self.num_rows, self.num_class,
-                      self._labels.data_ptr(), self._counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                      torch.cuda.current_stream(self.device).cuda_stream)
-            self._fresh = True
-        return self._labels
-
-    def counts(self):
-        self.labels()
-        return self._counts
+                  self.num_rows, self.num_class, self.scores.data_ptr(), self.vote_stats.data_ptr(), _stream(self.device))

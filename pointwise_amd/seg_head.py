@@ -21,8 +21,7 @@ return the confusion matrix (conv3p_seg_confusion).  With the defaults every cal
 import torch
 
 from . import _lib
-from .conv3p_op import Conv3pInvalidArgument, Conv3pRuntimeError, _SFX, _call, _check_device, _require
-from .head import _workspace
+from ._host import _HEADS, _SFX, Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _require, _workspace
 
 REDUCTIONS = ("points", "nonzero_weights", "sum_weights")
 
@@ -202,7 +201,7 @@ class SegmentationHead:
         cw = self._class_weights_on(dev, dtype)
         total = torch.empty(2, dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            ws = _workspace(dev, lib.conv3p_seg_head_weighted_workspace_bytes(rows, C))
+            ws = _workspace(dev, lib.conv3p_seg_head_weighted_workspace_bytes(rows, C), _HEADS)
             _call(getattr(lib, "conv3p_seg_weight_total_" + _SFX[dtype][0]), labels32.data_ptr(), rows, C,
                   cw.data_ptr() if cw is not None else None, pw.data_ptr() if pw is not None else None,
                   total.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
@@ -232,7 +231,7 @@ class SegmentationHead:
         counts = torch.empty(2 + 3 * C, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = _workspace(dev, lib.conv3p_seg_head_weighted_workspace_bytes(rows, C))
+            ws = _workspace(dev, lib.conv3p_seg_head_weighted_workspace_bytes(rows, C), _HEADS)
             _call(getattr(lib, "conv3p_seg_head_weighted_" + sfx), act.data_ptr(), labels.data_ptr(), rows, C,
                   cw.data_ptr() if cw is not None else None, pw.data_ptr() if pw is not None else None,
                   self.label_smoothing, real(scale), den.data_ptr() if den is not None else None,
@@ -241,7 +240,7 @@ class SegmentationHead:
             conf = None
             if confusion:
                 conf = torch.empty((C, C), dtype=torch.int64, device=dev)
-                ws = _workspace(dev, lib.conv3p_seg_confusion_workspace_bytes(rows, C))
+                ws = _workspace(dev, lib.conv3p_seg_confusion_workspace_bytes(rows, C), _HEADS)
                 _call(lib.conv3p_seg_confusion, labels.data_ptr(), pred.data_ptr(), rows, C, conf.data_ptr(), ws.data_ptr(),
                       ws.numel(), stream)
         self._counts = counts
