@@ -1,5 +1,5 @@
 """Which kernel family serves a call (-m gpu): one explicit row per (dtype, channel shape, tap count) cell, each run
-undilated (1, 1, 1) and dilated (2, 2, 2).  plan_backward / plan_forward in conv3p_abi.hip, the one place the table
+undilated (1, 1, 1) and dilated (2, 2, 2).  plan_backward / plan_forward in conv3p_abi_routes.hpp, the one place the table
 is stated, choose among the register path (dense G or populated rows; the fp64 36 -> 13 column split), the matrix-core kernels (conv3p_deep.hpp, blocks above
 256 channels), the fp64 channel blocks and the generic thread-per-pair kernels (global float atomics).  The choice
 depends on dtype, channels, taps, dilation, the density hint and -- it must not -- on how much scratch the buffer has.

@@ -1,6 +1,6 @@
 """developer (ON THE GPU BOX, with a -DCONV3P_DEV_WALK_STATS build: CONV3P_HIP_LIB=devlibs/lib_walkstats.so): lane use of
 the list-walking kernels on the cfg2 and cfg4 workloads -- one forward pass of each stack; the library prints one
-`walk_stats` line per forward launch to stderr (see dev_walk_stats in conv3p_abi.hip)."""
+`walk_stats` line per forward launch to stderr (see dev_walk_stats in conv3p_abi_search.hpp)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
