@@ -1029,7 +1029,15 @@ int conv3p_grid_segment_geometry(const float *voxel_data, int K, const int32_t *
  *                         dx (M, K) = dz . W^T  with dz = dy * act'(y);  dx and db may be NULL.
  * W is streamed exactly once per pass (it is the 151 MB object of the model); products are exact fp32 on the
  * matrix cores; results are bitwise reproducible.  Constraints: N % 8 == 0, N <= 1024, M <= 128
- * (CONV3P_ERR_UNSUPPORTED otherwise).  Scratch from conv3p_fc_workspace_bytes.
+ * (CONV3P_ERR_UNSUPPORTED otherwise).  The backward (and conv3p_fc_backward_step_f32) keeps all of dz in LDS for the dW
+ * pass, 2 STEPS rows of N + 1 floats within 160 KiB with STEPS = 16, 32, 64 for M <= 32, <= 64, <= 128, and so also
+ * refuses (CONV3P_ERR_UNSUPPORTED, before anything is launched)
+ *     33 <= M <= 64   with N > 632
+ *     65 <= M <= 128  with N > 312
+ * which the forward serves.  Scratch from conv3p_fc_workspace_bytes: 0 where the FORWARD's constraints fail; it does
+ * not reflect the backward's two regions (it is non-zero there).
+ * A non-finite input reaches exactly the outputs whose sums it enters (padded rows, columns and K-steps are zero on
+ * both operands: no 0 * Inf).  M == 0: nothing forward; the backward writes dW = 0 and, when given, db = 0.
  * ------------------------------------------------------------------------------------------- */
 size_t conv3p_fc_workspace_bytes(int M, int K, int N);
 int conv3p_fc_forward_f32(const float *x, const float *W, const float *b, int M, int K, int N, int act, float *y,

@@ -341,7 +341,11 @@ int conv3p_fc_backward_f32(const float *x, const float *W, const float *y, const
 {
     if (M < 0 || K < 0 || N < 0 || (act != 0 && act != 1)) return CONV3P_ERR_INVALID_ARGUMENT;
     if ((size_t)K * N == 0) return CONV3P_OK;
-    if (M == 0) return zero_async(dW, (size_t)K * N * 4, static_cast<hipStream_t>(stream));
+    if (M == 0) {                                                       // empty sums: dW = 0 and db = sum_m dz = 0
+        if (!dW) return CONV3P_ERR_INVALID_ARGUMENT;
+        TRY(zero_async(dW, (size_t)K * N * 4, static_cast<hipStream_t>(stream)));
+        return db ? zero_async(db, (size_t)N * 4, static_cast<hipStream_t>(stream)) : CONV3P_OK;
+    }
     if (!x || !W || !dy || !dW || (act && !y)) return CONV3P_ERR_INVALID_ARGUMENT;
     FcPlan p;
     if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;

@@ -247,8 +247,9 @@ __global__ __launch_bounds__(512) void fc_dw_kernel(const float *__restrict__ x,
     float a[STEPS];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
-        const int m = min(2 * s + half, M - 1);
-        a[s] = x[(size_t)m * K + k];                                    // rows past M meet dz == 0
+        const int m = 2 * s + half;                                     // unconditional load, clamped to the last row;
+        const float v = x[(size_t)min(m, M - 1) * K + k];               // rows past M meet dz == 0 in LDS and are zeroed
+        a[s] = m < M ? v : 0.0f;                                        // here as well (0 * Inf)
     }
     for (int nb = 0; nb < N; nb += 32) {
         const int n = min(nb + (lane & 31), N - 1);

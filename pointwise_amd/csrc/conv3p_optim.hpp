@@ -163,8 +163,9 @@ __global__ __launch_bounds__(512) void fc_dw_step_kernel(const float *__restrict
     float a[STEPS];
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
-        const int m = min(2 * s + half, M - 1);
-        a[s] = x[(size_t)m * K + k];                                    // rows past M meet dz == 0
+        const int m = 2 * s + half;                                     // unconditional load, clamped to the last row;
+        const float v = x[(size_t)min(m, M - 1) * K + k];               // rows past M meet dz == 0 in LDS and are zeroed
+        a[s] = m < M ? v : 0.0f;                                        // here as well (0 * Inf)
     }
     float *Wb = W + (size_t)kb * N, *ab = accum + (size_t)kb * N;     // scalar bases; 16 lane offsets below 32 N serve both
     unsigned off[16];
@@ -193,6 +194,10 @@ __global__ __launch_bounds__(512) void fc_dw_step_kernel(const float *__restrict
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], bv[s], acc, 0, 0, 0);
+        // vmcnt(0), stated ONCE: the operands were loaded under conditions, so hipcc cannot count them and would
+        // otherwise drain the memory queue -- the previous row's stores included -- before each of the 16 updates
+        // below and at the head of every block (fused step, model shape: 166 us against 132 us)
+        __builtin_amdgcn_s_waitcnt(0x0f70);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int kr = kb + (r & 3) + 8 * (r >> 2);

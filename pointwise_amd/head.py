@@ -65,7 +65,13 @@ def fully_connected(x, W, b=None, selu=True):
 
 
 def fully_connected_grad(x, W, y, dy, selu=True, need_dx=True, dW_out=None, db_out=None):
-    """Gradients of fully_connected given its OUTPUT y and dL/dy -> (dx or None, dW, db)."""
+    """Gradients of fully_connected given its OUTPUT y and dL/dy -> (dx or None, dW, db).
+
+    Narrower than the forward (N % 8 == 0, N <= 1024, M <= 128): the dW pass keeps all of dz in LDS, so batches of
+    33 .. 64 rows need N <= 632 and batches of 65 .. 128 rows N <= 312 (Conv3pRuntimeError "unsupported" otherwise,
+    before anything is launched; conv3p_fc_workspace_bytes does not reflect this).  A ClassificationHead with
+    hidden = 512 therefore runs forward at a batch of 65 .. 128 clouds and fails in backward; MomentumOptimizer.
+    fused_fc_step has the same limits.  An empty batch (M = 0) gives dW = 0 and db = 0."""
     lib = _lib.load()
     _check_fc(x, W, None)
     dev = _check_device(x, W, y, dy)
