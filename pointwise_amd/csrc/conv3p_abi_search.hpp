@@ -62,10 +62,10 @@ template <typename SlotT> inline const uint32_t *sched_of(const SlotT &S)
 // mean pre-filter hits per point below which a slot's lists count as SHORT (populated-rows backward for the dilated narrow
 // layers): Conv3pStack.tune()'s threshold of 32 neighbours per point plus the pre-filter's ~10 % of false positives
 // The regime word only matters for DILATED narrow layers (undilated ones never take the populated-rows kernel).  Of a
-// dilated stencil's hits the window tables of the fused search let through ~1.5 per neighbour (a third are false
-// positives, see fused_compacts), the tile-pair pre-filter of search_tile ~1.1: the same 32 neighbours per point are 48
-// hits there and 35 here.
-constexpr unsigned long long kShortListsPerPoint = 35, kShortListsPerPointFused = 48;
+// dilated stencil's hits the window tables of the fused search let through 1.24 per neighbour (measured, see
+// fused_compacts), the tile-pair pre-filter of search_tile ~1.1: the same 32 neighbours per point are
+// kFHitsOf32Neighbours = 40 hits there and 35 here.
+constexpr unsigned long long kShortListsPerPoint = 35, kShortListsPerPointFused = kFHitsOf32Neighbours;
 template <typename T> SchedJob make_sched_job(const Call<T> &c, int slot, bool fused)
 {
     const auto &S = c.L.slot[slot];

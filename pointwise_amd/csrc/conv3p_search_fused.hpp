@@ -32,7 +32,7 @@ namespace conv3p {
 
 constexpr int kFR = 16;                        // base buckets per voxel
 constexpr int kFK = 96;                        // buckets per axis in a tile's table (6 voxels at the base resolution)
-constexpr int kFEntries = 116;                 // >= kFK + (kFR + 2) + 1 window entries per axis
+constexpr int kFEntries = 116;                 // >= kFK + (kFR + 1) + 1 = 114 window entries per axis (116 keeps the 16-byte rows)
 constexpr int kFHeader = 3 * kFEntries;        // u64 index of the header: {tmin.x, tmin.y}, {tmin.z, e}, {all valid}, pad
 constexpr int kFTableU64 = kFHeader + 4;       // 352 x 8 B = 2816 B = 176 x 16 B
 constexpr int kFMaxExt = 8;                    // taps per axis the look-up loops take
@@ -56,9 +56,16 @@ __device__ __forceinline__ bool finite3(float x, float y, float z)
 // ---------------------------------------------------------------------------------------------------------------
 // Tables.  One wave per tile.  bucket(v) = floor((float(v) - tmin) * inv16) >> e, tmin = the tile's own minimum over
 // its finite points, e the smallest shift that brings every point of the tile into [0, kFK).  Window of k:
-// buckets k .. k + ws - 1, ws = (16 >> e) + 2.  Entry j of an axis holds the window of k = j - ws, so that entry 0
-// (k <= -ws) and entries >= kFK + ws (k >= kFK) are empty.
+// buckets k .. k + ws - 1, ws = fused_window(e): (16 >> e) + 1 while a voxel is a whole number of buckets (e <= 4: a
+// one-voxel interval that starts in bucket k ends in bucket k + (16 >> e); the look-up adds a second window where the
+// rounding fuzz reaches the bucket after that, see fused_mask), 2 at the coarser levels (a voxel is a fraction of a
+// bucket and ends in the same bucket or the next).  Entry j of an axis holds the window of k = j - ws, so that entry 0
+// (k <= -ws) and entries >= kFK + ws (k >= kFK) are empty: the last one a point reaches is kFK - 1 + ws <= 112, entries
+// 113 .. kFEntries - 1 stay empty for the look-ups clamped from above.
 // ---------------------------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int fused_window(int es) { return (kFR >> es) >= 1 ? (kFR >> es) + 1 : 2; }
+static_assert(kFEntries >= kFK + fused_window(0) + 1 && kFEntries % 2 == 0, "window entries per axis");
+
 template <typename T>
 __global__ __launch_bounds__(256) void tile_tables_kernel(const PointRec<T> *__restrict__ pts, int ntiles, float inv16,
                                                           unsigned long long *__restrict__ tables,
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(256) void tile_tables_kernel(const PointRec<T> *__r
         while (e <= kFMaxE && floor_i32(ext) >> e > kFK - 1) ++e;
     }
     const int es = e > 31 ? 31 : e;
-    const int ws = (kFR >> es) + 2;
+    const int ws = fused_window(es);
     int beta[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -201,28 +208,47 @@ __device__ __forceinline__ uint64_t tiles_meeting(const T *__restrict__ cloud_bo
 }
 
 // Pre-filter hit mask for the lane's centre against the candidate tile staged in `tab` (general filter extents).
-//   g[a] = (float(p) - tmin) * inv16 (the candidate side's own fp32 operations), gs[a] = g[a] - slack + (ws << e).
+//   g[a] = (float(p) - tmin) * inv16 (the candidate side's own fp32 operations), gs[a] = g[a] - slack + (ws << e),
+//   fz[a] = 2.5 slack, ws = fused_window(e), w = 16 >> e.
 // Superset argument.  A candidate accepted by the exact test for tap k of axis a satisfies, in real numbers,
 //   v - p in [(k step - full/2) voxel - eta, (k step + 1 - full/2) voxel + eta],  eta = a few ulps of the coordinates.
 // Its bucket coordinate b16(v) = floor(fl(fl(v - tmin) inv16)) is monotone in v and within D = ~1.5 ulp(M) inv16 +
 // 1.2e-7 |r| of the real r(v) = (v - tmin) 16 / voxel; g is within the same D of r(p).  With
 //   slack >= 2 D + eta 16 / voxel  (here 1e-3 + 4e-6 (|p| inv16 + |g|) >= 1e-3 + 2e-6 ((|p| + |tmin|) inv16 + |g|): ~17 ulps)
-// x = g + clo - slack <= r(lower edge) - D, hence floor(x) <= b16(v): no accepted candidate lies below the window.
-// Above: b16(v) <= floor(r(lower edge) + 16 + fuzz) <= floor(x) + 16 + ceil(fuzz) with fuzz <= 2.5 slack <= 2^e / 2
-// (enforced: a larger slack takes every valid candidate), and ((k16 + 16 + ceil(fuzz)) >> e) - (k16 >> e) <= ws - 1
-// for ws = (16 >> e) + 2.  Invalid / non-finite centres get an empty mask, non-finite candidates are in no window.
+// and x = g + clo - slack, clo = (k step - full/2) 16 the interval's lower edge relative to the centre:
+// Lower side.  x <= r(lower edge) - D, hence floor(x) <= b16(v) and k0 = floor(x) >> e <= bucket(v): no accepted
+//   candidate lies below the window of k0.
+// Upper side.  r(v) <= r(p) + clo + 16 + eta 16 / voxel and r(p) <= g + D, so b16(v) <= floor(r(v) + D) <=
+//   floor(x + 16 + 2 slack).  The look-up forms xh = fl(x + fz): the spare half slack (8 ulps of the operands) pays
+//   for the roundings of fz and of the sum, so b16(v) <= floor(xh) + 16.  For e <= 4 a voxel is w whole buckets,
+//   (floor(xh) + 16) >> e = (floor(xh) >> e) + w exactly, and with kh = floor(xh) >> e
+//       bucket(v) in [k0, kh + w],   kh in {k0, k0 + 1}  because fz <= 2^e / 2 (enforced: a larger slack takes every
+//   valid candidate).  The window of k0 is [k0, k0 + w] -- 17 buckets at e = 0 -- and covers the range whenever kh = k0.
+//   kh = k0 + 1 needs the fuzz to carry x over a bucket boundary (at e = 0: frac(x) + fz >= 1; fz is a few 1e-3 at the
+//   models' coordinates); only then can bucket k0 + w + 1 hold an accepted candidate, and it is the last bucket of the
+//   window of kh: the look-up ORs the entries of k0 and kh.  The second entry is read when any lane of the wave has
+//   kh != k0 for that look-up (the other lanes read their first entry again); otherwise the reads are those of k0 alone.
+// Coarse levels (e >= 5, ws = 2).  16 + ceil(fz) <= 16 + 2^e / 2 <= 2^e, so bucket(v) <= (floor(x) + 2^e) >> e = k0 + 1:
+//   the window [k0, k0 + 1] of the first entry is enough; the second entry, where read, only adds bucket kh + 1.
+// Entries.  The table holds the window of k at entry k + ws; gs carries the offset ws 2^e (a float sum whose rounding
+//   the slack covers like the others), clamped indices fall on entry 0 or on entries >= kFK + ws, all empty.
+// Invalid / non-finite centres get an empty mask, non-finite candidates are in no window.
 template <typename T>
-__device__ __forceinline__ uint64_t fused_mask(const FusedJob<T> &job, const unsigned long long *tab, const float *gs, int e)
+__device__ __forceinline__ uint64_t fused_mask(const FusedJob<T> &job, const unsigned long long *tab, const float *gs, const float *fz,
+                                               bool qvalid, int e)
 {
     uint64_t H = ~0ull;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         uint64_t A = 0;
         const unsigned long long *ta = tab + a * kFEntries;
-        for (int k = 0; k < job.st.ext[a]; ++k) {
-            int j = floor_i32(gs[a] + job.clo[a][k]) >> e;
+        for (int k = 0; k < job.st.ext[a]; ++k) {   // (uniform: the __any below is met by the whole wave)
+            const float x = gs[a] + job.clo[a][k];
+            int j = floor_i32(x) >> e, jh = floor_i32(x + fz[a]) >> e;
             j = j < 0 ? 0 : (j > kFEntries - 1 ? kFEntries - 1 : j);
+            jh = jh < 0 ? 0 : (jh > kFEntries - 1 ? kFEntries - 1 : jh);
             A |= ta[j];
+            if (__any(qvalid && jh != j)) A |= ta[jh];
         }
         H &= A;
     }
@@ -320,17 +346,23 @@ __device__ __forceinline__ void fused_resolve(const Stencil<T> &st, T rvoxel, co
 
 typedef int int4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
-// Which stencils' lists are squeezed after pass 2 (see the compaction stage of search_fused_kernel): the dilated ones.
-// A window of 16 + 2 buckets per one-voxel interval accepts ~(18/16)^3 = 1.42 x the volume: a third of a dilated
-// stencil's hits are false positives, but only a ninth of an undilated one's (its three intervals per axis merge into
-// one of 48 + 2 buckets: 12 % on the ModelNet-like clouds, 9 % on the rooms) -- there the pass costs more than the
-// walkers' shorter lists give back.
-// Undilated stencils are squeezed where the lists are long (more than 48 hits per centre on average over the tile: the
-// rooms, whose stride-1 lists serve two layers of the segmentation model; cfg4 step 1.380 -> 1.358 ms) -- the pass costs
-// per tile, the walkers save per record.  Decided per tile from its own hit count: the same for any batch it sits in.
+// Which tiles' lists are squeezed after pass 2 (see the compaction stage of search_fused_kernel).
+// A window of 16 + 1 buckets per one-voxel interval accepts ~(17/16)^3 = 1.20 x the volume.  Measured
+// (profiles/window17_walk_stats.txt): 1.24 hits per neighbour on the dilated stencils of the ModelNet-like clouds
+// (27.3 / 23.0 / 19.7 hits per point for 22.0 / 18.6 / 16.0 neighbours at strides 2 - 4), 1.20 on the rooms -- a fifth
+// of the hits are false positives (windows of 18 buckets: 1.52, a third) -- and 1.07 / 1.05 on the undilated stencil,
+// whose three intervals per axis merge into one of 48 + 1 buckets.  The pass costs per tile, the walkers save per
+// record: with a third of the records dead it paid on every dilated stencil, with a fifth it no longer does on the
+// models' short lists (cfg2 headline, six runs each, alternated: 0.3888 ms with every dilated list squeezed, 0.3831 with
+// none; profiles/window17_after.txt).  What is left is the rule for long lists, whatever the stencil: a tile is squeezed
+// when it holds more hits per centre than 32 neighbours bring (the rooms at every stride; their stride-1 lists serve two
+// layers of the segmentation model).  Decided per tile from its own hit count: the same for any batch it sits in.
+// kFHitsOf32Neighbours = 32 neighbours x 1.24 hits per neighbour = 39.7: also the mean hits per point up to which
+// tile_sched_kernel calls a slot's lists SHORT (kShortListsPerPointFused, conv3p_abi_search.hpp).
+constexpr uint32_t kFHitsOf32Neighbours = 40;
 template <typename T> __device__ __forceinline__ bool fused_compacts(const Stencil<T> &st, uint32_t tile_hits)
 {
-    return !(CONV3P_DEV_FUSED_ABLATE & 16) && (st.step[0] * st.step[1] * st.step[2] > 1 || tile_hits > 48u * 64u);
+    return !(CONV3P_DEV_FUSED_ABLATE & 16) && tile_hits > kFHitsOf32Neighbours * 64u;
 }
 
 // EXT3: the stencil has 3 taps per axis (all layers of the reference's models).  Tap 1's acceptance interval is then
@@ -405,7 +437,7 @@ __global__ __launch_bounds__(256) void search_fused_kernel(const PointRec<T> *__
         ulo[a] = (T)((double)red[a] - st.half[a]);
         uhi[a] = (T)((double)red[3 + a] + st.half[a]);
     }
-    const float s16[3] = {(float)(kFR * st.step[0]), (float)(kFR * st.step[1]), (float)(kFR * st.step[2])};
+    const int S16[3] = {kFR * st.step[0], kFR * st.step[1], kFR * st.step[2]};   // buckets between neighbouring taps
 
     // The wave's candidate tiles: tile ct belongs to wave ct % 4.  visit(ct, next ct of this wave in the block or -1)
     auto for_my_tiles = [&](auto &&visit) {
@@ -444,36 +476,58 @@ __global__ __launch_bounds__(256) void search_fused_kernel(const PointRec<T> *__
                                __builtin_bit_cast(float, (uint32_t)h1)};
         const int e = (int)(uint32_t)(h1 >> 32);
         const int es = e > kFMaxE ? kFMaxE : e;
-        const int ws = (kFR >> es) + 2;
-        float gs[3], smax = 0.0f;
+        const int ws = fused_window(es);
+        float gs[3], fz[3], smax = 0.0f;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const float g = (pf[a] - tmin[a]) * inv16;
             const float slack = __builtin_fmaf(4.0e-6f, fabsf(g), q0[a]);
             smax = fmaxf(smax, slack);
             gs[a] = (g - slack) + (float)(ws << es);
+            fz[a] = 2.5f * slack;
         }
         // the fuzz must stay below half a (scaled) bucket; coarser tables than 2^kFMaxE: everything is a candidate
         const bool wide = e > kFMaxE || __any(qvalid && !(smax <= 0.2f * (float)(1 << es)));
-        auto entry = [&](float x) {
-            int j = floor_i32(x) >> es;
+        // entry of base bucket i + d (i a floor, d a whole number of buckets; unsigned sum: the saturated floor of an
+        // invalid lane may wrap, to a clamped -- empty -- entry like any other)
+        auto entry = [&](int i, int d) {
+            const int j = (int)((uint32_t)i + (uint32_t)d) >> es;
             return j < 0 ? 0 : (j > kFEntries - 1 ? kFEntries - 1 : j);
         };
         uint64_t h;
         if (wide) {
             h = tab[kFHeader + 2];
         } else if (EXT3) {
+            // tap 1's look-up coordinate x1 and its fuzzed twin; taps 0 / 2 lie a whole S = 16 step buckets below /
+            // above, floor(x1 -+ S) = floor(x1) -+ S: one floor per axis and twin.  The nine first entries are read
+            // together; `far` = the fuzz carries this lane's x1 into the next (scaled) bucket -- for e <= 4 S is a
+            // whole number of scaled buckets, the same holds for taps 0 and 2 -- and only a wave with such a lane reads
+            // the second entries of that axis (see fused_mask).
             uint64_t A[3];
+            int ih[3];
+            bool far[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 const float x1 = gs[a] - (float)(kFR / 2);
+                const int i1 = floor_i32(x1);
+                ih[a] = floor_i32(x1 + fz[a]);
+                far[a] = ((i1 ^ ih[a]) >> es) != 0;
                 const unsigned long long *ta = tab + a * kFEntries;
-                const uint64_t r0 = ta[entry(x1 - s16[a])], r1 = ta[entry(x1)], r2 = ta[entry(x1 + s16[a])];
+                const uint64_t r0 = ta[entry(i1, -S16[a])], r1 = ta[entry(i1, 0)], r2 = ta[entry(i1, S16[a])];
                 A[a] = r0 | r1 | r2;
+            }
+            if (__any(qvalid && (far[0] | far[1] | far[2]))) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    if (!__any(qvalid && far[a])) continue;
+                    const unsigned long long *ta = tab + a * kFEntries;
+                    const uint64_t r0 = ta[entry(ih[a], -S16[a])], r1 = ta[entry(ih[a], 0)], r2 = ta[entry(ih[a], S16[a])];
+                    A[a] |= r0 | r1 | r2;
+                }
             }
             h = A[0] & A[1] & A[2];
         } else {
-            h = fused_mask(job, tab, gs, es);
+            h = fused_mask(job, tab, gs, fz, qvalid, es);
         }
         return qvalid ? h : 0ull;
     };
@@ -609,10 +663,11 @@ __global__ __launch_bounds__(256) void search_fused_kernel(const PointRec<T> *__
     __threadfence_block();
     __syncthreads();
 
-    // ---- compaction (round 5).  The tables are a superset filter: on the models' dilated stencils a third of the
-    //      pre-filter hits are false positives (window of 18 buckets where 16 decide, on three axes), stored above as
-    //      kNoTap records that every list-walking kernel then steps over -- a third of the forward's and backward's steps.
-    //      Here every centre's list is squeezed to its live records (forward tap present), order kept, in place: wave w
+    // ---- compaction (round 5).  The tables are a superset filter: on the models' dilated stencils a fifth of the
+    //      pre-filter hits are false positives (window of 17 buckets where 16 decide, on three axes), stored above as
+    //      kNoTap records that every list-walking kernel then steps over.  Where the tile's lists are long
+    //      (fused_compacts) every centre's list is squeezed to its live records (forward tap present), order kept, in
+    //      place: wave w
     //      takes the contiguous run of the centres 16w .. 16w + 15, lane = record, 64 at a time; a live record's place
     //      in its centre's list is the number of live records of the same centre before it (one ballot; the centre's
     //      first lane in the chunk from its slot offset; a count carried over when a list straddles two chunks).  A
