@@ -1,4 +1,6 @@
 """Shared helpers of the parity tests: tolerances, case generation, HIP-vs-oracle comparison."""
+import ctypes
+
 import numpy as np
 
 from pointwise_amd import synth
@@ -75,3 +77,25 @@ def exact_from_oracle_lists(cloud, X, W, dY, stride, voxel):
         dX += G @ W64[f].T
         dW[f] = X64.T @ G
     return y, dX, dW.reshape(W.shape)
+
+
+# Which kernel family served a call, read from the library's launch profile (tests/test_dispatch_map.py,
+# tests/test_exact_families.py): "register", "matrix-core", "f64-blocks" or "generic".
+def _read_profile(lib):
+    seen = {}
+    for k in range(lib.conv3p_profile_kinds()):
+        n = ctypes.c_uint64(0)
+        lib.conv3p_profile_read(k, ctypes.byref(n), None)
+        seen[lib.conv3p_profile_name(k).decode()] = n.value
+    lib.conv3p_profile_reset()
+    return seen
+
+
+def _family(seen, forward):
+    if seen.get("generic_forward_kernel" if forward else "generic_backward_kernel", 0):
+        return "generic"
+    if seen.get("deep_gemm_kernel", 0) or seen.get("deep_gemm_bf16_kernel", 0):
+        return "matrix-core"
+    if seen.get("transpose_filter_kernel", 0):   # (the fp64 blocks' filter packing; the matrix-core path is tested first)
+        return "f64-blocks"
+    return "register" if seen.get("forward_kernel" if forward else "backward_kernel", 0) else "none"

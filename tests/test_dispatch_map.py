@@ -11,15 +11,13 @@ The boundaries: fp32 narrow shapes stay on the register pa
 beyond), fp32 36 -> 13 up to 32 taps and on the matrix-core kernels for 33 .. 64, fp32 padded shapes on the matrix-core
 kernels up to 64 taps; fp64 on the register path while its dense G fits LDS, channel blocks after that (backward up to
 115 taps, forward up to 92), generic beyond."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle
 from pointwise_amd import _lib, conv3p_op as op
-from tests.parity_util import TOL, make_case, rel_err
+from tests.parity_util import TOL, _family, _read_profile, make_case, rel_err
 
 pytestmark = pytest.mark.gpu
 VOX = 0.1
@@ -120,26 +118,6 @@ def dev():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     _lib.load()
     return torch.device("cuda:0")
-
-
-def _read_profile(lib):
-    seen = {}
-    for k in range(lib.conv3p_profile_kinds()):
-        n = ctypes.c_uint64(0)
-        lib.conv3p_profile_read(k, ctypes.byref(n), None)
-        seen[lib.conv3p_profile_name(k).decode()] = n.value
-    lib.conv3p_profile_reset()
-    return seen
-
-
-def _family(seen, forward):
-    if seen.get("generic_forward_kernel" if forward else "generic_backward_kernel", 0):
-        return G
-    if seen.get("deep_gemm_kernel", 0) or seen.get("deep_gemm_bf16_kernel", 0):
-        return MC
-    if seen.get("transpose_filter_kernel", 0):   # (the fp64 blocks' filter packing; the matrix-core path is tested first)
-        return FB
-    return R if seen.get("forward_kernel" if forward else "backward_kernel", 0) else "none"
 
 
 def _run(dev, case, s, cache):
