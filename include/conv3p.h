@@ -957,6 +957,71 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   and 64-bit integer adds, one set per run of equal segment among the consecutive voxels of a wave; no float atomics;
  *   everything but G6 is bitwise independent of the launch geometry and of thread order, and G6 is a function of the exact
  *   moments alone.
+ *
+ * conv3p_grid_segment_adjacency:  which segments touch -- the region adjacency graph of a segmentation in CSR form, with
+ *   exact integer contact statistics per edge and per segment (pointwise_amd/csrc/conv3p_grid_adjacency.hpp;
+ *   tests/grid_adjacency_ref.py restates it in numpy).  neigh int32 (M, 27) as conv3p_grid_neighbors writes it; segment
+ *   int32 (M) and seg_stats as conv3p_grid_segments (or conv3p_grid_merge_segments) writes them -- any array with values
+ *   in [-1, S) is legal; grid_stats the subsampling's stats; connectivity 6, 18 or 26, independent of the connectivity
+ *   that made the segments; max_edges >= 0, the rows of the edge arrays.
+ *    E1. ne = min(max(grid_stats[0], 0), M) and S = min(max(seg_stats[0], 0), M), both read ON THE DEVICE.  Voxel v < ne is
+ *        a MEMBER of a = segment[v] when 0 <= a < S; any other word makes v a member of nothing.
+ *    E2. A CONTACT from a to b is a pair (v, t): v a member of a, t a tap of the connectivity (the taps of S2),
+ *        w = neigh[v][t] with 0 <= w < ne, w a member of b, and b != a.
+ *    E3. The directed EDGE (a, b) exists when there is at least one contact from a to b.  The table is symmetric below ne,
+ *        so (v, t) is a contact a -> b exactly when (w, 26 - t) is a contact b -> a: edges come in pairs and E, the number
+ *        of directed edges, is even.
+ *    E4. Per edge e, the edges in ascending (a, b), int32 (max_edges) each: edge_src[e] = a; edge_dst[e] = b;
+ *        edge_contacts[e] the number of contacts a -> b (the twin's value); edge_voxels[e] the number of distinct v in a
+ *        with a contact to b -- the border of a towards b, not symmetric; edge_offset int32 (max_edges, 3) the sum over
+ *        the contacts of the tap's (dx, dy, dz), the exact negative of the twin's (a positive dz: b lies above a);
+ *        edge_twin[e] the index of edge (b, a).  Contacts are at most 26 * 2^24, so int32 holds every sum.
+ *    E5. adj_start int32 (M + 1): adj_start[s] is the number of edges with src < s for s <= S, and E for s > S.  Row s of
+ *        the CSR is [adj_start[s], adj_start[s + 1]) and its edge_dst ascends.
+ *    E6. seg_border int32 (M, 4), for s < S counts of the (member, tap) pairs of s, 0 for s >= S, whatever max_edges:
+ *        {contacts to any other segment; pairs whose neighbour is a voxel below ne that is a member of nothing; pairs with
+ *        no neighbour (neigh < 0 or >= ne); members with at least one pair of these three kinds -- the surface voxels}.
+ *    E7. B is the number of distinct (member voxel, foreign segment) pairs, the sum of edge_voxels over all edges; it is
+ *        always computed and E <= B <= 26 M.  If E <= max_edges: rows e >= E hold src = dst = twin = -1 and 0, and
+ *        adj_stats int64 (8) = {E, B, S, total contacts, largest degree, largest edge_contacts, 0, 0}.  Otherwise
+ *        (OVERFLOW): every edge row is filler, adj_start is all 0, seg_border is still exact and adj_stats = {-1, B, S,
+ *        total contacts, 0, 0, 1, 0}; a caller retries with max_edges = B, which always fits.  Every output word is
+ *        written by every call.
+ *   Status, in this order, all before any launch: M < 0, connectivity not 6, 18 or 26, max_edges < 0:
+ *   CONV3P_ERR_INVALID_ARGUMENT; M == 0: CONV3P_OK, nothing launched and nothing written; any pointer NULL (the six edge
+ *   arrays may be NULL with max_edges == 0): CONV3P_ERR_INVALID_ARGUMENT; M or max_edges > 2^31 - 1:
+ *   CONV3P_ERR_UNSUPPORTED; workspace NULL or smaller than conv3p_grid_adjacency_scratch_bytes(M, max_edges):
+ *   CONV3P_ERR_INVALID_ARGUMENT.  The workspace is 18 words per row of max_edges (an open-addressed table of
+ *   2 max_edges + 64 slots, a 64-bit key and five counters each, and the two key buffers of the sort) plus a few KiB and
+ *   a histogram of 256 words per 4096 edges: a function of max_edges, nothing per voxel and no record per contact.
+ *   5 + 6 b launches with b the bytes of M - 1 (11, 17, 23, 29 for M <= 2^8, 2^16, 2^24, beyond): fixed by M whatever
+ *   the data; the radix passes above the top byte of S - 1 return at once.  No host read; no float arithmetic; the only
+ *   atomics are the 64-bit CAS that claims a slot, int32 adds and maxima, and the 64-bit adds of three counters.  Every
+ *   probe loop is bounded by the table's size and none waits for a thread.  Slot order is not reproducible; the outputs
+ *   are: the claimed keys are sorted before anything is written.
+ *
+ * conv3p_grid_merge_segments:  any set of segment pairs collapsed by union-find into a new segmentation.  segment,
+ *   seg_root, seg_size, seg_rows, seg_label, seg_stats of a segmentation numbered by S3; pair_a, pair_b int32 (P), P >= 0;
+ *   select int32 (P) or NULL.
+ *    U1. Pair p is ACTIVE when select is NULL or select[p] != 0, and 0 <= pair_a[p], pair_b[p] < S.  So the filler rows
+ *        of an adjacency (-1) are ignored, one direction of an edge is enough, and a == b joins nothing.
+ *    U2. A GROUP is a class of the transitive closure of the active pairs over the segments 0 .. S-1.  Its root segment
+ *        is its lowest number; groups are numbered 0 .. S'-1 in ascending root segment -- by S3 in ascending root voxel,
+ *        so the result is again numbered by S3.
+ *    U3. Outputs, int32 (M) each: seg_map[s] the group of s, -1 for s >= S; segment_out[v] = seg_map[segment[v]] where
+ *        0 <= segment[v] < S, -1 otherwise; root_out the seg_root of the root segment; size_out and rows_out the sums over
+ *        the group; label_out the seg_label of the member with the largest seg_size, the lowest number on a tie; rows
+ *        past S' as S4 fills them.  stats_out int32 (8) has S4's layout: entry 0 is S', 1-3 are copied from seg_stats,
+ *        4-5 are the new maxima.
+ *    U4. merge_stats int32 (4) = {S', S, active pairs with a != b, groups of more than one segment}.
+ *    U5. With no active pair every output equals the input segmentation to the bit and seg_map is the identity.
+ *   Status, in this order, all before any launch: M < 0 or P < 0: CONV3P_ERR_INVALID_ARGUMENT; M == 0: CONV3P_OK, nothing
+ *   launched; any pointer NULL (select may be; pair_a, pair_b only with P == 0): CONV3P_ERR_INVALID_ARGUMENT; M or
+ *   P > 2^31 - 1: CONV3P_ERR_UNSUPPORTED; workspace NULL or smaller than conv3p_grid_merge_scratch_bytes(M):
+ *   CONV3P_ERR_INVALID_ARGUMENT.  The workspace is 5 M words plus a word per 2048 segments: a function of M alone.  Seven
+ *   launches whatever the data; no host read; the union-find is that of conv3p_grid_segments (lock-free, entries only
+ *   ever decrease); the only atomics are int32 CAS / min / max / add and the 64-bit maximum of size << 32 |
+ *   (0x7fffffff - s) that picks the label; bitwise reproducible.
  * ------------------------------------------------------------------------------------------- */
 #define CONV3P_GRID_MEAN 0
 #define CONV3P_GRID_CENTER 1
@@ -1018,6 +1083,19 @@ int conv3p_grid_segment_geometry(const float *voxel_data, int K, const int32_t *
                                  int32_t *cell_box, float *box, int64_t *moments,
                                  double *centroid, double *eigenvalues, double *axes, double *extent,
                                  int32_t *geometry_stats, void *stream);
+size_t conv3p_grid_adjacency_scratch_bytes(int64_t M, int64_t max_edges);
+int conv3p_grid_segment_adjacency(const int32_t *neigh, const int32_t *segment, const int32_t *seg_stats,
+                                  const int32_t *grid_stats, int64_t M, int connectivity, int64_t max_edges,
+                                  int32_t *adj_start, int32_t *edge_src, int32_t *edge_dst, int32_t *edge_contacts,
+                                  int32_t *edge_voxels, int32_t *edge_offset, int32_t *edge_twin, int32_t *seg_border,
+                                  int64_t *adj_stats, void *workspace, size_t workspace_bytes, void *stream);
+size_t conv3p_grid_merge_scratch_bytes(int64_t M);
+int conv3p_grid_merge_segments(const int32_t *segment, const int32_t *seg_root, const int32_t *seg_size,
+                               const int32_t *seg_rows, const int32_t *seg_label, const int32_t *seg_stats,
+                               const int32_t *pair_a, const int32_t *pair_b, const int32_t *select, int64_t P, int64_t M,
+                               int32_t *seg_map, int32_t *segment_out, int32_t *root_out, int32_t *size_out,
+                               int32_t *rows_out, int32_t *label_out, int32_t *stats_out, int32_t *merge_stats,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The dense head of the classification model (/root/reference/pointcnn2_acsd.py:69-75:

@@ -12,12 +12,12 @@ synth (synthetic clouds).
 from .conv3p_op import (Conv3pFunction, Conv3pInvalidArgument, Conv3pRuntimeError, conv3p, conv3p_autograd,
                         conv3p_grad, conv3p_layer, conv3p_layer_grad, neighbor_count, selu, selu_grad)
 from .optim import MomentumOptimizer, exponential_decay, momentum_step
-from .grid import (GridNormals, GridRoomSubsample, GridSegments, GridSubsample, SegmentGeometry, grid_subsample,
-                   grid_subsample_rooms)
+from .grid import (GridNormals, GridRoomSubsample, GridSegments, GridSubsample, SegmentAdjacency, SegmentGeometry,
+                   grid_subsample, grid_subsample_rooms)
 from .provider import BatchBuffers, BatchProvider, assemble_batch
 from .scene import (SceneBlocks, SceneRoomBlocks, SceneScores, SceneVotes, default_max_blocks, default_max_blocks_rooms,
                     scene_blocks, scene_blocks_rooms)
 from .seg_head import SegmentationHead, class_weights_from_counts
 
-__all__ = ["grid_subsample", "GridSubsample", "grid_subsample_rooms", "GridRoomSubsample", "GridNormals", "GridSegments", "SegmentGeometry", "scene_blocks", "scene_blocks_rooms", "SceneRoomBlocks", "default_max_blocks_rooms", "SceneBlocks", "SceneVotes", "SceneScores", "default_max_blocks","BatchProvider", "BatchBuffers", "assemble_batch", "SegmentationHead", "class_weights_from_counts", "MomentumOptimizer", "exponential_decay", "momentum_step", "conv3p", "conv3p_grad", "conv3p_layer", "conv3p_layer_grad", "conv3p_autograd", "Conv3pFunction", "neighbor_count", "selu", "selu_grad",
+__all__ = ["grid_subsample", "GridSubsample", "grid_subsample_rooms", "GridRoomSubsample", "GridNormals", "GridSegments", "SegmentGeometry", "SegmentAdjacency", "scene_blocks", "scene_blocks_rooms", "SceneRoomBlocks", "default_max_blocks_rooms", "SceneBlocks", "SceneVotes", "SceneScores", "default_max_blocks","BatchProvider", "BatchBuffers", "assemble_batch", "SegmentationHead", "class_weights_from_counts", "MomentumOptimizer", "exponential_decay", "momentum_step", "conv3p", "conv3p_grad", "conv3p_layer", "conv3p_layer_grad", "conv3p_autograd", "Conv3pFunction", "neighbor_count", "selu", "selu_grad",
            "Conv3pInvalidArgument", "Conv3pRuntimeError"]

@@ -173,6 +173,12 @@ SYMBOLS = {
                                          _vp, _vp, _vp, _sz, _vp]),
     "conv3p_grid_segment_geometry": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp]),
+    "conv3p_grid_adjacency_scratch_bytes": (_sz, [ctypes.c_int64, ctypes.c_int64]),
+    "conv3p_grid_segment_adjacency": (_i, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "conv3p_grid_merge_scratch_bytes": (_sz, [ctypes.c_int64]),
+    "conv3p_grid_merge_segments": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "conv3p_stack_scratch_bytes": (_sz, [ctypes.POINTER(StackDesc), _i, _i, _i]),
     "conv3p_workspace_bytes": (_sz, [_i] * 9),
     "conv3p_cache_bytes": (_sz, [_i, _i, _i, ctypes.POINTER(CacheConfig)]),

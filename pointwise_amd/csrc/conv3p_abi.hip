@@ -41,6 +41,7 @@
 #include "conv3p_grid_normals.hpp"
 #include "conv3p_grid_segments.hpp"
 #include "conv3p_grid_geometry.hpp"
+#include "conv3p_grid_adjacency.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -1,5 +1,5 @@
 // conv3p_abi_grid.hpp -- host side of the voxel grid: subsample (single, rooms), project, neighbours, interpolate (plain,
-// rings), normals, segments, absorb, segment geometry.  Included by conv3p_abi.hip.
+// rings), normals, segments, absorb, segment geometry, segment adjacency, merge.  Included by conv3p_abi.hip.
 namespace {
 
 // The workspace of conv3p_grid_subsample_f32 (conv3p_grid.hpp): a host-side bound from the arguments.  The two pair
@@ -164,6 +164,34 @@ size_t carve_absorb(void *ws, int64_t M, AbsorbArgs &p)
     p.small_list = cv.take<int32_t>((size_t)M);
     p.small_off = cv.take<int32_t>((size_t)M);
     p.members = cv.take<int32_t>((size_t)M);
+    return cv.bytes();
+}
+// The adjacency call's: the counters, the radix passes' totals and histograms, the edge table of 2 max_edges + 64 slots (a
+// key and five counters each) and the two key buffers of the sort.  A function of max_edges alone: M only bounds it.
+size_t carve_adj(void *ws, int64_t max_edges, AdjArgs &p)
+{
+    Carver cv(ws);
+    p.slots = 2ull * (unsigned long long)max_edges + kAdjSlack;
+    p.sort_tiles = (int)(((size_t)max_edges + kAdjSortTile - 1) / kAdjSortTile);
+    if (p.sort_tiles < 1) p.sort_tiles = 1;
+    p.hdr = cv.take<AdjHeader>(1);
+    p.digit_total = cv.take<int>((size_t)2 * kAdjMaxBytes * kAdjDigits);
+    p.hist = cv.take<int>((size_t)p.sort_tiles * kAdjDigits);
+    p.keys = cv.take<unsigned long long>((size_t)p.slots);
+    p.vals = cv.take<int32_t>((size_t)p.slots * kAdjVals);
+    p.sort_a = cv.take<unsigned long long>((size_t)max_edges);
+    p.sort_b = cv.take<unsigned long long>((size_t)max_edges);
+    return cv.bytes();
+}
+// The merge call's: the tiles' roots, lab, parent, members, and the 64-bit label keys.
+size_t carve_merge(void *ws, int64_t M, MergeArgs &p)
+{
+    Carver cv(ws);
+    p.tile_count = cv.take<int32_t>(gseg_tiles(M));
+    p.lab = cv.take<int32_t>((size_t)M);
+    p.parent = cv.take<int32_t>((size_t)M);
+    p.members = cv.take<int32_t>((size_t)M);
+    p.best = cv.take<unsigned long long>((size_t)M);
     return cv.bytes();
 }
 unsigned gseg_grid(size_t work) { return (unsigned)(work < (size_t)kGsegMaxGrid ? (work ? work : 1) : (size_t)kGsegMaxGrid); }
@@ -450,6 +478,104 @@ int conv3p_grid_segment_geometry(const float *voxel_data, int K, const int32_t *
                        m, steps, centroid, axes, extent_key);
     hipLaunchKernelGGL(geom_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_stats, m, cell_box, box_key, mom,
                        extent_key, geometry_stats);
+    return hip_ok();
+}
+
+size_t conv3p_grid_adjacency_scratch_bytes(int64_t M, int64_t max_edges)
+{
+    AdjArgs p;
+    if (M <= 0 || M > (int64_t)INT32_MAX || max_edges < 0 || max_edges > (int64_t)INT32_MAX) return 0;
+    return carve_adj(nullptr, max_edges, p);
+}
+
+// Every status first, in the order include/conv3p.h gives; then 5 + 6 b launches, b the bytes of M - 1: fixed by M.
+int conv3p_grid_segment_adjacency(const int32_t *neigh, const int32_t *segment, const int32_t *seg_stats,
+                                  const int32_t *grid_stats, int64_t M, int connectivity, int64_t max_edges,
+                                  int32_t *adj_start, int32_t *edge_src, int32_t *edge_dst, int32_t *edge_contacts,
+                                  int32_t *edge_voxels, int32_t *edge_offset, int32_t *edge_twin, int32_t *seg_border,
+                                  int64_t *adj_stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const unsigned tapmask = gseg_tapmask(connectivity);
+    if (M < 0 || !tapmask || max_edges < 0) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!neigh || !segment || !seg_stats || !grid_stats || !adj_start || !seg_border || !adj_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (max_edges > 0 && (!edge_src || !edge_dst || !edge_contacts || !edge_voxels || !edge_offset || !edge_twin))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX || max_edges > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    AdjArgs p{};
+    const size_t need = carve_adj(workspace, max_edges, p);
+    if (!workspace || workspace_bytes < need) return CONV3P_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    p.neigh = neigh; p.segment = segment; p.seg_stats = seg_stats; p.grid_stats = grid_stats;
+    p.M = (int)M; p.max_edges = (int)max_edges; p.tapmask = tapmask;
+    p.adj_start = adj_start; p.edge_src = edge_src; p.edge_dst = edge_dst; p.edge_contacts = edge_contacts;
+    p.edge_voxels = edge_voxels; p.edge_offset = edge_offset; p.edge_twin = edge_twin; p.seg_border = seg_border;
+    p.adj_stats = reinterpret_cast<long long *>(adj_stats);
+    const size_t cells = std::max((size_t)p.slots * kAdjVals, (size_t)M * 4);
+    const unsigned per_cell = capped_grid((cells + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
+    const unsigned per_voxel = capped_grid(((size_t)M + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
+    const unsigned per_slot = capped_grid(((size_t)p.slots + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
+    const unsigned per_tile = capped_grid((size_t)p.sort_tiles, kAdjMaxGrid);
+    const size_t rows = std::max((size_t)M + 1, (size_t)max_edges);
+    int bytes = 1;                                       // of M - 1 >= S - 1: the passes a half of the key can need
+    while (bytes < kAdjMaxBytes && ((uint64_t)(M - 1) >> (8 * bytes))) ++bytes;
+    hipLaunchKernelGGL(adj_init_kernel, dim3(per_cell), dim3(kAdjThreads), 0, s, p);
+    hipLaunchKernelGGL(adj_walk_kernel, dim3(per_voxel), dim3(kAdjThreads), 0, s, p);
+    hipLaunchKernelGGL(adj_compact_kernel, dim3(per_slot), dim3(kAdjThreads), 0, s, p);
+    for (int half = 0; half < 2; ++half)
+        for (int j = 0; j < bytes; ++j) {                // a pass above the top byte of S - 1 returns at once
+            hipLaunchKernelGGL(adj_sort_hist_kernel, dim3(per_tile), dim3(kAdjThreads), 0, s, p, half, j);
+            hipLaunchKernelGGL(adj_sort_scan_kernel, dim3(kAdjDigits), dim3(kAdjScanThreads), 0, s, p, half, j);
+            hipLaunchKernelGGL(adj_sort_scatter_kernel, dim3(per_tile), dim3(64), 0, s, p, half, j);
+        }
+    hipLaunchKernelGGL(adj_finish_kernel, dim3(capped_grid((rows + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid)),
+                       dim3(kAdjThreads), 0, s, p);
+    hipLaunchKernelGGL(adj_stats_kernel, dim3(1), dim3(64), 0, s, p);
+    return hip_ok();
+}
+
+size_t conv3p_grid_merge_scratch_bytes(int64_t M)
+{
+    MergeArgs p;
+    if (M <= 0 || M > (int64_t)INT32_MAX) return 0;
+    return carve_merge(nullptr, M, p);
+}
+
+// Every status first, in the order include/conv3p.h gives; then seven launches whatever the data.
+int conv3p_grid_merge_segments(const int32_t *segment, const int32_t *seg_root, const int32_t *seg_size,
+                               const int32_t *seg_rows, const int32_t *seg_label, const int32_t *seg_stats,
+                               const int32_t *pair_a, const int32_t *pair_b, const int32_t *select, int64_t P, int64_t M,
+                               int32_t *seg_map, int32_t *segment_out, int32_t *root_out, int32_t *size_out,
+                               int32_t *rows_out, int32_t *label_out, int32_t *stats_out, int32_t *merge_stats,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (M < 0 || P < 0) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!segment || !seg_root || !seg_size || !seg_rows || !seg_label || !seg_stats || !seg_map || !segment_out || !root_out ||
+        !size_out || !rows_out || !label_out || !stats_out || !merge_stats || (P > 0 && (!pair_a || !pair_b)))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX || P > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    MergeArgs p{};
+    const size_t need = carve_merge(workspace, M, p);
+    if (!workspace || workspace_bytes < need) return CONV3P_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    p.segment = segment; p.seg_root = seg_root; p.seg_size = seg_size; p.seg_rows = seg_rows; p.seg_label = seg_label;
+    p.seg_stats = seg_stats; p.pair_a = pair_a; p.pair_b = pair_b; p.select = select; p.P = (long long)P;
+    p.M = (int)M; p.ntiles = (int)gseg_tiles(M);
+    p.seg_map = seg_map; p.segment_out = segment_out; p.root_out = root_out; p.size_out = size_out; p.rows_out = rows_out;
+    p.label_out = label_out; p.stats_out = stats_out; p.merge_stats = merge_stats;
+    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)p.ntiles);
+    hipLaunchKernelGGL(merge_init_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(merge_union_kernel, dim3(gseg_grid(((size_t)P + kGsegThreads - 1) / kGsegThreads)), dim3(kGsegThreads), 0,
+                       s, p);
+    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p.lab, p.parent, p.M, p.ntiles,
+                       p.tile_count);
+    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, p.tile_count, static_cast<int32_t *>(nullptr),
+                       p.ntiles, stats_out, static_cast<int32_t *>(nullptr));
+    hipLaunchKernelGGL(merge_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(merge_assign_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(merge_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
     return hip_ok();
 }
 

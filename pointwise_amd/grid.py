@@ -1,9 +1,9 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
 conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64,
 conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32, conv3p_grid_segments, conv3p_grid_absorb_segments,
-conv3p_grid_segment_geometry; kernels in csrc/conv3p_grid.hpp, csrc/conv3p_grid_interp.hpp,
-csrc/conv3p_grid_interp_rings.hpp, csrc/conv3p_grid_normals.hpp, csrc/conv3p_grid_segments.hpp and
-csrc/conv3p_grid_geometry.hpp).
+conv3p_grid_segment_geometry, conv3p_grid_segment_adjacency, conv3p_grid_merge_segments; kernels in csrc/conv3p_grid.hpp,
+csrc/conv3p_grid_interp.hpp, csrc/conv3p_grid_interp_rings.hpp, csrc/conv3p_grid_normals.hpp,
+csrc/conv3p_grid_segments.hpp, csrc/conv3p_grid_geometry.hpp and csrc/conv3p_grid_adjacency.hpp).
 
 A raw room or scan has hundreds of thousands to millions of rows at a density that varies by an order of magnitude.  The
 first step of a scene pipeline thins it to one row per occupied voxel of a lattice; the model runs on those rows, and
@@ -27,6 +27,10 @@ tests/grid_ref.py restates it in numpy.
     GridSegments.geometry       -> SegmentGeometry: per segment the box of its cells and of its representatives, the exact
                      integer moments of its cells, the centroid, the principal axes and the oriented extents
                      (tests/grid_geometry_ref.py): a list of objects from a labelled scan
+    GridSegments.adjacency      -> SegmentAdjacency: which segments touch, in CSR form, with the contacts, border voxels
+                     and summed direction of every edge and the border counts of every segment
+                     (tests/grid_adjacency_ref.py); GridSegments.merge / SegmentAdjacency.merge: segments joined along
+                     any selection of pairs -> a GridSegments again
     grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
                      voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
@@ -348,6 +352,8 @@ class GridSubsample:
         if out is None:
             out = GridSegments(M, dev)
         out._source = (self, voxel_labels, L, 1 if voxel_labels is None else num_class, connectivity)
+        if out._merged:                                  # an object merge() wrote into earlier: a plain segmentation again
+            del out._merged, out.seg_map, out.merge_stats
         if M == 0:
             out.stats.zero_()
             return out
@@ -400,7 +406,13 @@ class GridSegments:
     root, size (voxels), rows (raw rows: the members' voxel_count summed) and label per segment, -1 / 0 / 0 / -1 past the
     last one; stats int32 (8) on the device = {segments, labelled voxels, unlabelled voxels below the emitted ones, filler
     rows, largest size, largest rows, 0, 0}.  After absorb(): absorbed_label int32 (M), the label per segment behind the
-    clean-up, and absorb_stats int64 (4) = {small segments, absorbed, orphans, voxels whose label changed}."""
+    clean-up, and absorb_stats int64 (4) = {small segments, absorbed, orphans, voxels whose label changed}.  On the object
+    merge() returned: seg_map int32 (M), the new number of every segment of the object it was called on (-1 past its
+    last one), and merge_stats int32 (4) = {groups, segments, active pairs with a != b, groups of more than one
+    segment}."""
+
+    seg_map = merge_stats = None                         # set on the object merge() returns, and on no other
+    _merged = False
 
     def __init__(self, num_voxels, device):
         M = int(num_voxels)
@@ -422,10 +434,14 @@ class GridSegments:
         return int(self.stats[0])
 
     def trim(self):
-        """Views of the first num_segments() segment rows, as a GridSegments (segment and stats shared)."""
+        """Views of the first num_segments() segment rows, as a GridSegments (segment and stats shared; of a merged object
+        seg_map and merge_stats too)."""
         S = self.num_segments()
-        return _view(self, GridSegments, slice(S), ("root", "size", "rows", "label", "absorbed_label"),
-                     ("segment", "stats", "absorb_stats"), shape=self.shape, workspace=None, _absorb_workspace=None, _source=None)
+        t = _view(self, GridSegments, slice(S), ("root", "size", "rows", "label", "absorbed_label"),
+                  ("segment", "stats", "absorb_stats"), shape=self.shape, workspace=None, _absorb_workspace=None, _source=None)
+        if self._merged:                                 # seg_map is a row per segment of the object merge() was called on
+            t._merged, t.seg_map, t.merge_stats = True, self.seg_map, self.merge_stats
+        return t
 
     def absorb(self, min_size, drop_orphans=False, out=None):
         """One clean-up pass -> labels int32 (M): every segment of fewer than min_size voxels takes the label most of the
@@ -439,6 +455,8 @@ class GridSegments:
         _require_int(min_size, "min_size must be a positive integer", 1, 2 ** 31 - 1)
         _require(isinstance(drop_orphans, bool), "drop_orphans must be a bool")
         _require(self._source is not None, "absorb works on the object segments() returned, not on its trim()")
+        _require(not self._merged, "absorb works on what segments() returned: a merged segment may hold "
+                 "several classes, which rule A2 excludes")
         grid, voxel_labels, L, num_class, connectivity = self._source
         dev = self.segment.device
         M = self.shape[0]
@@ -509,6 +527,171 @@ class GridSegments:
                   out.moments.data_ptr(), out.centroid.data_ptr(), out.eigenvalues.data_ptr(), out.axes.data_ptr(),
                   out.extent.data_ptr(), out.stats.data_ptr(), _stream(dev))
         return out
+
+    def adjacency(self, connectivity=None, max_edges=None, out=None):
+        """Which segments touch -> SegmentAdjacency: the region adjacency graph of this segmentation in CSR form, with the
+        exact number of contacts, the border voxels and the summed direction of every edge, and the border counts of every
+        segment (include/conv3p.h: conv3p_grid_segment_adjacency, rules E1-E7; tests/grid_adjacency_ref.py).
+
+        connectivity 6, 18 or 26 decides which taps are contacts; None takes the connectivity the segments were made
+        with, but the two are independent: two pieces of one class that only share a corner are segments at 6 and
+        neighbours at 26.  max_edges is the number of rows of the edge arrays; None takes 2 * M.  A field in which every
+        voxel is its own segment has up to 26 * M directed edges, so the default can overflow: then num_edges() is -1,
+        every edge row is filler, border is still exact, and a retry with max_edges=adj.edges_bound() always fits.  out: a
+        SegmentAdjacency of an earlier call with the same M and max_edges.
+
+        A policy is a torch expression over the edge arrays, and merge() applies it:
+
+            adj = seg.adjacency().trim()                 # every small segment into the neighbour it touches most
+            src = adj.src.long()
+            most = torch.zeros_like(seg.size).scatter_reduce(0, src, adj.contacts, "amax")
+            merged = adj.merge((seg.size[src] < 4) & (adj.contacts == most[src]))
+
+        Works on the object segments() or merge() returned, on a trimmed GridSubsample and on the many-clouds result as
+        they stand: the table is per room, so no edge crosses a room.  5 + 6 b launches, b the bytes of M - 1 (fixed by M,
+        whatever the data; and the neighbour table's on first use), nothing synchronised on."""
+        _require(connectivity is None or (_is_int(connectivity, 6, 26) and connectivity in (6, 18, 26)),
+                 "connectivity must be None, 6, 18 or 26")
+        _require(self._source is not None, "adjacency works on the object segments() or merge() returned, not on its trim()")
+        grid = self._source[0]
+        if connectivity is None:
+            connectivity = self._source[4]
+        dev = self.segment.device
+        M = self.shape[0]
+        if max_edges is None:
+            max_edges = 2 * M
+        _require_int(max_edges, "max_edges must be a non-negative integer below 2^31", 0, 2 ** 31 - 1)
+        _require_table(dev, (("voxel_cell", grid.voxel_cell, (M, 3)), ("stats", grid.stats, (8,)),
+                             ("segment", self.segment, (M,)), ("stats", self.stats, (8,))))
+        if out is not None:
+            _require(isinstance(out, SegmentAdjacency) and out.shape == (M, max_edges) and out.start.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", _NO_CPU)
+        if out is None:
+            out = SegmentAdjacency(M, max_edges, dev)
+        out._segments = self
+        out.connectivity = connectivity
+        if M == 0:
+            _fill_empty(out)
+            return out
+        lib = _lib.load()
+        ws = _grow(out, "workspace", int(lib.conv3p_grid_adjacency_scratch_bytes(M, max_edges)), dev)
+        neigh = grid.neighbors()
+        with torch.cuda.device(dev):
+            _call(lib.conv3p_grid_segment_adjacency, neigh.data_ptr(), self.segment.data_ptr(), self.stats.data_ptr(),
+                  grid.stats.data_ptr(), M, connectivity, max_edges, out.start.data_ptr(), _ptr(out.src), _ptr(out.dst),
+                  _ptr(out.contacts), _ptr(out.voxels), _ptr(out.offset), _ptr(out.twin), out.border.data_ptr(),
+                  out.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+        return out
+
+    def merge(self, pair_a, pair_b, select=None, out=None):
+        """Segments joined along pairs -> a GridSegments: the pairs (pair_a[p], pair_b[p]) with select[p] != 0 (all of them
+        with select=None) and both numbers in [0, S) are collapsed by union-find, transitively; the groups are numbered in
+        ascending lowest voxel like any segmentation (include/conv3p.h: conv3p_grid_merge_segments, rules U1-U5).
+
+        pair_a, pair_b: contiguous int32 (P,) tensors on the device, for example adj.src and adj.dst: filler rows (-1) are
+        ignored, one direction of an edge is enough, and a == b joins nothing.  select: a contiguous int32 or bool (P,)
+        tensor, or None.  The result's size and rows are the sums over a group, its root the group's lowest voxel, its
+        label that of the member with the most voxels (the lowest number on a tie); it also carries seg_map int32 (M), the
+        group of every old segment (-1 past S), and merge_stats int32 (4) = {groups, segments, active pairs with a != b,
+        groups of more than one segment}.  With nothing selected it equals this object to the bit.  geometry(),
+        adjacency(), merge() and g.project(merged.segment) work on it as on any other; absorb() does not: a merged
+        segment may hold several classes.  out: a GridSegments of the same number of rows, not this one.  Seven launches
+        whatever the data, nothing synchronised on."""
+        _require(self._source is not None, "merge works on the object segments() or merge() returned, not on its trim()")
+        dev = self.segment.device
+        M = self.shape[0]
+        _require_tensor(pair_a, "pair_a must be a contiguous int32 (P,) tensor on the segments' device", torch.int32, dev=dev, ndim=1)
+        P = pair_a.numel()
+        _require_tensor(pair_b, "pair_b must be a contiguous int32 (P,) tensor on the segments' device, as long as pair_a",
+                        torch.int32, (P,), dev)
+        if select is not None:
+            _require_tensor(select, "select must be None or a contiguous int32 or bool (P,) tensor on the segments' device",
+                            (torch.int32, torch.bool), (P,), dev)
+        _require_table(dev, (("segment", self.segment, (M,)), ("root", self.root, (M,)), ("size", self.size, (M,)),
+                             ("rows", self.rows, (M,)), ("label", self.label, (M,)), ("stats", self.stats, (8,))))
+        if out is not None:
+            _require(isinstance(out, GridSegments) and out is not self and out.shape == (M,) and out.segment.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", _NO_CPU)
+        if out is None:
+            out = GridSegments(M, dev)
+        out._source = (self._source[0], None, 0, self._source[3], self._source[4])
+        out._merged = True
+        if out.seg_map is None:
+            out.seg_map = torch.empty((M,), dtype=torch.int32, device=dev)
+            out.merge_stats = torch.zeros((4,), dtype=torch.int32, device=dev)
+        if M == 0:
+            out.stats.zero_()
+            out.merge_stats.zero_()
+            return out
+        if select is not None and select.dtype == torch.bool:
+            select = select.to(torch.int32)
+        lib = _lib.load()
+        ws = _grow(out, "workspace", int(lib.conv3p_grid_merge_scratch_bytes(M)), dev)
+        with torch.cuda.device(dev):
+            _call(lib.conv3p_grid_merge_segments, self.segment.data_ptr(), self.root.data_ptr(), self.size.data_ptr(),
+                  self.rows.data_ptr(), self.label.data_ptr(), self.stats.data_ptr(), _ptr(pair_a), _ptr(pair_b), _ptr(select),
+                  P, M, out.seg_map.data_ptr(), out.segment.data_ptr(), out.root.data_ptr(), out.size.data_ptr(),
+                  out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr(), out.merge_stats.data_ptr(), ws.data_ptr(),
+                  ws.numel(), _stream(dev))
+        return out
+
+
+class SegmentAdjacency:
+    """The outputs of GridSegments.adjacency.  Per segment: start int32 (M + 1), row s of the CSR is the edges
+    [start[s], start[s + 1]); border int32 (M, 4) = {contacts to other segments, (member, tap) pairs towards a voxel in no
+    segment, pairs with no neighbour, surface voxels}.  Per directed edge, in ascending (src, dst), max_edges rows: src,
+    dst, contacts (the (voxel, tap) pairs from src into dst: the twin's value), voxels (the voxels of src that touch dst:
+    not symmetric), offset int32 (max_edges, 3) (the taps' (dx, dy, dz) summed over the contacts: the negative of the
+    twin's; a positive z says dst lies above src), twin (the row of the edge (dst, src)); rows past the last edge hold -1,
+    -1, 0, 0, 0, -1.  stats int64 (8) on the device = {edges E, B = the sum of voxels, segments, contacts in all, largest
+    degree, largest contacts, 0, 0}, or on overflow (E > max_edges) {-1, B, segments, contacts in all, 0, 0, 1, 0} with
+    every edge row filler and start all 0."""
+
+    _FILL = (("start", 0), ("src", -1), ("dst", -1), ("contacts", 0), ("voxels", 0), ("offset", 0), ("twin", -1), ("border", 0),
+             ("stats", 0))
+
+    def __init__(self, num_voxels, max_edges, device):
+        M, E = int(num_voxels), int(max_edges)
+        self.shape = (M, E)
+        self.start = torch.empty((M + 1,), dtype=torch.int32, device=device)
+        self.src = torch.empty((E,), dtype=torch.int32, device=device)
+        self.dst = torch.empty((E,), dtype=torch.int32, device=device)
+        self.contacts = torch.empty((E,), dtype=torch.int32, device=device)
+        self.voxels = torch.empty((E,), dtype=torch.int32, device=device)
+        self.offset = torch.empty((E, 3), dtype=torch.int32, device=device)
+        self.twin = torch.empty((E,), dtype=torch.int32, device=device)
+        self.border = torch.empty((M, 4), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((8,), dtype=torch.int64, device=device)
+        self.workspace = None
+        self.connectivity = None
+        self._segments = None
+
+    def num_edges(self):
+        """The number of directed edges, -1 on overflow: the one host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def edges_bound(self):
+        """B, the number of (voxel, foreign segment) pairs: at least the number of edges, whatever max_edges was, so an
+        adjacency(max_edges=edges_bound()) always fits.  A host read."""
+        return int(self.stats[1])
+
+    def overflowed(self):
+        """Whether the edges did not fit max_edges.  A host read."""
+        return int(self.stats[6]) != 0
+
+    def trim(self):
+        """Views of the first num_edges() edge rows (none on overflow), as a SegmentAdjacency (start, border and stats
+        shared)."""
+        E = max(self.num_edges(), 0)
+        return _view(self, SegmentAdjacency, slice(E), ("src", "dst", "contacts", "voxels", "offset", "twin"),
+                     ("start", "border", "stats", "connectivity", "_segments"), shape=(self.shape[0], E), workspace=None)
+
+    def merge(self, select=None, out=None):
+        """The segments joined along the selected edges -> GridSegments: segments.merge(src, dst, select)."""
+        _require(self._segments is not None, "merge works on the object adjacency() returned")
+        return self._segments.merge(self.src, self.dst, select, out)
 
 
 _GEOMETRY_WEIGHTS = {"voxels": 0, "rows": 1}
