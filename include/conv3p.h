@@ -906,6 +906,71 @@ int conv3p_scene_score_labels(const int64_t *scores, int64_t N, int num_class, i
  *   entries only ever decrease, so every retry follows another thread's progress and no loop waits for a thread to arrive.
  *   The only atomics are int32 CAS / min / max / add and the int64 adds of absorb_stats; bitwise reproducible.
  *
+ * conv3p_grid_segments_smooth:  segments under a join predicate -- region growing over normals, curvature and features
+ *   (pointwise_amd/csrc/conv3p_grid_smooth.hpp; tests/grid_smooth_ref.py restates it in numpy).  The arguments of
+ *   conv3p_grid_segments, and: normals float32 (M, 3) or NULL; normal_flags int32 (M) or NULL; curvature float32 (M) or
+ *   NULL, all as conv3p_grid_normals_f32 writes them; min_cos; signed_normals 0 or 1; max_curvature; features float32, F
+ *   channels (0 with features NULL, else 1 .. 16) at a row stride of feature_stride >= F floats, or NULL; max_difference;
+ *   smooth_stats int64 (8).  The workspace is that of conv3p_grid_segments_workspace_bytes(M).  The library is built with
+ *   -ffp-contract=off: every float operation below is one separately rounded float32 operation.
+ *    J1. Labelling is S1 and the taps are S2's.  A pair (v, u) with u = neigh[v][t] for a tap of the connectivity,
+ *        0 <= u < ne, both labelled with the same label, is a CANDIDATE pair.  It is JOINED when it also passes J2, J3 and
+ *        J4, each for the input that is given; at least one of normals and features must be given.  Segments are the
+ *        transitive closure of the joined pairs.  Numbering and the outputs segment, seg_root, seg_size, seg_rows,
+ *        seg_label and seg_stats are S3 and S4 unchanged.
+ *    J2. Normals.  Voxel v HAS A NORMAL when normal_flags is NULL or normal_flags[v] == 0, and its three components are
+ *        finite.  A pair with an endpoint without a normal is not joined: such a voxel is a segment of its own, not
+ *        unlabelled.  d = (nx_v * nx_u + ny_v * ny_u) + nz_v * nz_u in that association, which is symmetric in u and v;
+ *        with signed_normals == 0, d = fabsf(d).  The pair passes iff d >= min_cos: equality joins, a NaN does not.
+ *    J3. Curvature, read only when curvature is given: the pair passes iff curvature[v] <= max_curvature and
+ *        curvature[u] <= max_curvature (a NaN fails).
+ *    J4. Features: the pair passes iff fabsf(f_v[k] - f_u[k]) <= max_difference for every channel k < F (a NaN fails).
+ *    J5. smooth_stats int64 (8), overwritten by every call: [0] candidate pairs with u < v, so each undirected pair once
+ *        (for the half taps t < 13 of a table of conv3p_grid_neighbors u < v always holds); [1] pairs joined; [2] pairs
+ *        refused for a missing normal; [3] refused by angle; [4] refused by curvature; [5] refused by features; [6]
+ *        labelled voxels without a normal (0 without normals); [7] 0.  The first rule that fails, in the order J2, J3, J4,
+ *        takes the pair, so [0] = [1] + [2] + [3] + [4] + [5].
+ *   Status: those of conv3p_grid_segments in its order (M == 0 is CONV3P_OK there, nothing launched or written); then
+ *   normals and features both NULL; F outside [0, 16], or F == 0 with features given, or F > 0 without; features given
+ *   with feature_stride < F; signed_normals not 0 or 1; min_cos, max_curvature or max_difference a NaN; smooth_stats NULL:
+ *   CONV3P_ERR_INVALID_ARGUMENT.  All before any launch.  Seven launches whatever the data behind a 64-byte memset of
+ *   smooth_stats: the two union-find kernels of conv3p_grid_segments with the predicate evaluated behind the label test,
+ *   and its other five launches as they are.  The predicate reads nothing the kernels write and is evaluated before the
+ *   union, so the progress argument stands: no loop waits for a thread.  J5 is counted in registers, summed over a wave
+ *   by shuffles and added with 64-bit integer adds.  The only atomics are integer CAS / min / max / add; no float
+ *   atomics; bitwise reproducible and independent of the launch geometry.
+ *
+ * conv3p_grid_segment_pool_f32, conv3p_grid_segment_pool_i64:  exact sums of a value row per voxel over the segments of
+ *   any segmentation: mean normals, mean colours, summed class scores and the class they vote for
+ *   (pointwise_amd/csrc/conv3p_grid_smooth.hpp; tests/grid_smooth_ref.py).  values (L, C), L <= M, C in [1, 128], at a row
+ *   stride of value_stride >= C elements: float32, or int64 fixed-point sums as conv3p_scene_vote_scores_f32 writes them;
+ *   segment and seg_stats as conv3p_grid_segments, _smooth or conv3p_grid_merge_segments write them; voxel_count and
+ *   grid_stats the subsampling's; weight 0 (every voxel counts once) or 1 (as its voxel_count raw rows; _f32 only).
+ *    P1. Membership is G1: ne and S read on the device, v < ne and 0 <= segment[v] < S.
+ *    P2. A member CONTRIBUTES when v < L and, for _f32, all its C values are finite with |x| <= 256.  Its quantum of
+ *        channel c is q = llrint((double)x * 2^30) for _f32 (the product is exact, the rounding to nearest even) and
+ *        q = values[v][c] for _i64.
+ *    P3. sums[s][c] = sum of w_v * q and weights[s] = sum of w_v over the contributors of s, w_v = 1 or voxel_count[v], in
+ *        wrapping 64-bit integer arithmetic.  With |x| <= 256 and at most 2^24 rows in all, |sums| <= 2^8 * 2^30 * 2^24 =
+ *        2^62: _f32 cannot wrap.
+ *    P4. mean[s][c] = (double)sums[s][c] / ((double)weights[s] * 2^30): the conversions round to nearest even, the product
+ *        is exact, one division.  0 where weights[s] == 0 (no contributor).
+ *    P5. seg_label[s] is class 0 unless a later class is strictly greater: the lowest class of a tie wins (on
+ *        non-negative sums the rule of conv3p_scene_score_labels).  -1 when weights[s] == 0 or every sum is 0.
+ *        voxel_label[v] = seg_label[segment[v]] for a member, else -1.  Rows s >= S hold sums 0, weights 0, mean 0,
+ *        seg_label -1.
+ *    P6. pool_stats int64 (4) = {contributors, members that did not contribute, segments s < S with a label, without}.
+ *   Outputs, every word written by every call: sums int64 (M, C), weights int64 (M), mean float64 (M, C) or NULL,
+ *   seg_label int32 (M), voxel_label int32 (M) or NULL, pool_stats.
+ *   Status, in this order, all before any launch: M < 0, L < 0 or L > M, C outside [1, 128], value_stride < C, weight not
+ *   0 or 1 (_i64: not 0): CONV3P_ERR_INVALID_ARGUMENT; M == 0: CONV3P_OK, nothing launched and nothing written; values
+ *   NULL with L > 0, or any other pointer but mean and voxel_label NULL: CONV3P_ERR_INVALID_ARGUMENT; M > 2^31 - 1:
+ *   CONV3P_ERR_UNSUPPORTED.  NO workspace: the outputs are the accumulators.  Three launches, four with voxel_label,
+ *   whatever the data (zeroes; the sums -- a wave takes consecutive voxels, reduces runs of equal segment by a segmented
+ *   shuffle, carries the open run from step to step, and walks the channels eight at a time: one 64-bit integer atomic add
+ *   per channel and finished run; a thread per segment for P4-P6; voxel_label).  No host read; no float atomics; bitwise
+ *   reproducible and independent of the launch geometry.
+ *
  * conv3p_grid_segment_geometry:  where every segment is, how large it is in space and how it is oriented -- the step from
  *   a segmentation to a list of objects (pointwise_amd/csrc/conv3p_grid_geometry.hpp; tests/grid_geometry_ref.py restates it
  *   in numpy).  voxel_data (M, K) with row stride K, xyz first; voxel_cell int32 (M, 3) and voxel_count int32 (M) as the
@@ -1071,6 +1136,21 @@ int conv3p_grid_segments(const int32_t *neigh, const int32_t *voxel_labels, int6
                          const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment,
                          int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label, int32_t *seg_stats,
                          void *workspace, size_t workspace_bytes, void *stream);
+int conv3p_grid_segments_smooth(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *voxel_count,
+                                const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment,
+                                int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label,
+                                int32_t *seg_stats, const float *normals, const int32_t *normal_flags, const float *curvature,
+                                float min_cos, int signed_normals, float max_curvature, const float *features, int F,
+                                int64_t feature_stride, float max_difference, int64_t *smooth_stats, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int conv3p_grid_segment_pool_f32(const float *values, int64_t L, int C, int64_t value_stride, const int32_t *segment,
+                                 const int32_t *seg_stats, const int32_t *voxel_count, const int32_t *grid_stats, int64_t M,
+                                 int weight, int64_t *sums, int64_t *weights, double *mean, int32_t *seg_label,
+                                 int32_t *voxel_label, int64_t *pool_stats, void *stream);
+int conv3p_grid_segment_pool_i64(const int64_t *values, int64_t L, int C, int64_t value_stride, const int32_t *segment,
+                                 const int32_t *seg_stats, const int32_t *voxel_count, const int32_t *grid_stats, int64_t M,
+                                 int weight, int64_t *sums, int64_t *weights, double *mean, int32_t *seg_label,
+                                 int32_t *voxel_label, int64_t *pool_stats, void *stream);
 size_t conv3p_grid_absorb_workspace_bytes(int64_t M);
 int conv3p_grid_absorb_segments(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *segment,
                                 const int32_t *seg_size, const int32_t *seg_label, const int32_t *seg_stats,

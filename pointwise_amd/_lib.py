@@ -168,6 +168,13 @@ SYMBOLS = {
     "conv3p_grid_segments_workspace_bytes": (_sz, [ctypes.c_int64]),
     "conv3p_grid_segments": (_i, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _sz, _vp]),
+    "conv3p_grid_segments_smooth": (_i, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, ctypes.c_float, _i, ctypes.c_float, _vp, _i, ctypes.c_int64,
+                                         ctypes.c_float, _vp, _vp, _sz, _vp]),
+    "conv3p_grid_segment_pool_f32": (_i, [_vp, ctypes.c_int64, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
+    "conv3p_grid_segment_pool_i64": (_i, [_vp, ctypes.c_int64, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "conv3p_grid_absorb_workspace_bytes": (_sz, [ctypes.c_int64]),
     "conv3p_grid_absorb_segments": (_i, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _i, _i, _vp,
                                          _vp, _vp, _vp, _sz, _vp]),

@@ -42,6 +42,7 @@
 #include "conv3p_grid_segments.hpp"
 #include "conv3p_grid_geometry.hpp"
 #include "conv3p_grid_adjacency.hpp"
+#include "conv3p_grid_smooth.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -1,5 +1,6 @@
 // conv3p_abi_grid.hpp -- host side of the voxel grid: subsample (single, rooms), project, neighbours, interpolate (plain,
-// rings), normals, segments, absorb, segment geometry, segment adjacency, merge.  Included by conv3p_abi.hip.
+// rings), normals, segments (by label, smooth), absorb, segment geometry, segment pool, segment adjacency, merge.  Included
+// by conv3p_abi.hip.
 namespace {
 
 // The workspace of conv3p_grid_subsample_f32 (conv3p_grid.hpp): a host-side bound from the arguments.  The two pair
@@ -144,6 +145,9 @@ unsigned gseg_tapmask(int connectivity)
     return mask;
 }
 size_t gseg_tiles(int64_t M) { return ((size_t)M + kGsegTile - 1) / kGsegTile; }
+// The consecutive voxels a wave takes in the kernels that reduce runs of equal segment, in steps of 64: more of them where
+// there are waves enough to fill the device anyway.
+int gseg_steps(int64_t M) { return M >= (1 << 20) ? 16 : (M >= (1 << 16) ? 4 : 1); }
 // The segments call's workspace: the tiles' roots, lab, parent.
 size_t carve_gseg(void *ws, int64_t M, int32_t *&tile_count, int32_t *&lab, int32_t *&parent)
 {
@@ -195,6 +199,100 @@ size_t carve_merge(void *ws, int64_t M, MergeArgs &p)
     return cv.bytes();
 }
 unsigned gseg_grid(size_t work) { return (unsigned)(work < (size_t)kGsegMaxGrid ? (work ? work : 1) : (size_t)kGsegMaxGrid); }
+
+// conv3p_grid_segments (rule NULL: labels equal) and conv3p_grid_segments_smooth (the rule of J2-J4): every status first,
+// in the order include/conv3p.h gives; then seven launches whatever the data, the smooth call's behind a memset.
+int gseg_run(const SmoothJoin *rule, const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *voxel_count,
+             const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment, int32_t *seg_root,
+             int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label, int32_t *seg_stats, void *workspace,
+             size_t workspace_bytes, void *stream)
+{
+    const unsigned tapmask = gseg_tapmask(connectivity);
+    if (M < 0 || (voxel_labels && (L < 0 || L > M)) || num_class < 1 || num_class > kGsegMaxClass || !tapmask)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!neigh || !voxel_count || !grid_stats || !segment || !seg_root || !seg_size || !seg_rows || !seg_label || !seg_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    int32_t *tile_count, *lab, *parent;
+    const size_t need = carve_gseg(workspace, M, tile_count, lab, parent);
+    if (!workspace || workspace_bytes < need) return CONV3P_ERR_INVALID_ARGUMENT;
+    if (rule) {
+        if (!rule->normals && !rule->features) return CONV3P_ERR_INVALID_ARGUMENT;
+        if (rule->F < 0 || rule->F > kSmoothMaxFeatures || (rule->features != nullptr) != (rule->F > 0))
+            return CONV3P_ERR_INVALID_ARGUMENT;
+        if (rule->features && rule->feature_stride < rule->F) return CONV3P_ERR_INVALID_ARGUMENT;
+        if (rule->signed_normals != 0 && rule->signed_normals != 1) return CONV3P_ERR_INVALID_ARGUMENT;
+        if (std::isnan(rule->min_cos) || std::isnan(rule->max_curvature) || std::isnan(rule->max_difference))
+            return CONV3P_ERR_INVALID_ARGUMENT;
+        if (!rule->stats) return CONV3P_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int m = (int)M, ntiles = (int)gseg_tiles(M), l = voxel_labels ? (int)L : 0, nc = voxel_labels ? num_class : 1;
+    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)ntiles);
+    const dim3 local_grid(gseg_grid(((size_t)M + kGsegLocalTile - 1) / kGsegLocalTile));
+    if (rule) {
+        if (hipMemsetAsync(rule->stats, 0, 8 * sizeof(int64_t), s) != hipSuccess) return CONV3P_ERR_LAUNCH;
+        hipLaunchKernelGGL(smooth_local_kernel, local_grid, dim3(kGsegLocalTile), 0, s, *rule, neigh, voxel_labels, l, grid_stats,
+                           m, nc, tapmask, lab, parent, seg_root, seg_size, seg_rows, seg_label, seg_stats);
+        hipLaunchKernelGGL(smooth_link_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, *rule, neigh, lab, parent, grid_stats,
+                           m, tapmask);
+    } else {
+        hipLaunchKernelGGL(gseg_local_kernel, local_grid, dim3(kGsegLocalTile), 0, s, neigh, voxel_labels, l, grid_stats, m, nc,
+                           tapmask, lab, parent, seg_root, seg_size, seg_rows, seg_label, seg_stats);
+        hipLaunchKernelGGL(gseg_link_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, neigh, lab, parent, grid_stats, m,
+                           tapmask);
+    }
+    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count);
+    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, tile_count, static_cast<int32_t *>(nullptr),
+                       ntiles, seg_stats, static_cast<int32_t *>(nullptr));
+    hipLaunchKernelGGL(gseg_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count, segment,
+                       seg_root, seg_label);
+    const int steps = gseg_steps(M);
+    const size_t per_wave = (size_t)64 * steps * (kGsegThreads / 64);
+    hipLaunchKernelGGL(gseg_assign_kernel, dim3(gseg_grid(((size_t)M + per_wave - 1) / per_wave)), dim3(kGsegThreads), 0, s, lab,
+                       parent, voxel_count, grid_stats, m, steps, segment, seg_size, seg_rows, seg_stats);
+    hipLaunchKernelGGL(gseg_max_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_size, seg_rows, m, seg_stats);
+    return hip_ok();
+}
+
+// The pool's two entries: every status first, in the order include/conv3p.h gives; then three launches, four with
+// voxel_label, whatever the data; no workspace (conv3p_grid_smooth.hpp).
+template <typename T>
+int grid_segment_pool(const T *values, int64_t L, int C, int64_t value_stride, const int32_t *segment, const int32_t *seg_stats,
+                      const int32_t *voxel_count, const int32_t *grid_stats, int64_t M, int weight, bool rows_allowed,
+                      int64_t *sums, int64_t *weights, double *mean, int32_t *seg_label, int32_t *voxel_label,
+                      int64_t *pool_stats, void *stream)
+{
+    if (M < 0 || L < 0 || L > M || C < 1 || C > kPoolMaxChannels || value_stride < C || (weight != 0 && weight != 1) ||
+        (weight == 1 && !rows_allowed))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if ((L > 0 && !values) || !segment || !seg_stats || !voxel_count || !grid_stats || !sums || !weights || !seg_label ||
+        !pool_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int m = (int)M;
+    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads);
+    const unsigned per_word = gseg_grid(((size_t)M * (size_t)C + kGsegThreads - 1) / kGsegThreads);
+    const int steps = gseg_steps(M);
+    const size_t per_wave = (size_t)64 * steps * (kGsegThreads / 64);
+    unsigned long long *usums = reinterpret_cast<unsigned long long *>(sums);
+    unsigned long long *uweights = reinterpret_cast<unsigned long long *>(weights);
+    unsigned long long *ustats = reinterpret_cast<unsigned long long *>(pool_stats);
+    hipLaunchKernelGGL(pool_init_kernel, dim3(per_word), dim3(kGsegThreads), 0, s, m, C, usums, uweights, ustats);
+    hipLaunchKernelGGL((pool_sum_kernel<T>), dim3(gseg_grid(((size_t)M + per_wave - 1) / per_wave)), dim3(kGsegThreads), 0, s,
+                       values, (int)L, C, (long long)value_stride, segment, seg_stats, voxel_count, grid_stats, m, weight, steps,
+                       usums, uweights, ustats);
+    hipLaunchKernelGGL(pool_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_stats, m, C,
+                       reinterpret_cast<const long long *>(sums), reinterpret_cast<const long long *>(weights), mean, seg_label,
+                       ustats);
+    if (voxel_label)
+        hipLaunchKernelGGL(pool_voxel_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, segment, seg_stats, grid_stats, m,
+                           seg_label, voxel_label);
+    return hip_ok();
+}
 
 // The workspace of conv3p_grid_subsample_rooms_f32 (conv3p_grid_rooms.hpp): the single call's words -- the records grown
 // by one per room, the tiles' pair offsets giving way to the voxel tiles' maxima -- and per room a frame and two prefixes.
@@ -368,36 +466,26 @@ int conv3p_grid_segments(const int32_t *neigh, const int32_t *voxel_labels, int6
                          int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label, int32_t *seg_stats,
                          void *workspace, size_t workspace_bytes, void *stream)
 {
-    const unsigned tapmask = gseg_tapmask(connectivity);
-    if (M < 0 || (voxel_labels && (L < 0 || L > M)) || num_class < 1 || num_class > kGsegMaxClass || !tapmask)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M == 0) return CONV3P_OK;
-    if (!neigh || !voxel_count || !grid_stats || !segment || !seg_root || !seg_size || !seg_rows || !seg_label || !seg_stats)
-        return CONV3P_ERR_INVALID_ARGUMENT;
-    if (M > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
-    int32_t *tile_count, *lab, *parent;
-    const size_t need = carve_gseg(workspace, M, tile_count, lab, parent);
-    if (!workspace || workspace_bytes < need) return CONV3P_ERR_INVALID_ARGUMENT;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int m = (int)M, ntiles = (int)gseg_tiles(M);
-    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)ntiles);
-    hipLaunchKernelGGL(gseg_local_kernel, dim3(gseg_grid(((size_t)M + kGsegLocalTile - 1) / kGsegLocalTile)),
-                       dim3(kGsegLocalTile), 0, s, neigh, voxel_labels,
-                       voxel_labels ? (int)L : 0, grid_stats, m, voxel_labels ? num_class : 1, tapmask, lab, parent, seg_root,
-                       seg_size, seg_rows, seg_label, seg_stats);
-    hipLaunchKernelGGL(gseg_link_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, neigh, lab, parent, grid_stats, m, tapmask);
-    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count);
-    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, tile_count, static_cast<int32_t *>(nullptr),
-                       ntiles, seg_stats, static_cast<int32_t *>(nullptr));
-    hipLaunchKernelGGL(gseg_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, lab, parent, m, ntiles, tile_count, segment,
-                       seg_root, seg_label);
-    // consecutive voxels a wave: more of them where there are waves enough to fill the device anyway
-    const int steps = M >= (1 << 20) ? 16 : (M >= (1 << 16) ? 4 : 1);
-    const size_t per_wave = (size_t)64 * steps * (kGsegThreads / 64);
-    hipLaunchKernelGGL(gseg_assign_kernel, dim3(gseg_grid(((size_t)M + per_wave - 1) / per_wave)), dim3(kGsegThreads), 0, s, lab,
-                       parent, voxel_count, grid_stats, m, steps, segment, seg_size, seg_rows, seg_stats);
-    hipLaunchKernelGGL(gseg_max_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_size, seg_rows, m, seg_stats);
-    return hip_ok();
+    return gseg_run(nullptr, neigh, voxel_labels, L, voxel_count, grid_stats, M, num_class, connectivity, segment, seg_root,
+                    seg_size, seg_rows, seg_label, seg_stats, workspace, workspace_bytes, stream);
+}
+
+int conv3p_grid_segments_smooth(const int32_t *neigh, const int32_t *voxel_labels, int64_t L, const int32_t *voxel_count,
+                                const int32_t *grid_stats, int64_t M, int num_class, int connectivity, int32_t *segment,
+                                int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows, int32_t *seg_label,
+                                int32_t *seg_stats, const float *normals, const int32_t *normal_flags, const float *curvature,
+                                float min_cos, int signed_normals, float max_curvature, const float *features, int F,
+                                int64_t feature_stride, float max_difference, int64_t *smooth_stats, void *workspace,
+                                size_t workspace_bytes, void *stream)
+{
+    SmoothJoin rule{};                                   // the counters 0
+    rule.normals = normals; rule.flags = normal_flags; rule.curvature = curvature; rule.features = features;
+    rule.F = F; rule.feature_stride = (long long)feature_stride;
+    rule.min_cos = min_cos; rule.max_curvature = max_curvature; rule.max_difference = max_difference;
+    rule.signed_normals = signed_normals;
+    rule.stats = reinterpret_cast<unsigned long long *>(smooth_stats);
+    return gseg_run(&rule, neigh, voxel_labels, L, voxel_count, grid_stats, M, num_class, connectivity, segment, seg_root,
+                    seg_size, seg_rows, seg_label, seg_stats, workspace, workspace_bytes, stream);
 }
 
 size_t conv3p_grid_absorb_workspace_bytes(int64_t M)
@@ -479,6 +567,24 @@ int conv3p_grid_segment_geometry(const float *voxel_data, int K, const int32_t *
     hipLaunchKernelGGL(geom_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, seg_stats, m, cell_box, box_key, mom,
                        extent_key, geometry_stats);
     return hip_ok();
+}
+
+int conv3p_grid_segment_pool_f32(const float *values, int64_t L, int C, int64_t value_stride, const int32_t *segment,
+                                 const int32_t *seg_stats, const int32_t *voxel_count, const int32_t *grid_stats, int64_t M,
+                                 int weight, int64_t *sums, int64_t *weights, double *mean, int32_t *seg_label,
+                                 int32_t *voxel_label, int64_t *pool_stats, void *stream)
+{
+    return grid_segment_pool(values, L, C, value_stride, segment, seg_stats, voxel_count, grid_stats, M, weight, true, sums,
+                             weights, mean, seg_label, voxel_label, pool_stats, stream);
+}
+
+int conv3p_grid_segment_pool_i64(const int64_t *values, int64_t L, int C, int64_t value_stride, const int32_t *segment,
+                                 const int32_t *seg_stats, const int32_t *voxel_count, const int32_t *grid_stats, int64_t M,
+                                 int weight, int64_t *sums, int64_t *weights, double *mean, int32_t *seg_label,
+                                 int32_t *voxel_label, int64_t *pool_stats, void *stream)
+{
+    return grid_segment_pool(reinterpret_cast<const long long *>(values), L, C, value_stride, segment, seg_stats, voxel_count,
+                             grid_stats, M, weight, false, sums, weights, mean, seg_label, voxel_label, pool_stats, stream);
 }
 
 size_t conv3p_grid_adjacency_scratch_bytes(int64_t M, int64_t max_edges)

@@ -4,7 +4,8 @@
 // include/conv3p.h defines both by the rules S1-S4 and A1-A4 and tests/grid_segments_ref.py restates them in numpy.
 // Everything is int32 arithmetic: the result is exact and does not depend on the launch geometry or on thread order.
 //
-// conv3p_grid_segments, seven launches whatever the data:
+// conv3p_grid_segments, seven launches whatever the data (the first two kernels are gseg_local_body / gseg_link_body with
+// the join rule "labels equal"; conv3p_grid_smooth.hpp runs the same bodies under a smoothness rule):
 //
 //   gseg_local_kernel     a workgroup per tile of 1024 CONSECUTIVE voxels, a thread per voxel: lab[v] by S1 (-1: unlabelled);
 //                        the union-find below on a copy of the tile in LDS, over the taps whose neighbour lies in the same
@@ -125,11 +126,24 @@ __device__ __forceinline__ int gseg_label(const int32_t *voxel_labels, int L, in
     return (c >= 0 && c < num_class) ? c : -1;
 }
 
-__global__ __launch_bounds__(kGsegLocalTile) void gseg_local_kernel(const int32_t *neigh, const int32_t *voxel_labels, int L,
-                                                                    const int32_t *grid_stats, int M, int num_class,
-                                                                    unsigned tapmask, int32_t *lab, int32_t *parent,
-                                                                    int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows,
-                                                                    int32_t *seg_label, int32_t *seg_stats)
+// The join rule of the two union-find kernels is a functor: join(v, u) says whether the neighbours v and u, which carry the
+// same label, are joined; enter(v) comes before the taps of a labelled voxel v in either kernel, mark() behind it in the
+// local kernel alone (so once a labelled voxel), and done() ends the kernel for every thread.  "Labels equal" is the rule
+// of conv3p_grid_segments: it joins every such pair and the four calls compile to nothing.
+// conv3p_grid_segments_smooth's rule is in conv3p_grid_smooth.hpp.  Which pairs join does not touch the progress
+// argument below: the functor is evaluated before the union and waits for nothing.
+struct LabelsJoin {
+    __device__ __forceinline__ bool join(int, int) { return true; }
+    __device__ __forceinline__ void enter(int) {}
+    __device__ __forceinline__ void mark() {}
+    __device__ __forceinline__ void done() {}
+};
+
+template <typename Join>
+__device__ __forceinline__ void gseg_local_body(Join rule, const int32_t *neigh, const int32_t *voxel_labels, int L,
+                                                const int32_t *grid_stats, int M, int num_class, unsigned tapmask, int32_t *lab,
+                                                int32_t *parent, int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows,
+                                                int32_t *seg_label, int32_t *seg_stats)
 {
     __shared__ int32_t parent_s[kGsegLocalTile], lab_s[kGsegLocalTile];
     const int ne = gseg_ne(grid_stats, M), i = threadIdx.x;
@@ -142,6 +156,8 @@ __global__ __launch_bounds__(kGsegLocalTile) void gseg_local_kernel(const int32_
         parent_s[i] = i;
         __syncthreads();
         if (c >= 0) {                                    // v < ne
+            rule.enter(v);
+            rule.mark();
             const int32_t *row = neigh + (size_t)v * kInterpNeigh;
             int r = i;
             for (int t = 0; t < kGsegHalfTaps; ++t) {
@@ -149,6 +165,7 @@ __global__ __launch_bounds__(kGsegLocalTile) void gseg_local_kernel(const int32_
                 const int u = row[t];
                 if (u < base || u >= v) continue;        // the tile's own taps: base <= u < v (< ne); the rest is the link's
                 if (lab_s[u - (int)base] != c) continue;
+                if (!rule.join(v, u)) continue;
                 r = gseg_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent_s, r, u - (int)base);
             }
         }
@@ -165,16 +182,29 @@ __global__ __launch_bounds__(kGsegLocalTile) void gseg_local_kernel(const int32_
         }
         __syncthreads();                                 // before the next tile takes the arrays
     }
+    rule.done();
 }
 
-__global__ __launch_bounds__(kGsegThreads) void gseg_link_kernel(const int32_t *neigh, const int32_t *lab, int32_t *parent,
-                                                                 const int32_t *grid_stats, int M, unsigned tapmask)
+__global__ __launch_bounds__(kGsegLocalTile) void gseg_local_kernel(const int32_t *neigh, const int32_t *voxel_labels, int L,
+                                                                    const int32_t *grid_stats, int M, int num_class,
+                                                                    unsigned tapmask, int32_t *lab, int32_t *parent,
+                                                                    int32_t *seg_root, int32_t *seg_size, int32_t *seg_rows,
+                                                                    int32_t *seg_label, int32_t *seg_stats)
+{
+    gseg_local_body(LabelsJoin(), neigh, voxel_labels, L, grid_stats, M, num_class, tapmask, lab, parent, seg_root, seg_size,
+                    seg_rows, seg_label, seg_stats);
+}
+
+template <typename Join>
+__device__ __forceinline__ void gseg_link_body(Join rule, const int32_t *neigh, const int32_t *lab, int32_t *parent,
+                                               const int32_t *grid_stats, int M, unsigned tapmask)
 {
     const int ne = gseg_ne(grid_stats, M);
     for (long long w = (long long)blockIdx.x * kGsegThreads + threadIdx.x; w < ne; w += (long long)gridDim.x * kGsegThreads) {
         const int v = (int)w;
         const int lv = lab[v];
         if (lv < 0) continue;
+        rule.enter(v);
         const int32_t *row = neigh + (size_t)v * kInterpNeigh;
         const int base = v / kGsegLocalTile * kGsegLocalTile;
         int r = v;                                       // v's set, followed from link to link: most taps find it joined
@@ -184,9 +214,17 @@ __global__ __launch_bounds__(kGsegThreads) void gseg_link_kernel(const int32_t *
             if (u < 0 || u >= ne || u == v) continue;   // S2
             if (u >= base && u < v) continue;            // joined in the tile already
             if (lab[u] != lv) continue;
+            if (!rule.join(v, u)) continue;
             r = gseg_union<__HIP_MEMORY_SCOPE_AGENT>(parent, r, u);
         }
     }
+    rule.done();
+}
+
+__global__ __launch_bounds__(kGsegThreads) void gseg_link_kernel(const int32_t *neigh, const int32_t *lab, int32_t *parent,
+                                                                 const int32_t *grid_stats, int M, unsigned tapmask)
+{
+    gseg_link_body(LabelsJoin(), neigh, lab, parent, grid_stats, M, tapmask);
 }
 
 __global__ __launch_bounds__(kGsegThreads) void gseg_flatten_kernel(const int32_t *lab, int32_t *parent, int M, int ntiles,

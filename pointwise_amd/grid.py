@@ -1,6 +1,7 @@
 """Voxel-grid subsampling of a cloud, and voxel predictions carried back to every raw row (include/conv3p.h:
 conv3p_grid_subsample_f32, conv3p_grid_project_labels, conv3p_grid_neighbors, conv3p_grid_interpolate_f32 / _i64,
 conv3p_grid_interpolate_rings_f32 / _i64, conv3p_grid_normals_f32, conv3p_grid_segments, conv3p_grid_absorb_segments,
+conv3p_grid_segments_smooth, conv3p_grid_segment_pool_f32 / _i64 (kernels in csrc/conv3p_grid_smooth.hpp),
 conv3p_grid_segment_geometry, conv3p_grid_segment_adjacency, conv3p_grid_merge_segments; kernels in csrc/conv3p_grid.hpp,
 csrc/conv3p_grid_interp.hpp, csrc/conv3p_grid_interp_rings.hpp, csrc/conv3p_grid_normals.hpp,
 csrc/conv3p_grid_segments.hpp, csrc/conv3p_grid_geometry.hpp and csrc/conv3p_grid_adjacency.hpp).
@@ -23,7 +24,11 @@ tests/grid_ref.py restates it in numpy.
     GridSubsample.with_normals  data and those normals side by side, (M, K + 3): what scene_blocks takes in place of data
     GridSubsample.segments      voxel labels -> GridSegments: the connected pieces of one class over the 27-cell table (a
                      lock-free union-find), their root, size, rows and label (tests/grid_segments_ref.py);
-                     GridSegments.absorb / GridSubsample.clean_labels: pieces below a size take the label around them
+                     GridSegments.absorb / GridSubsample.clean_labels: pieces below a size take the label around them;
+                     with normals= / features=: smooth segments, joined only where the normals, the curvature and the
+                     features agree across the contact -- planes and patches (tests/grid_smooth_ref.py)
+    GridSegments.pool           a row of values per voxel -> SegmentPool: exact int64 fixed-point sums per segment, their
+                     mean, the class they vote for and that class per voxel (tests/grid_smooth_ref.py)
     GridSegments.geometry       -> SegmentGeometry: per segment the box of its cells and of its representatives, the exact
                      integer moments of its cells, the centroid, the principal axes and the oriented extents
                      (tests/grid_geometry_ref.py): a list of objects from a labelled scan
@@ -327,7 +332,8 @@ class GridSubsample:
         parts = [self.data, nrm.normals] + ([nrm.curvature[:, None]] if curvature else [])
         return torch.cat(parts, dim=1).contiguous()
 
-    def segments(self, voxel_labels=None, num_class=None, connectivity=26, out=None):
+    def segments(self, voxel_labels=None, num_class=None, connectivity=26, out=None, *, normals=None, max_angle=None,
+                 signed=False, max_curvature=None, features=None, max_difference=None):
         """The connected segments of a label per voxel -> GridSegments: voxels are joined when they are neighbours under
         the connectivity (6: faces, 18: and edges, 26: and corners of the 27 cells of neighbors()) and carry the same
         label; a segment's number is its rank by lowest voxel, so for one class it is scipy.ndimage.label's numbering
@@ -339,10 +345,31 @@ class GridSubsample:
         of an earlier call with the same number of rows.  Works on a trimmed object and on the many-clouds result as they
         stand: the table is per room, so no segment crosses a room, the numbers run room after room and a segment's room
         is voxel_room[root].  g.project(seg.segment) gives the segment number of every raw row.  Seven launches whatever
-        the data (and the neighbour table's on first use), nothing synchronised on."""
+        the data (and the neighbour table's on first use), nothing synchronised on.
+
+        Smooth segments (include/conv3p.h: conv3p_grid_segments_smooth, rules J1-J5; tests/grid_smooth_ref.py): with
+        normals= or features= two neighbours of one label are joined only when the surface is smooth across the contact,
+        so a floor and its walls, or two tables that touch, come apart.  normals: the GridNormals of normals() -- its
+        normals, flags and curvature are read -- or a contiguous float32 (M, 3) tensor on the device (no flags, and
+        max_curvature is then refused); max_angle, in degrees in [0, 180], is required with it, and the pair passes when
+        the dot product d of the two normals (|d| unless signed=True) satisfies d >= min_cos with
+
+            min_cos = np.float32(math.cos(math.radians(max_angle)))
+
+        computed on the host; that line is part of the definition.  A voxel without a normal (flags != 0, or a non-finite
+        component) joins nobody and is a segment of its own.  max_curvature: both voxels' curvature must be at most it.
+        features: a float32 (M, F <= 16) tensor on the device whose rows may be strided (a column slice such as
+        g.data[:, 3:6]: its row stride is passed); it requires max_difference >= 0, and every channel of the pair must
+        differ by at most that.  The result carries smooth_stats int64 (8) on the device = {candidate pairs, joined,
+        refused for a missing normal, by angle, by curvature, by features, labelled voxels without a normal, 0}.  The same
+        seven launches behind a 64-byte memset.  geometry(), adjacency(), merge(), pool() and g.project(seg.segment) work
+        on it as on any other; absorb() and clean_labels() do not: rule A2 assumes that neighbours of one class share a
+        segment.  Small patches are folded in with adjacency() and merge() (README: smooth segments).  With all six
+        keywords at their defaults the call is the plain one, argument for argument."""
         dev = self.voxel_count.device
         M = self.voxel_count.shape[0]
         L = _check_segment_arguments(voxel_labels, num_class, connectivity, M, dev)
+        smooth = _check_smooth_arguments(normals, max_angle, signed, max_curvature, features, max_difference, M, dev)
         _require(_is_tensor(self.voxel_count, torch.int32) and tuple(self.voxel_cell.shape) == (M, 3),
                  "voxel_count must be a contiguous int32 (M,) tensor beside voxel_cell (M, 3)")
         if out is not None:
@@ -354,17 +381,28 @@ class GridSubsample:
         out._source = (self, voxel_labels, L, 1 if voxel_labels is None else num_class, connectivity)
         if out._merged:                                  # an object merge() wrote into earlier: a plain segmentation again
             del out._merged, out.seg_map, out.merge_stats
+        out._smooth = smooth is not None                 # absorb() asks
+        if smooth is None:
+            out.smooth_stats = None
+        elif out.smooth_stats is None:
+            out.smooth_stats = torch.zeros((8,), dtype=torch.int64, device=dev)
         if M == 0:
             out.stats.zero_()
+            if smooth is not None:
+                out.smooth_stats.zero_()
             return out
         lib = _lib.load()
         ws = _grow(out, "workspace", int(lib.conv3p_grid_segments_workspace_bytes(M)), dev)
         neigh = self.neighbors()
+        plain = (neigh.data_ptr(), _labels_pointer(voxel_labels, L, out.segment), L, self.voxel_count.data_ptr(),
+                 self.stats.data_ptr(), M, out._source[3], connectivity, out.segment.data_ptr(), out.root.data_ptr(),
+                 out.size.data_ptr(), out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr())
         with torch.cuda.device(dev):
-            _call(lib.conv3p_grid_segments, neigh.data_ptr(), _labels_pointer(voxel_labels, L, out.segment), L,
-                  self.voxel_count.data_ptr(), self.stats.data_ptr(), M, out._source[3], connectivity, out.segment.data_ptr(),
-                  out.root.data_ptr(), out.size.data_ptr(), out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr(),
-                  ws.data_ptr(), ws.numel(), _stream(dev))
+            if smooth is None:
+                _call(lib.conv3p_grid_segments, *plain, ws.data_ptr(), ws.numel(), _stream(dev))
+            else:
+                _call(lib.conv3p_grid_segments_smooth, *plain, *smooth, out.smooth_stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                      _stream(dev))
         return out
 
     def clean_labels(self, voxel_labels, num_class, min_size, connectivity=26, drop_orphans=False):
@@ -393,6 +431,58 @@ def _check_segment_arguments(voxel_labels, num_class, connectivity, M, dev):
     return L
 
 
+def _is_real(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and not math.isnan(v)
+
+
+def _check_smooth_arguments(normals, max_angle, signed, max_curvature, features, max_difference, M, dev):
+    """The checks of the six smooth keywords of GridSubsample.segments -> None with all of them at their defaults (the
+    plain call), else conv3p_grid_segments_smooth's arguments from normals to max_difference.  The tuple holds addresses
+    of the arguments' own tensors: nothing is copied."""
+    _require(isinstance(signed, bool), "signed must be a bool")
+    if normals is None:
+        _require(max_angle is None, "max_angle needs normals=")
+        _require(max_curvature is None, "max_curvature needs normals= (a GridNormals)")
+        _require(not signed, "signed needs normals=")
+    if features is None:
+        _require(max_difference is None, "max_difference needs features=")
+    if normals is None and features is None:
+        return None
+    nrm = flags = curv = None
+    min_cos = 0.0
+    if normals is not None:
+        if isinstance(normals, GridNormals):
+            nrm, flags, curv = normals.normals, normals.flags, normals.curvature
+            _require(_is_tensor(nrm, torch.float32, (M, 3), dev) and _is_tensor(flags, torch.int32, (M,), dev)
+                     and _is_tensor(curv, torch.float32, (M,), dev),
+                     "normals was made for another subsampling (%d voxels here)" % M)
+        else:
+            _require_tensor(normals, "normals must be the GridNormals of normals() or a contiguous float32 (M, 3) tensor on "
+                            "the cloud's device (%d voxels here)" % M, torch.float32, (M, 3), dev)
+            _require(max_curvature is None, "max_curvature needs the curvature of a GridNormals: normals= is a bare tensor")
+            nrm = normals
+        _require(_is_real(max_angle) and 0 <= max_angle <= 180, "max_angle, in degrees in [0, 180], is required with normals=")
+        min_cos = float(np.float32(math.cos(math.radians(max_angle))))
+        if max_curvature is None:
+            curv = None
+        else:
+            _require(_is_real(max_curvature) and not math.isnan(float(np.float32(max_curvature))),
+                     "max_curvature must be None or a number")
+    F = stride = 0
+    if features is not None:
+        _require(_is_tensor(features, torch.float32, dev=dev, ndim=2, contiguous=False) and features.shape[0] == M
+                 and 1 <= features.shape[1] <= 16,
+                 "features must be a float32 (M, 1 <= F <= 16) tensor on the cloud's device (%d voxels here)" % M)
+        F = features.shape[1]
+        stride = features.stride(0) if M > 1 else F      # a single row has no stride to speak of
+        _require((F == 1 or features.stride(1) == 1) and stride >= F,
+                 "features must have contiguous rows (a column slice of a contiguous tensor is fine)")
+        _require(_is_real(max_difference) and max_difference >= 0 and not math.isnan(float(np.float32(max_difference))),
+                 "max_difference >= 0 is required with features=")
+    return (_ptr(nrm), _ptr(flags), _ptr(curv), min_cos, int(signed), float(max_curvature) if curv is not None else 0.0,
+            _ptr(features), F, stride, float(max_difference) if features is not None else 0.0)
+
+
 def _labels_pointer(voxel_labels, L, stand_in):
     """The labels' address for the C entries, where NULL means "no labels": an EMPTY labels tensor, whose own address may
     be NULL, goes in as another valid address with L = 0, of which nothing is read."""
@@ -409,10 +499,13 @@ class GridSegments:
     clean-up, and absorb_stats int64 (4) = {small segments, absorbed, orphans, voxels whose label changed}.  On the object
     merge() returned: seg_map int32 (M), the new number of every segment of the object it was called on (-1 past its
     last one), and merge_stats int32 (4) = {groups, segments, active pairs with a != b, groups of more than one
-    segment}."""
+    segment}.  On the object segments(normals=... / features=...) returned: smooth_stats int64 (8) = {candidate pairs,
+    joined, refused for a missing normal, by angle, by curvature, by features, labelled voxels without a normal, 0}."""
 
     seg_map = merge_stats = None                         # set on the object merge() returns, and on no other
     _merged = False
+    smooth_stats = None                                  # set by segments(normals= / features=), and by no other call
+    _smooth = False
 
     def __init__(self, num_voxels, device):
         M = int(num_voxels)
@@ -441,6 +534,8 @@ class GridSegments:
                   ("segment", "stats", "absorb_stats"), shape=self.shape, workspace=None, _absorb_workspace=None, _source=None)
         if self._merged:                                 # seg_map is a row per segment of the object merge() was called on
             t._merged, t.seg_map, t.merge_stats = True, self.seg_map, self.merge_stats
+        if self._smooth:
+            t._smooth, t.smooth_stats = True, self.smooth_stats
         return t
 
     def absorb(self, min_size, drop_orphans=False, out=None):
@@ -457,6 +552,8 @@ class GridSegments:
         _require(self._source is not None, "absorb works on the object segments() returned, not on its trim()")
         _require(not self._merged, "absorb works on what segments() returned: a merged segment may hold "
                  "several classes, which rule A2 excludes")
+        _require(not self._smooth, "absorb works on what the plain segments() returned: in a smooth segmentation neighbours of "
+                 "one class lie in different segments, which rule A2 excludes; fold small patches in with adjacency() and merge()")
         grid, voxel_labels, L, num_class, connectivity = self._source
         dev = self.segment.device
         M = self.shape[0]
@@ -526,6 +623,58 @@ class GridSegments:
                   grid.stats.data_ptr(), M, _GEOMETRY_WEIGHTS[weight], out.cell_box.data_ptr(), out.box.data_ptr(),
                   out.moments.data_ptr(), out.centroid.data_ptr(), out.eigenvalues.data_ptr(), out.axes.data_ptr(),
                   out.extent.data_ptr(), out.stats.data_ptr(), _stream(dev))
+        return out
+
+    def pool(self, values, weight="voxels", return_mean=True, out=None):
+        """A row of values per voxel summed over every segment -> SegmentPool: exact int64 fixed-point sums, their weight,
+        the mean and the class the sums vote for, per segment, and that class per voxel (include/conv3p.h:
+        conv3p_grid_segment_pool_f32 / _i64, rules P1-P6; tests/grid_smooth_ref.py).
+
+        values: a float32 or int64 (L <= M, C <= 128) tensor on the device, for example nrm.normals, g.data[:, 3:6] or
+        SceneScores.scores.  Its rows may be strided -- a column slice of a contiguous tensor goes in as it is, its row
+        stride is passed -- but a row's channels must be contiguous.  A float32 value x counts as llrint(x * 2^30); a
+        voxel with a non-finite value or one beyond |x| <= 256, and a voxel past L, does not contribute.  int64 values are
+        summed as they are (SceneScores' sums are in the same fixed point) and take weight "voxels" only.  weight
+        "voxels": every voxel counts once; "rows": as its voxel_count raw rows.  mean = sums / (weights * 2^30), float64,
+        None with return_mean=False.  label: the channel with the largest sum, the lowest on a tie, -1 for a segment
+        without a contributor or with all sums 0; voxel_label: that per voxel, -1 outside every segment, so
+        g.project(pool.voxel_label) labels every raw row by its patch -- the "superpoint" clean-up of a prediction.  Works
+        on what segments(), the smooth call and merge() returned, on a trimmed GridSubsample and on the many-clouds
+        result; not on a trim() of the segments.  out: a SegmentPool of an earlier call with the same shapes.  Four
+        launches whatever the data, no workspace, nothing synchronised on."""
+        _require(isinstance(weight, str) and weight in _GEOMETRY_WEIGHTS, "weight must be \"voxels\" or \"rows\"")
+        _require(isinstance(return_mean, bool), "return_mean must be a bool")
+        _require(self._source is not None, "pool works on the object segments() or merge() returned, not on its trim()")
+        grid = self._source[0]
+        dev = self.segment.device
+        M = self.shape[0]
+        _require(_is_tensor(values, (torch.float32, torch.int64), dev=dev, ndim=2, contiguous=False) and values.shape[0] <= M
+                 and 1 <= values.shape[1] <= 128,
+                 "values must be a float32 or int64 (L <= %d, 1 <= C <= 128) tensor on the segments' device" % M)
+        L, C = values.shape
+        stride = values.stride(0) if L > 1 else C
+        _require((C == 1 or values.stride(1) == 1) and stride >= C,
+                 "values must have contiguous rows (a column slice of a contiguous tensor is fine)")
+        _require(values.dtype == torch.float32 or weight == "voxels", "int64 values take weight \"voxels\" only")
+        _require_table(dev, (("voxel_count", grid.voxel_count, (M,)), ("stats", grid.stats, (8,)), ("segment", self.segment, (M,)),
+                             ("stats", self.stats, (8,))))
+        if out is not None:
+            _require(isinstance(out, SegmentPool) and out.shape == (M, C, return_mean) and out.sums.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", _NO_CPU)
+        if out is None:
+            out = SegmentPool(M, C, return_mean, dev)
+        out._segments = self
+        if M == 0:
+            out.stats.zero_()
+            return out
+        lib = _lib.load()
+        entry = lib.conv3p_grid_segment_pool_f32 if values.dtype == torch.float32 else lib.conv3p_grid_segment_pool_i64
+        with torch.cuda.device(dev):
+            _call(entry, _ptr(values), L, C, stride, self.segment.data_ptr(), self.stats.data_ptr(),
+                  grid.voxel_count.data_ptr(), grid.stats.data_ptr(), M, _GEOMETRY_WEIGHTS[weight], out.sums.data_ptr(),
+                  out.weights.data_ptr(), _ptr(out.mean), out.label.data_ptr(), out.voxel_label.data_ptr(),
+                  out.stats.data_ptr(), _stream(dev))
         return out
 
     def adjacency(self, connectivity=None, max_edges=None, out=None):
@@ -618,6 +767,7 @@ class GridSegments:
             out = GridSegments(M, dev)
         out._source = (self._source[0], None, 0, self._source[3], self._source[4])
         out._merged = True
+        out._smooth, out.smooth_stats = False, None
         if out.seg_map is None:
             out.seg_map = torch.empty((M,), dtype=torch.int32, device=dev)
             out.merge_stats = torch.zeros((4,), dtype=torch.int32, device=dev)
@@ -695,6 +845,36 @@ class SegmentAdjacency:
 
 
 _GEOMETRY_WEIGHTS = {"voxels": 0, "rows": 1}
+
+
+class SegmentPool:
+    """The outputs of GridSegments.pool, a row per segment: sums int64 (M, C), the fixed-point sums (a float32 value x
+    counts as llrint(x * 2^30) times the voxel's weight); weights int64 (M), the summed weights of the contributors; mean
+    float64 (M, C) = sums / (weights * 2^30), or None; label int32 (M), the channel with the largest sum, the lowest on a
+    tie, -1 without a contributor or with all sums 0; and per voxel voxel_label int32 (M) = label[segment], -1 outside
+    every segment.  stats int64 (4) on the device = {voxels that contributed, members that did not, segments with a
+    label, segments without}.  Rows past the last segment hold 0 and label -1."""
+
+    def __init__(self, num_voxels, channels, with_mean, device):
+        M, C = int(num_voxels), int(channels)
+        self.shape = (M, C, bool(with_mean))
+        self.sums = torch.empty((M, C), dtype=torch.int64, device=device)
+        self.weights = torch.empty((M,), dtype=torch.int64, device=device)
+        self.mean = torch.empty((M, C), dtype=torch.float64, device=device) if with_mean else None
+        self.label = torch.empty((M,), dtype=torch.int32, device=device)
+        self.voxel_label = torch.empty((M,), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((4,), dtype=torch.int64, device=device)
+        self._segments = None
+
+    def num_segments(self):
+        """The number of segments of the segmentation that was pooled: a host read (a synchronisation)."""
+        return self._segments.num_segments()
+
+    def trim(self):
+        """Views of the first num_segments() rows, as a SegmentPool (voxel_label and stats shared)."""
+        S = self.num_segments()
+        return _view(self, SegmentPool, slice(S), ("sums", "weights", "mean", "label"), ("voxel_label", "stats", "_segments"),
+                     shape=(S,) + self.shape[1:])
 
 
 class SegmentGeometry:
