@@ -59,6 +59,14 @@ def _ptr(t, when=True):
     return t.data_ptr() if when and t is not None and t.numel() else None
 
 
+def _upload(host, dev):
+    """A small CPU tensor a call was given as host data -> its copy on `dev`, enqueued on the current stream without the
+    host waiting for the device (the stream contract): the values are staged in pinned memory and
+    copied from there asynchronously; torch's pinned allocator keeps the staging block until the copy's event has passed.
+    A pageable .to(dev) would be followed by a stream synchronise."""
+    return host.pin_memory().to(dev, non_blocking=True)
+
+
 def _workspace(dev, nbytes, pool):
     """The caller-owned workspace of the C ABI: pool's growing scratch buffer for (device, current stream).  A pool is a
     dict its module owns; the conv3p op and the heads keep separate ones."""

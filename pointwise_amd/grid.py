@@ -75,7 +75,7 @@ import torch
 
 from . import _lib
 from ._host import (_LABEL_DTYPES, _call, _fill_empty, _grow, _is_int, _is_tensor, _ptr, _require, _require_int,
-                    _require_tensor, _stream, _view)
+                    _require_tensor, _stream, _upload, _view)
 
 _VIEWPOINT = "viewpoint must be None, three finite numbers, or a float32 (1, 3) or (R, 3) tensor on the cloud's device"
 _MODES = {"mean": _lib.GRID_MEAN, "center": _lib.GRID_CENTER}
@@ -269,7 +269,7 @@ class GridSubsample:
         conv3p_grid_normals_f32, rules R1-R6; tests/grid_normals_ref.py).
 
         viewpoint: None -- the normal's component of largest magnitude is made positive; a sequence of three finite
-        numbers (uploaded as a (1, 3) tensor) or a contiguous float32 (1, 3) tensor on the device -- every normal turned
+        numbers (uploaded as a (1, 3) tensor through pinned memory, on the current stream) or a contiguous float32 (1, 3) tensor on the device -- every normal turned
         towards that point; on a GridRoomSubsample also a contiguous float32 (R, 3) tensor on the device, a point per
         room.  A voxel with fewer than min_neighbors (3 .. 27) occupied cells around it, itself included, gets flags 1 and
         a zero normal; flags 2 marks degenerate moments, -1 the filler rows past the emitted voxels.  return_moments: also
@@ -309,7 +309,7 @@ class GridSubsample:
             out.stats.zero_()
             return out
         if upload is not None:
-            viewpoint = torch.tensor([upload], dtype=torch.float32, device=dev)
+            viewpoint = _upload(torch.tensor([upload], dtype=torch.float32), dev)
         neigh = self.neighbors()
         with torch.cuda.device(dev):
             _call(_lib.load().conv3p_grid_normals_f32, self.data.data_ptr(), K, neigh.data_ptr(), self.stats.data_ptr(),

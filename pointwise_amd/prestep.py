@@ -23,10 +23,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._host import Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _ptr, _stream
+from ._host import Conv3pInvalidArgument, Conv3pRuntimeError, _call, _check_device, _ptr, _stream, _upload
 
 
 def _augment(batch_data, cos_sin, noise, sigma, clip):
+    """conv3p_augment_f32 on the current stream.  cos_sin is the host's (numpy draws the angles): it is uploaded through
+    pinned memory without a synchronisation."""
     lib = _lib.load()
     dev = _check_device(batch_data)
     if batch_data.dim() != 3 or batch_data.shape[2] != 3 or batch_data.dtype != torch.float32:
@@ -36,7 +38,7 @@ def _augment(batch_data, cos_sin, noise, sigma, clip):
     out = torch.empty_like(x)
     cs = None
     if cos_sin is not None:
-        cs = torch.as_tensor(np.ascontiguousarray(cos_sin, dtype=np.float64)).to(dev)
+        cs = _upload(torch.as_tensor(np.ascontiguousarray(cos_sin, dtype=np.float64)), dev)
         if tuple(cs.shape) != (B, 2):
             raise Conv3pInvalidArgument("one rotation per cloud expected")
     if noise is not None:

@@ -53,7 +53,7 @@ import torch
 
 from . import _lib
 from ._host import (_LABEL_DTYPES, _call, _fill_empty, _grow, _is_tensor, _ptr, _require, _require_int, _require_tensor,
-                    _stream, _view)
+                    _stream, _upload, _view)
 
 
 def default_max_blocks(num_rows, block=1.0, stride=1.0, min_points=100, num_point=None):
@@ -191,7 +191,7 @@ def _blocks(many, data, room_start, labels, num_point, block, stride, min_points
         _grow(out, "workspace", need, dev)
     if many:
         out._room_blocks_host = None
-        out.room_start = torch.from_numpy(rs.astype(np.int32)).to(dev) if rs is not None else room_start
+        out.room_start = _upload(torch.from_numpy(rs.astype(np.int32)), dev) if rs is not None else room_start
     if N == 0 or max_blocks == 0 or R == 0:  # nothing is launched, so nothing is written
         _fill_empty(out)
         return out
@@ -283,7 +283,7 @@ def scene_blocks_rooms(data, room_start, labels=None, num_point=4096, block=1.0,
     data float32 (N, K >= 3), the rooms' rows one room after the other; labels (N) or None.  room_start: the R + 1
     boundaries.  A device int32 tensor is used as is (a malformed one is reported in stats[7], bit 1); a Python
     sequence, numpy array or CPU tensor is checked here (ascending, inside [0, N], rooms of at most 2^24 rows) and copied
-    once.  max_blocks=None: default_max_blocks summed per room when the host knows room_start, otherwise a bound from N
+    once, through pinned memory on the current stream.  max_blocks=None: default_max_blocks summed per room when the host knows room_start, otherwise a bound from N
     and R alone; neither synchronises.  That second bound is very loose -- R + min(65536 R, N m^2 // min_points) + N m^2
     // num_point blocks, and the outputs are allocated for it: 4 M rows at stride 0.5 ask for tens of GB -- so a caller
     with a device room_start should pass max_blocks (from the rooms' extents, or from a first call with max_blocks=1
