@@ -13,14 +13,16 @@
 //                             tiles' finite rows -> where a tile's pairs start; M pairs, T sort tiles, the passes the
 //                             cell ids need (ceil(bits of cells - 1 / 8): the passes above are skipped by this word)
 //   grid_pairs_kernel         the same tiles again: the pairs in row order; inverse = -1 for a row without a pair
-//   5 x { grid_sort_hist_kernel     per sort tile of 4096 pairs a histogram of 8 bits of the cell id
+//   5 x { grid_sort_hist_kernel     per sort tile of 4096 pairs a histogram of 8 bits of the cell id (radix_hist_tile)
 //         grid_sort_scan_kernel     a workgroup per digit: prefix over (digit, tile) from the digits' totals
-//         grid_sort_scatter_kernel  one WAVE per sort tile, 64 pairs a step in order, as rooms_sort_scatter_kernel: the
-//                                   lanes of equal digit from eight ballots, rank = popcount below the lane }
+//                                   (radix_digit_scan)
+//         grid_sort_scatter_kernel  one WAVE per sort tile, 64 pairs a step in order (radix_scatter_tile): the lanes of
+//                                   equal digit from eight ballots, rank = popcount below the lane }
 //                             pass p reads buffer p & 1 and writes the other; a skipped pass returns at once, so the
 //                             sorted pairs are in buffer passes & 1
 //   grid_heads_kernel<0>      per sort tile the pairs whose cell differs from the pair before: the lists' heads
-//   grid_heads_scan_kernel    one workgroup: prefix of the tiles' heads -> voxel numbers; occupied and emitted voxels
+//   grid_heads_scan_kernel    one workgroup: prefix of the tiles' heads (wg_exscan_inplace) -> voxel numbers; occupied
+//                             and emitted voxels
 //   grid_heads_kernel<1>      the same tiles again: start[v] = the position of voxel v's head; start[V] = M
 //   grid_voxel_kernel         eight lanes per voxel: count, cell, inverse of every member; mean: voxel_row and the majority
 //                             label by the group's LDS histogram; centre: the representative, its row copied
@@ -29,7 +31,8 @@
 //   grid_stats_kernel         one workgroup: the largest member count from the voxel kernel's partial maxima; stats
 //
 // No float atomics (the only atomics are integer adds: the two LDS histograms and a pass's totals per digit); every output word is written once by a
-// plain store; the result does not depend on the launch geometry.
+// plain store; the result does not depend on the launch geometry.  The scans, the radix pass and the bounding-box
+// records are conv3p_workgroup.hpp's.
 #pragma once
 
 #include "conv3p_scene_rooms.hpp"
@@ -96,30 +99,15 @@ __global__ __launch_bounds__(kSceneThreads) void grid_bounds_kernel(const GridAr
     const int tid = threadIdx.x, tile = blockIdx.x;
     const int t0 = tile * kGridRowTile, t1 = t0 + kGridRowTile < p.N ? t0 + kGridRowTile : p.N;
     SceneRange g;
-    for (int e = 0; e < 3; ++e) {
-        g.lo[e] = INFINITY;
-        g.hi[e] = -INFINITY;
-    }
-    g.bad = 0;
+    range_init(g);
     for (int i = t0 + tid; i < t1; i += kSceneThreads) {
         const float *v = p.data + (size_t)i * p.K;
-        const float x = v[0], y = v[1], z = v[2];
-        if (scene_finite(x, y, z)) {
-            g.lo[0] = fminf(g.lo[0], x); g.hi[0] = fmaxf(g.hi[0], x);
-            g.lo[1] = fminf(g.lo[1], y); g.hi[1] = fmaxf(g.hi[1], y);
-            g.lo[2] = fminf(g.lo[2], z); g.hi[2] = fmaxf(g.hi[2], z);
-        } else {
-            g.bad += 1;
-        }
+        range_add(g, v[0], v[1], v[2]);
     }
     g = scene_reduce(g, red, tid, kSceneThreads);
     if (tid == 0) {
         float *w = p.records + (size_t)tile * 8;
-        for (int e = 0; e < 3; ++e) {
-            w[e] = g.lo[e];
-            w[3 + e] = g.hi[e];
-        }
-        w[6] = __int_as_float(g.bad);
+        range_store(g, w);
         w[7] = 0.0f;
     }
 }
@@ -128,31 +116,22 @@ __global__ __launch_bounds__(kGridScanThreads) void grid_frame_kernel(const Grid
 {
     __shared__ float red[(kGridScanThreads / 64) * 7];
     __shared__ int scan_s[kGridScanThreads / 64];
-    const int tid = threadIdx.x, n = p.row_tiles;
-    const int per = (n + kGridScanThreads - 1) / kGridScanThreads;
-    const int a = tid * per < n ? tid * per : n, b = a + per < n ? a + per : n;
+    const int tid = threadIdx.x;
+    int a, b;
+    wg_chunk(p.row_tiles, kGridScanThreads, tid, &a, &b);
     for (int e = tid; e < kGridPasses * kGridDigits; e += kGridScanThreads) p.digit_total[e] = 0;
     SceneRange g;
-    for (int e = 0; e < 3; ++e) {
-        g.lo[e] = INFINITY;
-        g.hi[e] = -INFINITY;
-    }
-    g.bad = 0;
+    range_init(g);
     int fin = 0;                                         // the finite rows of this thread's tiles
     for (int t = a; t < b; ++t) {
         const float *w = p.records + (size_t)t * 8;
-        for (int e = 0; e < 3; ++e) {
-            g.lo[e] = fminf(g.lo[e], w[e]);
-            g.hi[e] = fmaxf(g.hi[e], w[3 + e]);
-        }
-        const int bad = __float_as_int(w[6]);
         const int rows = (t + 1) * kGridRowTile <= p.N ? kGridRowTile : p.N - t * kGridRowTile;
-        g.bad += bad;
-        fin += rows - bad;
+        range_fold(g, w);
+        fin += rows - __float_as_int(w[6]);
     }
     g = scene_reduce(g, red, tid, kGridScanThreads);
     int total;
-    int run = scene_exscan(fin, scan_s, tid, kGridScanThreads, &total);
+    int run = wg_exscan(fin, scan_s, tid, kGridScanThreads, &total);
     for (int t = a; t < b; ++t) {
         const float *w = p.records + (size_t)t * 8;
         const int rows = (t + 1) * kGridRowTile <= p.N ? kGridRowTile : p.N - t * kGridRowTile;
@@ -165,9 +144,8 @@ __global__ __launch_bounds__(kGridScanThreads) void grid_frame_kernel(const Grid
         long long cells = any ? 1 : 0;
         bool over = false;
         for (int e = 0; e < 3; ++e) {
-            // fminf is the device's min instruction, which takes -0.0 as below +0.0, so a zero minimum has one sign
-            // whatever the order of the reduction.  s and the quotient are monotone in v, so the largest cell along an
-            // axis is the cell of the largest coordinate.
+            // a zero minimum has one sign whatever the order of the reduction (see SceneRange).  s and the quotient are
+            // monotone in v, so the largest cell along an axis is the cell of the largest coordinate.
             h.lo[e] = any ? g.lo[e] : 0.0f;
             h.n[e] = any ? grid_axis_cell(g.hi[e] - g.lo[e], p.voxel) + 1 : 0;
             if (h.n[e] > kGridMaxAxis) over = true;
@@ -217,7 +195,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_pairs_kernel(const GridArg
         }
     }
     int total;
-    int pos = p.tile_off[tile] + scene_exscan(n, scan_s, tid, kSceneThreads, &total);
+    int pos = p.tile_off[tile] + wg_exscan(n, scan_s, tid, kSceneThreads, &total);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (has[k] && pos < h.pairs) p.pairs_a[pos++] = key[k];                     // pos < M <= N: the frame's prefix
@@ -231,71 +209,32 @@ __global__ __launch_bounds__(kSceneThreads) void grid_sort_hist_kernel(const Gri
     if (pass >= p.hdr->passes) return;
     const unsigned long long *src = (pass & 1) ? p.pairs_b : p.pairs_a;
     const int shift = kGridRowBits + pass * kGridDigitBits;
-    int mine = 0;                                        // this workgroup's pairs of digit tid
-    for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
-        hist_s[tid] = 0;                                 // kSceneThreads == kGridDigits
-        __syncthreads();
-        const int i0 = tile * kGridSortTile, i1 = i0 + kGridSortTile < M ? i0 + kGridSortTile : M;
-        for (int i = i0 + tid; i < i1; i += kSceneThreads) atomicAdd(&hist_s[(int)(src[i] >> shift) & (kGridDigits - 1)], 1);
-        __syncthreads();
-        p.hist[(size_t)tid * T + tile] = hist_s[tid];
-        mine += hist_s[tid];
-        __syncthreads();
-    }
+    int mine = 0;                                        // this workgroup's pairs of digit tid: kSceneThreads == kGridDigits
+    for (int tile = blockIdx.x; tile < T; tile += gridDim.x)
+        mine += radix_hist_tile<kGridDigitBits>(src, M, tile, kGridSortTile, shift, hist_s, p.hist, T, tid, kSceneThreads);
     if (mine) atomicAdd(&p.digit_total[pass * kGridDigits + tid], mine);   // integers: exact in any order
 }
 
-// A workgroup per digit: the digit's first position is the sum of the totals of the digits below it, and its row of
-// the histogram, a tile a thread, is scanned behind that -- the exclusive prefix over (digit, tile), every load coalesced.
+// A workgroup per digit: radix_digit_scan from this pass's totals.
 __global__ __launch_bounds__(kGridScanThreads) void grid_sort_scan_kernel(const GridArgs p, int pass)
 {
     __shared__ int scan_s[kGridScanThreads / 64];
-    const int tid = threadIdx.x, digit = blockIdx.x, T = p.hdr->sort_tiles;
+    const int digit = blockIdx.x, T = p.hdr->sort_tiles;
     if (pass >= p.hdr->passes) return;
-    int run;
-    (void)scene_exscan(tid < digit ? p.digit_total[pass * kGridDigits + tid] : 0, scan_s, tid, kGridScanThreads, &run);
-    int *row = p.hist + (size_t)digit * T;
-    for (int t0 = 0; t0 < T; t0 += kGridScanThreads) {
-        const int t = t0 + tid;
-        int total;
-        const int before = scene_exscan(t < T ? row[t] : 0, scan_s, tid, kGridScanThreads, &total);
-        if (t < T) row[t] = run + before;
-        run += total;
-    }
+    radix_digit_scan(p.digit_total + pass * kGridDigits, p.hist + (size_t)digit * T, T, digit, scan_s, threadIdx.x,
+                     kGridScanThreads);
 }
 
 __global__ __launch_bounds__(64) void grid_sort_scatter_kernel(const GridArgs p, int pass)
 {
     __shared__ int run_s[kGridDigits];
-    const int lane = threadIdx.x, M = p.hdr->pairs, T = p.hdr->sort_tiles;
+    const int M = p.hdr->pairs, T = p.hdr->sort_tiles;
     if (pass >= p.hdr->passes) return;
     const unsigned long long *src = (pass & 1) ? p.pairs_b : p.pairs_a;
     unsigned long long *dst = (pass & 1) ? p.pairs_a : p.pairs_b;
     const int shift = kGridRowBits + pass * kGridDigitBits;
-    for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
-        __syncthreads();
-        for (int d = lane; d < kGridDigits; d += 64) run_s[d] = p.hist[(size_t)d * T + tile];
-        __syncthreads();
-        const int i0 = tile * kGridSortTile, i1 = i0 + kGridSortTile < M ? i0 + kGridSortTile : M;
-        for (int c0 = i0; c0 < i1; c0 += 64) {
-            const int i = c0 + lane;
-            const bool valid = i < i1;
-            const unsigned long long v = valid ? src[i] : 0ull;
-            const int digit = (int)(v >> shift) & (kGridDigits - 1);
-            unsigned long long peer = __ballot(valid);
-            for (int bit = 0; bit < kGridDigitBits; ++bit) {
-                const bool one = (digit >> bit) & 1;
-                const unsigned long long m = __ballot(valid && one);
-                peer &= one ? m : ~m;
-            }
-            const int rank = __popcll(peer & ((1ull << lane) - 1ull));
-            const int pos = valid ? run_s[digit] + rank : 0;
-            __syncthreads();
-            if (valid && rank == 0) run_s[digit] += __popcll(peer);     // one lane per digit
-            __syncthreads();
-            if (valid && pos < M) dst[pos] = v;              // pos < M: a prefix of the M pairs' histogram
-        }
-    }
+    for (int tile = blockIdx.x; tile < T; tile += gridDim.x)
+        radix_scatter_tile<kGridDigitBits, int>(src, dst, M, tile, kGridSortTile, shift, p.hist, T, run_s, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------ lists behind the sort
@@ -321,7 +260,7 @@ template <bool kWrite> __global__ __launch_bounds__(kSceneThreads) void grid_hea
             prev = c;
         }
         int total;
-        int v = scene_exscan(n, scan_s, tid, kSceneThreads, &total);
+        int v = wg_exscan(n, scan_s, tid, kSceneThreads, &total);
         if (!kWrite) {
             if (tid == 0) p.heads[tile] = total;
         } else {
@@ -343,25 +282,16 @@ template <bool kWrite> __global__ __launch_bounds__(kSceneThreads) void grid_hea
 __global__ __launch_bounds__(kGridScanThreads) void grid_heads_scan_kernel(const GridArgs p)
 {
     __shared__ int scan_s[kGridScanThreads / 64];
-    const int tid = threadIdx.x, n = p.hdr->sort_tiles;
-    const int per = (n + kGridScanThreads - 1) / kGridScanThreads;
-    const int a = tid * per < n ? tid * per : n, b = a + per < n ? a + per : n;
-    int mine = 0;
-    for (int t = a; t < b; ++t) mine += p.heads[t];
-    int total;
-    int run = scene_exscan(mine, scan_s, tid, kGridScanThreads, &total);
-    for (int t = a; t < b; ++t) {
-        const int v = p.heads[t];
-        p.heads[t] = run;
-        run += v;
-    }
+    const int tid = threadIdx.x;
+    const int total = wg_exscan_inplace(p.heads, p.hdr->sort_tiles, scan_s, tid, kGridScanThreads);
     if (tid == 0) {
         p.hdr->occupied = total;
         p.hdr->emitted = total < p.max_voxels ? total : p.max_voxels;
     }
 }
 
-// Is the label of row idx in [0, num_class)?  Compared in the label's own width, so an int64 label is not wrapped first.
+// Is the label of row idx in [0, num_class)?  Compared in the label's own width, so an int64 label is not wrapped first
+// -- which is why this is not row_label: 2^32 + 3 is no label, and row_label makes it 3.
 __device__ __forceinline__ int grid_valid_label(const GridArgs &p, size_t idx)
 {
     long long l;
@@ -369,13 +299,6 @@ __device__ __forceinline__ int grid_valid_label(const GridArgs &p, size_t idx)
     else if (p.label_bytes == 4) l = (long long) static_cast<const int32_t *>(p.labels)[idx];
     else l = static_cast<const long long *>(p.labels)[idx];
     return l >= 0 && l < (long long)p.num_class ? (int)l : -1;
-}
-
-__device__ __forceinline__ int32_t grid_label(const GridArgs &p, size_t idx)
-{
-    if (p.label_bytes == 1) return (int32_t) static_cast<const uint8_t *>(p.labels)[idx];
-    if (p.label_bytes == 4) return static_cast<const int32_t *>(p.labels)[idx];
-    return (int32_t) static_cast<const long long *>(p.labels)[idx];
 }
 
 // The frame of one room of conv3p_grid_subsample_rooms_f32 (conv3p_grid_rooms.hpp), and what grid_voxel_body reads of
@@ -509,7 +432,7 @@ template <bool kRooms> __device__ __forceinline__ void grid_voxel_body(const Gri
                 }
             }
             rep = best_row;
-            if (p.labels) label = grid_label(p, (size_t)rep);
+            if (p.labels) label = row_label(p.labels, p.label_bytes, (size_t)rep);
             const float *q = p.data + (size_t)rep * K;
             for (int k = gl; k < K; k += kGridGroup) p.out[(size_t)v * K + k] = q[k];
         }

@@ -29,7 +29,7 @@
 //   adj_compact_kernel   the claimed keys, a wave's at a time behind one add of the wave's count: E, and the keys in SLOT
 //                        order, which is not reproducible -- the sort makes it so
 //   2 b x { adj_sort_hist_kernel, adj_sort_scan_kernel, adj_sort_scatter_kernel }
-//                        the stable 8-bit radix passes of conv3p_grid.hpp on the 64-bit keys, b passes over the bytes of
+//                        the stable 8-bit radix passes of conv3p_workgroup.hpp on the 64-bit keys, b passes over the bytes of
 //                        dst, then b over the bytes of src; a pass above the top byte of S - 1 returns at once on the
 //                        device, and since both halves skip the same number the sorted keys always end in the first
 //                        buffer.  On overflow nothing is sorted.
@@ -58,7 +58,8 @@ constexpr int kAdjThreads = 256;
 constexpr int kAdjMaxGrid = 2048;
 constexpr int kAdjVals = 5;                             // contacts, voxels, offset x y z
 constexpr int kAdjSortTile = 4096;
-constexpr int kAdjDigits = 256;
+constexpr int kAdjDigitBits = 8;
+constexpr int kAdjDigits = 1 << kAdjDigitBits;
 constexpr int kAdjScanThreads = 1024;
 constexpr int kAdjMaxBytes = 4;                         // of a segment number
 constexpr unsigned long long kAdjEmpty = ~0ull;         // no key: a and b are below 2^31
@@ -90,12 +91,6 @@ struct AdjArgs {
     unsigned long long *sort_a, *sort_b;                // (max_edges) each
     int sort_tiles;
 };
-
-__device__ __forceinline__ int adj_S(const int32_t *seg_stats, int M)
-{
-    const int S = seg_stats[0];
-    return S < 0 ? 0 : (S > M ? M : S);
-}
 
 __device__ __forceinline__ unsigned long long adj_key(int a, int b)
 {
@@ -133,13 +128,7 @@ __device__ __forceinline__ int adj_bytes(int S)
 // The first i in [0, n) with keys[i] >= key, n if there is none.
 __device__ __forceinline__ int adj_lower_bound(const unsigned long long *keys, int n, unsigned long long key)
 {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return lower_bound(0, n, [&](int m) { return keys[m] < key; });
 }
 
 __global__ __launch_bounds__(kAdjThreads) void adj_init_kernel(const AdjArgs p)
@@ -230,7 +219,7 @@ __global__ __launch_bounds__(kAdjThreads) void adj_walk_kernel(const AdjArgs p)
     claims_s[tid] = 0;
     if (tid < 2) sum_s[tid] = 0ull;
     __syncthreads();
-    const int ne = gseg_ne(p.grid_stats, p.M), S = adj_S(p.seg_stats, p.M);
+    const int ne = clamped_count(p.grid_stats, p.M), S = clamped_count(p.seg_stats, p.M);
     unsigned long long n_pairs = 0, n_contacts = 0;
     const long long waves = (long long)gridDim.x * (kAdjThreads / 64);
     for (long long c0 = ((long long)blockIdx.x * (kAdjThreads / 64) + (tid >> 6)) * 64; c0 < ne; c0 += waves * 64) {
@@ -360,7 +349,7 @@ struct AdjPass {
 };
 __device__ __forceinline__ bool adj_pass(const AdjArgs &p, int half, int j, AdjPass &q)
 {
-    const int nb = adj_bytes(adj_S(p.seg_stats, p.M));
+    const int nb = adj_bytes(clamped_count(p.seg_stats, p.M));
     const int E = adj_edges(p);
     if (j >= nb || E <= 0) return false;
     const int ordinal = half * nb + j;                   // among the passes that run: both halves run nb
@@ -379,70 +368,33 @@ __global__ __launch_bounds__(kAdjThreads) void adj_sort_hist_kernel(const AdjArg
     AdjPass q;
     if (!adj_pass(p, half, j, q)) return;
     const int tid = threadIdx.x;
-    int mine = 0;                                        // this workgroup's keys of digit tid
-    for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x) {
-        hist_s[tid] = 0;
-        __syncthreads();
-        const long long i0 = (long long)tile * kAdjSortTile, i1 = i0 + kAdjSortTile < q.n ? i0 + kAdjSortTile : q.n;
-        for (long long i = i0 + tid; i < i1; i += kAdjThreads) atomicAdd(&hist_s[(int)(q.src[i] >> q.shift) & (kAdjDigits - 1)], 1);
-        __syncthreads();
-        p.hist[(size_t)tid * p.sort_tiles + tile] = hist_s[tid];
-        mine += hist_s[tid];
-        __syncthreads();
-    }
+    int mine = 0;                                        // this workgroup's keys of digit tid: kAdjThreads == kAdjDigits
+    for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x)
+        mine += radix_hist_tile<kAdjDigitBits>(q.src, (long long)q.n, tile, kAdjSortTile, q.shift, hist_s, p.hist, p.sort_tiles, tid,
+                                               kAdjThreads);
     if (mine) atomicAdd(&p.digit_total[q.row * kAdjDigits + tid], mine);
 }
 
-// A workgroup per digit: the exclusive prefix over (digit, tile), as grid_sort_scan_kernel.
+// A workgroup per digit: radix_digit_scan from this pass's totals.
 __global__ __launch_bounds__(kAdjScanThreads) void adj_sort_scan_kernel(const AdjArgs p, int half, int j)
 {
     __shared__ int scan_s[kAdjScanThreads / 64];
     AdjPass q;
     if (!adj_pass(p, half, j, q)) return;
-    const int tid = threadIdx.x, digit = blockIdx.x;
-    int run;
-    (void)scene_exscan(tid < digit ? p.digit_total[q.row * kAdjDigits + tid] : 0, scan_s, tid, kAdjScanThreads, &run);
-    int *row = p.hist + (size_t)digit * p.sort_tiles;
-    for (int t0 = 0; t0 < q.tiles; t0 += kAdjScanThreads) {
-        const int t = t0 + tid;
-        int total;
-        const int before = scene_exscan(t < q.tiles ? row[t] : 0, scan_s, tid, kAdjScanThreads, &total);
-        if (t < q.tiles) row[t] = run + before;
-        run += total;
-    }
+    const int digit = blockIdx.x;
+    radix_digit_scan(p.digit_total + q.row * kAdjDigits, p.hist + (size_t)digit * p.sort_tiles, q.tiles, digit, scan_s,
+                     threadIdx.x, kAdjScanThreads);
 }
 
-// One wave per sort tile, 64 keys a step in order: stable, as grid_sort_scatter_kernel.
+// One wave per sort tile: radix_scatter_tile.  64-bit positions in the loop: n may be within a tile of 2^31.
 __global__ __launch_bounds__(64) void adj_sort_scatter_kernel(const AdjArgs p, int half, int j)
 {
     __shared__ int run_s[kAdjDigits];
     AdjPass q;
     if (!adj_pass(p, half, j, q)) return;
-    const int lane = threadIdx.x;
-    for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x) {
-        __syncthreads();
-        for (int d = lane; d < kAdjDigits; d += 64) run_s[d] = p.hist[(size_t)d * p.sort_tiles + tile];
-        __syncthreads();
-        const long long i0 = (long long)tile * kAdjSortTile, i1 = i0 + kAdjSortTile < q.n ? i0 + kAdjSortTile : q.n;
-        for (long long c0 = i0; c0 < i1; c0 += 64) {                        // 64-bit: n may be within a tile of 2^31
-            const long long i = c0 + lane;
-            const bool valid = i < i1;
-            const unsigned long long v = valid ? q.src[i] : 0ull;
-            const int digit = (int)(v >> q.shift) & (kAdjDigits - 1);
-            unsigned long long peer = __ballot(valid);
-            for (int bit = 0; bit < 8; ++bit) {
-                const bool one = (digit >> bit) & 1;
-                const unsigned long long m = __ballot(valid && one);
-                peer &= one ? m : ~m;
-            }
-            const int rank = __popcll(peer & ((1ull << lane) - 1ull));
-            const int pos = valid ? run_s[digit] + rank : 0;
-            __syncthreads();
-            if (valid && rank == 0) run_s[digit] += __popcll(peer);             // one lane per digit
-            __syncthreads();
-            if (valid && pos >= 0 && pos < q.n) q.dst[pos] = v;                 // a prefix of the n keys' histogram
-        }
-    }
+    for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x)
+        radix_scatter_tile<kAdjDigitBits, long long>(q.src, q.dst, q.n, tile, kAdjSortTile, q.shift, p.hist, p.sort_tiles, run_s,
+                                          threadIdx.x);
 }
 
 __global__ __launch_bounds__(kAdjThreads) void adj_finish_kernel(const AdjArgs p)
@@ -451,7 +403,7 @@ __global__ __launch_bounds__(kAdjThreads) void adj_finish_kernel(const AdjArgs p
     const int tid = threadIdx.x;
     if (tid < 2) max_s[tid] = 0;
     __syncthreads();
-    const int S = adj_S(p.seg_stats, p.M);
+    const int S = clamped_count(p.seg_stats, p.M);
     const int E = adj_edges(p), n = E < 0 ? 0 : E;       // on overflow: adj_start all 0, the rows stay filler
     const unsigned long long *keys = p.sort_a;
     int md = 0, mc = 0;
@@ -514,7 +466,7 @@ __global__ __launch_bounds__(64) void adj_stats_kernel(const AdjArgs p)
     long long *o = p.adj_stats;                          // E7
     o[0] = E;
     o[1] = (long long)h.pairs;
-    o[2] = adj_S(p.seg_stats, p.M);
+    o[2] = clamped_count(p.seg_stats, p.M);
     o[3] = (long long)h.contacts;
     o[4] = E < 0 ? 0 : h.max_degree;
     o[5] = E < 0 ? 0 : h.max_contacts;
@@ -535,7 +487,7 @@ struct MergeArgs {
 
 __global__ __launch_bounds__(kGsegThreads) void merge_init_kernel(const MergeArgs p)
 {
-    const int S = adj_S(p.seg_stats, p.M);
+    const int S = clamped_count(p.seg_stats, p.M);
     if (blockIdx.x == 0 && threadIdx.x < 8) {
         const int i = threadIdx.x;
         p.stats_out[i] = (i >= 1 && i <= 3) ? p.seg_stats[i] : 0;               // U3
@@ -560,7 +512,7 @@ __global__ __launch_bounds__(kGsegThreads) void merge_union_kernel(const MergeAr
     __shared__ int count_s;
     if (threadIdx.x == 0) count_s = 0;
     __syncthreads();
-    const int S = adj_S(p.seg_stats, p.M);
+    const int S = clamped_count(p.seg_stats, p.M);
     int n = 0;
     for (long long i = (long long)blockIdx.x * kGsegThreads + threadIdx.x; i < p.P; i += (long long)gridDim.x * kGsegThreads) {
         if (p.select && p.select[i] == 0) continue;      // U1
@@ -586,7 +538,7 @@ __global__ __launch_bounds__(kGsegThreads) void merge_number_kernel(const MergeA
             const int s = (int)w;
             const int f = (w < p.M && p.lab[s] >= 0 && p.parent[s] == s) ? 1 : 0;
             int total;
-            const int g = base + scene_exscan(f, scan_s, tid, kGsegThreads, &total);
+            const int g = base + wg_exscan(f, scan_s, tid, kGsegThreads, &total);
             if (f) {                                     // g < S' <= S
                 p.seg_map[s] = g;
                 p.root_out[g] = p.seg_root[s];
@@ -599,7 +551,7 @@ __global__ __launch_bounds__(kGsegThreads) void merge_number_kernel(const MergeA
 
 __global__ __launch_bounds__(kGsegThreads) void merge_assign_kernel(const MergeArgs p)
 {
-    const int S = adj_S(p.seg_stats, p.M);
+    const int S = clamped_count(p.seg_stats, p.M);
     for (long long w = (long long)blockIdx.x * kGsegThreads + threadIdx.x; w < S; w += (long long)gridDim.x * kGsegThreads) {
         const int s = (int)w;
         const int r = p.parent[s];                       // flattened: the group's root segment
@@ -619,7 +571,7 @@ __global__ __launch_bounds__(kGsegThreads) void merge_finish_kernel(const MergeA
     const int tid = threadIdx.x;
     if (tid < 3) red_s[tid] = 0;
     __syncthreads();
-    const int S = adj_S(p.seg_stats, p.M), groups = adj_S(p.stats_out, p.M);
+    const int S = clamped_count(p.seg_stats, p.M), groups = clamped_count(p.stats_out, p.M);
     int a = 0, b = 0, many = 0;
     for (long long w = (long long)blockIdx.x * kGsegThreads + tid; w < p.M; w += (long long)gridDim.x * kGsegThreads) {
         const int s = p.segment[w];

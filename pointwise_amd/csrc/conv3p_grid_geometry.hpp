@@ -37,12 +37,6 @@ constexpr int kGeomBoxWords = 12;      // cell min 3, cell max 3, box key min 3,
 constexpr int kGeomMoments = 10;
 constexpr int kGeomExtentWords = 6;
 
-__device__ __forceinline__ int geom_S(const int32_t *seg_stats, int M)
-{
-    const int S = seg_stats[0];
-    return S < 0 ? 0 : (S > M ? M : S);
-}
-
 // The ordered key of a float's bits and back: one map, its own inverse.
 __device__ __forceinline__ int geom_key32(int b) { return b >= 0 ? b : b ^ 0x7fffffff; }
 __device__ __forceinline__ long long geom_key64(long long b) { return b >= 0 ? b : b ^ 0x7fffffffffffffffll; }
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(kGsegThreads) void geom_box_kernel(const float *vox
                                                                 const int32_t *grid_stats, int M, int steps, int32_t *cell_box,
                                                                 int32_t *box_key)
 {
-    const int ne = gseg_ne(grid_stats, M), S = geom_S(seg_stats, M);
+    const int ne = clamped_count(grid_stats, M), S = clamped_count(seg_stats, M);
     auto op = [](int k, int a, int b) { return (k % 6) < 3 ? (a < b ? a : b) : (a > b ? a : b); };
     auto flush = [=](int s, const int (&x)[kGeomBoxWords]) {
 #pragma unroll
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(kGsegThreads) void geom_moments_kernel(const int32_
                                                                     const int32_t *cell_box, unsigned long long *moments)
 {
     using u64 = unsigned long long;
-    const int ne = gseg_ne(grid_stats, M), S = geom_S(seg_stats, M);
+    const int ne = clamped_count(grid_stats, M), S = clamped_count(seg_stats, M);
     auto op = [](int, u64 a, u64 b) { return a + b; };
     auto flush = [=](int s, const u64 (&x)[kGeomMoments]) {
 #pragma unroll
@@ -229,7 +223,7 @@ __global__ __launch_bounds__(kGsegThreads) void geom_frame_kernel(const int32_t 
     const int tid = threadIdx.x;
     if (tid < 2) count_s[tid] = 0;
     __syncthreads();
-    const int S = geom_S(seg_stats, M);
+    const int S = clamped_count(seg_stats, M);
     int n_one = 0, n_flat = 0;
     for (long long s = (long long)blockIdx.x * kGsegThreads + tid; s < M; s += (long long)gridDim.x * kGsegThreads) {
         double c0 = 0.0, c1 = 0.0, c2 = 0.0, l0 = 0.0, l1 = 0.0, l2 = 0.0;
@@ -279,7 +273,7 @@ __global__ __launch_bounds__(kGsegThreads) void geom_extent_kernel(const int32_t
                                                                    int steps, const double *centroid, const double *axes,
                                                                    long long *extent_key)
 {
-    const int ne = gseg_ne(grid_stats, M), S = geom_S(seg_stats, M);
+    const int ne = clamped_count(grid_stats, M), S = clamped_count(seg_stats, M);
     auto op = [](int k, long long a, long long b) { return k < 3 ? (a < b ? a : b) : (a > b ? a : b); };
     auto flush = [=](int s, const long long (&x)[kGeomExtentWords]) {
 #pragma unroll
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(kGsegThreads) void geom_finish_kernel(const int32_t
                                                                    int32_t *box, long long *moments, long long *extent,
                                                                    int32_t *geometry_stats)
 {
-    const int S = geom_S(seg_stats, M);
+    const int S = clamped_count(seg_stats, M);
     if (blockIdx.x == 0 && threadIdx.x == 0) geometry_stats[0] = S;
     for (long long s = (long long)blockIdx.x * kGsegThreads + threadIdx.x; s < M; s += (long long)gridDim.x * kGsegThreads) {
         const bool live = s < S && moments[s * kGeomMoments] != 0ll;

@@ -53,8 +53,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_neighbors_kernel(const int
                                                                        const int32_t *voxel_start, const int32_t *grid_stats,
                                                                        int max_voxels, int num_rooms, int32_t *neigh)
 {
-    int ne = grid_stats[0];
-    ne = ne < 0 ? 0 : (ne > max_voxels ? max_voxels : ne);
+    const int ne = clamped_count(grid_stats, max_voxels);
     const long long total = (long long)max_voxels * 9;
     for (long long w = (long long)blockIdx.x * kSceneThreads + threadIdx.x; w < total; w += (long long)gridDim.x * kSceneThreads) {
         const int v = (int)(w / 9), col = (int)(w - (long long)v * 9);

@@ -11,8 +11,8 @@
 //
 //   grid_rooms_check_kernel      one workgroup: room_start well formed?  Everything behind trusts it only if so
 //   grid_rooms_bounds_kernel     a workgroup per tile of 1024 global rows; per room that meets the tile one record {min,
-//                                max of x, y, z over the finite rows, other rows} at record tile + room, as
-//                                rooms_bounds_kernel: distinct for distinct (tile, room), a room's records consecutive
+//                                max of x, y, z over the finite rows, other rows} at record tile + room (the numbering
+//                                of rooms_bounds_kernel): distinct for distinct (tile, room), a room's records consecutive
 //   grid_rooms_frame_kernel      a workgroup per room: its records -> lo, n, cells, the error, the finite rows; and into
 //                                word 7 of every record the room's finite rows in the tiles before it
 //   grid_rooms_base_kernel       one workgroup: cell_base (64-bit) and pair_base, the prefixes of the rooms' cells and
@@ -64,19 +64,9 @@ struct GridRoomsArgs {
 __global__ __launch_bounds__(kGridScanThreads) void grid_rooms_check_kernel(const GridRoomsArgs p)
 {
     __shared__ int bad_s;
-    const int tid = threadIdx.x;
-    if (tid == 0) bad_s = 0;
-    __syncthreads();
-    bool bad = false;
-    for (int i = tid; i <= p.R; i += kGridScanThreads) {
-        const int a = p.room_start[i];
-        if (i == 0 && a < 0) bad = true;
-        if (i == p.R && a > p.g.N) bad = true;
-        if (i < p.R && p.room_start[i + 1] < a) bad = true;
-    }
-    if (bad) atomicOr(&bad_s, 1);
-    __syncthreads();
-    if (tid == 0) p.xh->bad = bad_s;
+    // no limit on a room's rows of its own: a well-formed room has at most N
+    const int bad = room_start_bad(p.room_start, p.R, p.g.N, 0x7fffffffffffffffll, &bad_s, threadIdx.x, kGridScanThreads);
+    if (threadIdx.x == 0) p.xh->bad = bad;
 }
 
 __global__ __launch_bounds__(kSceneThreads) void grid_rooms_bounds_kernel(const GridRoomsArgs p)
@@ -102,31 +92,14 @@ __global__ __launch_bounds__(kSceneThreads) void grid_rooms_bounds_kernel(const 
         const int a = ra > t0 ? ra : t0, b = rb < t1 ? rb : t1;
         if (a >= b) continue;
         SceneRange g;
-        for (int e = 0; e < 3; ++e) {
-            g.lo[e] = INFINITY;
-            g.hi[e] = -INFINITY;
-        }
-        g.bad = 0;
+        range_init(g);
         for (int k = 0; k < 4; ++k) {
             const int i = t0 + tid + k * kSceneThreads;
-            if (i < a || i >= b) continue;
-            if (scene_finite(x[k], y[k], z[k])) {
-                g.lo[0] = fminf(g.lo[0], x[k]); g.hi[0] = fmaxf(g.hi[0], x[k]);
-                g.lo[1] = fminf(g.lo[1], y[k]); g.hi[1] = fmaxf(g.hi[1], y[k]);
-                g.lo[2] = fminf(g.lo[2], z[k]); g.hi[2] = fmaxf(g.hi[2], z[k]);
-            } else {
-                g.bad += 1;
-            }
+            if (i >= a && i < b) range_add(g, x[k], y[k], z[k]);
         }
         g = scene_reduce(g, red, tid, kSceneThreads);
-        if (tid == 0) {
-            float *w = p.g.records + (size_t)(tile + r) * 8;     // tile + r < row tiles + R
-            for (int e = 0; e < 3; ++e) {
-                w[e] = g.lo[e];
-                w[3 + e] = g.hi[e];
-            }
-            w[6] = __int_as_float(g.bad);
-        }
+        // tile + r < row tiles + R.  Word 7 stays unwritten: grid_rooms_frame_kernel writes it
+        if (tid == 0) range_store(g, p.g.records + (size_t)(tile + r) * 8);
     }
 }
 
@@ -142,19 +115,8 @@ __global__ __launch_bounds__(kSceneThreads) void grid_rooms_frame_kernel(const G
         const int a = bad ? 0 : p.room_start[r], b = bad ? 0 : p.room_start[r + 1];
         const int ta = a / kGridRowTile, tb = b > a ? (b - 1) / kGridRowTile : ta - 1;
         SceneRange g;
-        for (int e = 0; e < 3; ++e) {
-            g.lo[e] = INFINITY;
-            g.hi[e] = -INFINITY;
-        }
-        g.bad = 0;
-        for (int t = ta + tid; t <= tb; t += kSceneThreads) {
-            const float *w = p.g.records + (size_t)(t + r) * 8;
-            for (int e = 0; e < 3; ++e) {
-                g.lo[e] = fminf(g.lo[e], w[e]);
-                g.hi[e] = fmaxf(g.hi[e], w[3 + e]);
-            }
-            g.bad += __float_as_int(w[6]);
-        }
+        range_init(g);
+        for (int t = ta + tid; t <= tb; t += kSceneThreads) range_fold(g, p.g.records + (size_t)(t + r) * 8);
         g = scene_reduce(g, red, tid, kSceneThreads);
         int run = 0;
         for (int c0 = ta; c0 <= tb; c0 += kSceneThreads) {       // uniform over the workgroup
@@ -166,7 +128,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_rooms_frame_kernel(const G
                 fin = ((b < t1 ? b : t1) - (a > t0 ? a : t0)) - __float_as_int(w[6]);
             }
             int total;
-            const int before = scene_exscan(fin, scan_s, tid, kSceneThreads, &total);
+            const int before = wg_exscan(fin, scan_s, tid, kSceneThreads, &total);
             if (t <= tb) w[7] = __int_as_float(run + before);
             run += total;
         }
@@ -175,7 +137,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_rooms_frame_kernel(const G
             const bool any = g.bad < b - a;
             bool over = false;
             for (int e = 0; e < 3; ++e) {
-                // fminf takes -0.0 as below +0.0, as in grid_frame_kernel: a zero minimum has the single call's sign
+                // as in grid_frame_kernel: a zero minimum has the single call's sign
                 h.lo[e] = any ? g.lo[e] : 0.0f;
                 h.n[e] = any ? grid_axis_cell(g.hi[e] - g.lo[e], p.g.voxel) + 1 : 0;
                 if (h.n[e] > kGridMaxAxis) over = true;
@@ -198,8 +160,8 @@ __global__ __launch_bounds__(kGridScanThreads) void grid_rooms_base_kernel(const
     __shared__ long long scan_s[kGridScanThreads / 64];
     __shared__ int scan_i[kGridScanThreads / 64];
     const int tid = threadIdx.x;
-    const int per = (p.R + kGridScanThreads - 1) / kGridScanThreads;
-    const int r0 = tid * per < p.R ? tid * per : p.R, r1 = r0 + per < p.R ? r0 + per : p.R;
+    int r0, r1;
+    wg_chunk(p.R, kGridScanThreads, tid, &r0, &r1);
     for (int e = tid; e < kGridPasses * kGridDigits; e += kGridScanThreads) p.g.digit_total[e] = 0;
     long long cells = 0;
     int pairs = 0, bad_rows = 0, errors = 0;             // the rooms' rows, summed, are <= N <= 2^24
@@ -211,10 +173,10 @@ __global__ __launch_bounds__(kGridScanThreads) void grid_rooms_base_kernel(const
     }
     long long cells_all;
     int pairs_all, bad_all, err_all;
-    long long cbase = rooms_exscan<long long>(cells, scan_s, tid, kGridScanThreads, &cells_all);
-    int pbase = scene_exscan(pairs, scan_i, tid, kGridScanThreads, &pairs_all);
-    (void)scene_exscan(bad_rows, scan_i, tid, kGridScanThreads, &bad_all);
-    (void)scene_exscan(errors, scan_i, tid, kGridScanThreads, &err_all);
+    long long cbase = wg_exscan(cells, scan_s, tid, kGridScanThreads, &cells_all);
+    int pbase = wg_exscan(pairs, scan_i, tid, kGridScanThreads, &pairs_all);
+    (void)wg_exscan(bad_rows, scan_i, tid, kGridScanThreads, &bad_all);
+    (void)wg_exscan(errors, scan_i, tid, kGridScanThreads, &err_all);
     const bool over = cells_all > kGridMaxCells;         // a global cell id must fit the 40 bits of a pair
     for (int r = r0; r < r1; ++r) {
         p.cell_base[r] = over ? 0 : cbase;
@@ -289,7 +251,7 @@ __global__ __launch_bounds__(kSceneThreads) void grid_rooms_pairs_kernel(const G
         if (room[k] < 0) p.g.inverse[i] = -1;
     }
     int total;
-    int rank = scene_exscan(n, scan_s, tid, kSceneThreads, &total);
+    int rank = wg_exscan(n, scan_s, tid, kSceneThreads, &total);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         rank_s[4 * tid + k] = rank;
@@ -350,12 +312,8 @@ __global__ __launch_bounds__(kSceneThreads) void grid_rooms_out_kernel(const Gri
         int f = 0;
         if (lane < 2) {
             const long long base = p.cell_base[r + lane];
-            int lo = 0, hi = V;                          // the voxels whose cell id is below base
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if ((long long)(sorted[p.g.start[mid]] >> kGridRowBits) < base) lo = mid + 1; else hi = mid;
-            }
-            f = lo;
+            // the voxels whose cell id is below base
+            f = lower_bound(0, V, [&](int m) { return (long long)(sorted[p.g.start[m]] >> kGridRowBits) < base; });
         }
         const int f0 = __shfl(f, 0, 64), f1 = __shfl(f, 1, 64);
         const int T0 = (f0 + kGridCountTile - 1) / kGridCountTile, T1 = f1 / kGridCountTile;
@@ -405,7 +363,7 @@ __global__ __launch_bounds__(kGridScanThreads) void grid_rooms_stats_kernel(cons
         m = s[6] > m ? s[6] : m;
     }
     int with_all;
-    (void)scene_exscan(with, scan_s, tid, kGridScanThreads, &with_all);
+    (void)wg_exscan(with, scan_s, tid, kGridScanThreads, &with_all);
     for (int d = 32; d >= 1; d >>= 1) {
         const int o = __shfl_xor(m, d, 64);
         m = o > m ? o : m;

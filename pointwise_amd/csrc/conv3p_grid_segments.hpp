@@ -35,7 +35,7 @@
 //   gseg_flatten_kernel   parent[v] = the root of v, behind the kernel boundary, so the forest is final: no atomics on the
 //                        links.  In place: a word is read either before or after its own flattening and both are ancestors
 //                        on the path to the same root.  Also the roots of every tile of kGsegTile voxels.
-//   gseg_scan_kernel      one workgroup: exclusive prefix of the tiles' counts (the pattern of grid_heads_scan_kernel); S
+//   gseg_scan_kernel      one workgroup: exclusive prefix of the tiles' counts (wg_exscan_inplace); S
 //   gseg_number_kernel    roots numbered in ascending voxel number: segment[root], seg_root, seg_label
 //   gseg_assign_kernel    segment[v] = segment[root] (roots are only read here), sizes and rows by integer adds: runs of
 //                        equal segment among the consecutive voxels of a wave are summed by a segmented shuffle and carried
@@ -77,12 +77,6 @@ constexpr size_t kGsegHeaderBytes = 256;
 template <int kScope> __device__ __forceinline__ int gseg_load(const int32_t *p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, kScope);
-}
-
-__device__ __forceinline__ int gseg_ne(const int32_t *grid_stats, int M)
-{
-    const int ne = grid_stats[0];
-    return ne < 0 ? 0 : (ne > M ? M : ne);
 }
 
 // The root of x.  Every step goes to a strictly smaller voxel, so the walk ends whatever other threads do.  Path halving:
@@ -146,7 +140,7 @@ __device__ __forceinline__ void gseg_local_body(Join rule, const int32_t *neigh,
                                                 int32_t *seg_label, int32_t *seg_stats)
 {
     __shared__ int32_t parent_s[kGsegLocalTile], lab_s[kGsegLocalTile];
-    const int ne = gseg_ne(grid_stats, M), i = threadIdx.x;
+    const int ne = clamped_count(grid_stats, M), i = threadIdx.x;
     if (blockIdx.x == 0 && i < 8) seg_stats[i] = i == 3 ? M - ne : 0;
     for (long long base = (long long)blockIdx.x * kGsegLocalTile; base < M; base += (long long)gridDim.x * kGsegLocalTile) {
         const long long w = base + i;
@@ -199,7 +193,7 @@ template <typename Join>
 __device__ __forceinline__ void gseg_link_body(Join rule, const int32_t *neigh, const int32_t *lab, int32_t *parent,
                                                const int32_t *grid_stats, int M, unsigned tapmask)
 {
-    const int ne = gseg_ne(grid_stats, M);
+    const int ne = clamped_count(grid_stats, M);
     for (long long w = (long long)blockIdx.x * kGsegThreads + threadIdx.x; w < ne; w += (long long)gridDim.x * kGsegThreads) {
         const int v = (int)w;
         const int lv = lab[v];
@@ -261,22 +255,11 @@ __global__ __launch_bounds__(kGsegScanThreads) void gseg_scan_kernel(int32_t *a,
                                                                    int32_t *total_b)
 {
     __shared__ int scan_s[kGsegScanThreads / 64];
-    const int tid = threadIdx.x;
-    const int per = (n + kGsegScanThreads - 1) / kGsegScanThreads;
-    const int i0 = (long long)tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
     for (int pass = 0; pass < 2; ++pass) {
         int32_t *x = pass ? b : a;
         if (!x) break;                                   // uniform
-        int mine = 0;
-        for (int i = i0; i < i1; ++i) mine += x[i];
-        int total;
-        int run = scene_exscan(mine, scan_s, tid, kGsegScanThreads, &total);
-        for (int i = i0; i < i1; ++i) {
-            const int v = x[i];
-            x[i] = run;
-            run += v;
-        }
-        if (tid == 0) (pass ? total_b : total_a)[0] = total;
+        const int total = wg_exscan_inplace(x, n, scan_s, (int)threadIdx.x, kGsegScanThreads);
+        if (threadIdx.x == 0) (pass ? total_b : total_a)[0] = total;
     }
 }
 
@@ -294,7 +277,7 @@ __global__ __launch_bounds__(kGsegThreads) void gseg_number_kernel(const int32_t
             const int c = w < M ? lab[v] : -1;
             const int f = (c >= 0 && parent[v] == v) ? 1 : 0;
             int total;
-            const int s = base + scene_exscan(f, scan_s, tid, kGsegThreads, &total);
+            const int s = base + wg_exscan(f, scan_s, tid, kGsegThreads, &total);
             if (f) {                                     // s < S <= M
                 segment[v] = s;
                 seg_root[s] = v;
@@ -319,7 +302,7 @@ __global__ __launch_bounds__(kGsegThreads) void gseg_assign_kernel(const int32_t
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 2) count_s[tid] = 0;
     __syncthreads();
-    const int ne = gseg_ne(grid_stats, M);
+    const int ne = clamped_count(grid_stats, M);
     int labelled = 0, bare = 0;
     const long long chunk = 64ll * steps, waves = (long long)gridDim.x * (kGsegThreads / 64);
     for (long long c0 = ((long long)blockIdx.x * (kGsegThreads / 64) + (tid >> 6)) * chunk; c0 < M; c0 += waves * chunk) {
@@ -430,12 +413,6 @@ struct AbsorbArgs {
     int32_t *cursor, *small_list, *small_off, *members;  // M words each
 };
 
-__device__ __forceinline__ int absorb_S(const AbsorbArgs &p)
-{
-    const int S = p.seg_stats[0];
-    return S < 0 ? 0 : (S > p.M ? p.M : S);
-}
-
 // seg_size[s] of a small segment, 0 otherwise (A1); sizes are held to [0, M] so that no sum leaves int32
 __device__ __forceinline__ int absorb_small_size(const AbsorbArgs &p, long long s, int S)
 {
@@ -448,7 +425,7 @@ __global__ __launch_bounds__(kGsegThreads) void absorb_count_kernel(const Absorb
 {
     __shared__ int count_s[2];
     const int tid = threadIdx.x;
-    const int S = absorb_S(p);
+    const int S = clamped_count(p.seg_stats, p.M);
     if (blockIdx.x == 0 && tid < 4) p.stats[tid] = 0ull;
     for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
         if (tid < 2) count_s[tid] = 0;
@@ -476,15 +453,15 @@ __global__ __launch_bounds__(kGsegThreads) void absorb_plan_kernel(const AbsorbA
 {
     __shared__ int scan_s[kGsegThreads / 64];
     const int tid = threadIdx.x;
-    const int S = absorb_S(p);
+    const int S = clamped_count(p.seg_stats, p.M);
     for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
         int kbase = p.tile_small[tile], mbase = p.tile_members[tile];
         for (int j = 0; j < kGsegTileSteps; ++j) {        // uniform
             const long long s = (long long)tile * kGsegTile + j * kGsegThreads + tid;
             const int n = absorb_small_size(p, s, S);
             int ktot, mtot;
-            const int k = kbase + scene_exscan(n > 0, scan_s, tid, kGsegThreads, &ktot);
-            const int off = mbase + scene_exscan(n, scan_s, tid, kGsegThreads, &mtot);
+            const int k = kbase + wg_exscan(n > 0 ? 1 : 0, scan_s, tid, kGsegThreads, &ktot);
+            const int off = mbase + wg_exscan(n, scan_s, tid, kGsegThreads, &mtot);
             if (n > 0) {                                 // k < M, off + n <= M: at most M voxels lie in segments
                 p.small_list[k] = (int)s;
                 p.small_off[k] = off;
@@ -500,7 +477,7 @@ __global__ __launch_bounds__(kGsegThreads) void absorb_plan_kernel(const AbsorbA
 
 __global__ __launch_bounds__(kGsegThreads) void absorb_scatter_kernel(const AbsorbArgs p)
 {
-    const int S = absorb_S(p);
+    const int S = clamped_count(p.seg_stats, p.M);
     for (long long w = (long long)blockIdx.x * kGsegThreads + threadIdx.x; w < p.M; w += (long long)gridDim.x * kGsegThreads) {
         const int s = p.segment[w];
         if (s < 0 || s >= S) continue;
@@ -515,8 +492,8 @@ __global__ __launch_bounds__(kGsegThreads) void absorb_vote_kernel(const AbsorbA
 {
     __shared__ int hist_s[kGsegThreads / 64][kGsegMaxClass];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int S = absorb_S(p);
-    const int ne = gseg_ne(p.grid_stats, p.M);
+    const int S = clamped_count(p.seg_stats, p.M);
+    const int ne = clamped_count(p.grid_stats, p.M);
     int small = p.hdr[0];
     small = small < 0 ? 0 : (small > p.M ? p.M : small);
     int *hist = hist_s[wv];
@@ -578,8 +555,8 @@ __global__ __launch_bounds__(kGsegThreads) void absorb_vote_kernel(const AbsorbA
 
 __global__ __launch_bounds__(kGsegThreads) void absorb_labels_kernel(const AbsorbArgs p)
 {
-    const int S = absorb_S(p);
-    const int ne = gseg_ne(p.grid_stats, p.M);
+    const int S = clamped_count(p.seg_stats, p.M);
+    const int ne = clamped_count(p.grid_stats, p.M);
     const int keep = p.voxel_labels ? (p.L < ne ? p.L : ne) : 0;
     for (long long w = (long long)blockIdx.x * kGsegThreads + threadIdx.x; w < p.M; w += (long long)gridDim.x * kGsegThreads) {
         const int s = p.segment[w];

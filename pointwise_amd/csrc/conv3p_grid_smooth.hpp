@@ -162,7 +162,7 @@ __global__ __launch_bounds__(kGsegThreads) void pool_sum_kernel(const T *values,
 {
     using u64 = unsigned long long;
     constexpr int kNV = kPoolChunk + 1;                  // the chunk's channels and the weight
-    const int ne = gseg_ne(grid_stats, M), S = geom_S(seg_stats, M);
+    const int ne = clamped_count(grid_stats, M), S = clamped_count(seg_stats, M);
     const int tid = threadIdx.x, lane = tid & 63;
     const long long chunk = 64ll * steps, waves = (long long)gridDim.x * (kGsegThreads / 64);
     auto op = [](int, u64 a, u64 b) { return a + b; };
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(kGsegThreads) void pool_finish_kernel(const int32_t
     const int tid = threadIdx.x;
     if (tid < 2) count_s[tid] = 0;
     __syncthreads();
-    const int S = geom_S(seg_stats, M);
+    const int S = clamped_count(seg_stats, M);
     int n_with = 0, n_without = 0;
     for (long long s = (long long)blockIdx.x * kGsegThreads + tid; s < M; s += (long long)gridDim.x * kGsegThreads) {
         const long long W = weights[s];
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(kGsegThreads) void pool_voxel_kernel(const int32_t 
                                                                   const int32_t *grid_stats, int M, const int32_t *seg_label,
                                                                   int32_t *voxel_label)
 {
-    const int ne = gseg_ne(grid_stats, M), S = geom_S(seg_stats, M);
+    const int ne = clamped_count(grid_stats, M), S = clamped_count(seg_stats, M);
     for (long long w = (long long)blockIdx.x * kGsegThreads + threadIdx.x; w < M; w += (long long)gridDim.x * kGsegThreads) {
         const int s = geom_member(segment, w, ne, S);
         voxel_label[w] = s >= 0 ? seg_label[s] : -1;

@@ -46,6 +46,7 @@
 
 #include "conv3p_cls_tail.hpp"
 #include "conv3p_prestep.hpp"
+#include "conv3p_workgroup.hpp"
 
 namespace conv3p {
 
@@ -75,13 +76,6 @@ struct ProviderArgs {
 __device__ __forceinline__ long long provider_sample(const ProviderArgs &p, int b)
 {
     return p.perm ? (long long)p.perm[p.start + b] : p.start + b;
-}
-
-__device__ __forceinline__ int32_t provider_label(const ProviderArgs &p, size_t idx)
-{
-    if (p.label_bytes == 1) return (int32_t) static_cast<const uint8_t *>(p.labels)[idx];
-    if (p.label_bytes == 4) return static_cast<const int32_t *>(p.labels)[idx];
-    return (int32_t) static_cast<const long long *>(p.labels)[idx];
 }
 
 __device__ __forceinline__ double2 provider_draw_cos_sin(const ProviderArgs &p, unsigned s)
@@ -116,7 +110,7 @@ __device__ __forceinline__ void provider_cloud_head(const ProviderArgs &p, int b
     *cs_s = t;
     if (!first) return;
     if (p.cos_sin_out) p.cos_sin_out[b] = t;
-    if (p.labels_out && !p.per_point) p.labels_out[b] = valid ? provider_label(p, (size_t)s) : -1;
+    if (p.labels_out && !p.per_point) p.labels_out[b] = valid ? row_label(p.labels, p.label_bytes, (size_t)s) : -1;
 }
 
 // Source row i of cloud b (sample s) -> its augmented xyz; noise_out.  An invalid sample reads nothing and gives zeros.
@@ -183,7 +177,7 @@ __global__ __launch_bounds__(kProviderTile) void provider_flat_kernel(const Prov
         xyz_s[3 * tid + 1] = r[1];
         xyz_s[3 * tid + 2] = r[2];
         const size_t o = (size_t)b * N + i;
-        if (p.labels_out && p.per_point) p.labels_out[o] = valid ? provider_label(p, (size_t)s * p.Nsrc + i) : -1;
+        if (p.labels_out && p.per_point) p.labels_out[o] = valid ? row_label(p.labels, p.label_bytes, (size_t)s * p.Nsrc + i) : -1;
         if (p.order_out) p.order_out[o] = i;
     }
     __syncthreads();
@@ -279,7 +273,7 @@ __global__ __launch_bounds__(1024) void provider_sort_kernel(const ProviderArgs 
     for (int r = tid; r < N; r += nthr) {
         const int i = (int)row_of(r);
         const size_t o = (size_t)b * N + r;
-        if (p.labels_out && p.per_point) p.labels_out[o] = valid ? provider_label(p, (size_t)s * p.Nsrc + i) : -1;
+        if (p.labels_out && p.per_point) p.labels_out[o] = valid ? row_label(p.labels, p.label_bytes, (size_t)s * p.Nsrc + i) : -1;
         if (p.order_out) p.order_out[o] = i;
     }
 }

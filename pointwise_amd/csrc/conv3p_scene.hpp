@@ -28,6 +28,7 @@
 #pragma once
 
 #include "conv3p_cls_tail.hpp"
+#include "conv3p_workgroup.hpp"
 
 namespace conv3p {
 
@@ -71,10 +72,6 @@ struct SceneArgs {
     int4 *table;                       // (max_blocks): {cell, list start + a_j, n_j, j * P}
 };
 
-__device__ __forceinline__ bool scene_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-struct SceneRange { float lo[3], hi[3]; int bad; };
-
 // Workgroup reduction of the lanes' ranges -> every thread gets the workgroup's.  red: (nthr / 64) * 7 floats.  min and
 // max are exact, so the order does not matter to the bits; it is fixed all the same (butterfly, then wave order).
 __device__ __forceinline__ SceneRange scene_reduce(SceneRange r, float *red, int tid, int nthr)
@@ -87,28 +84,11 @@ __device__ __forceinline__ SceneRange scene_reduce(SceneRange r, float *red, int
         r.bad += __shfl_xor(r.bad, d, 64);
     }
     __syncthreads();
-    if ((tid & 63) == 0) {
-        float *w = red + (tid >> 6) * 7;
-        for (int a = 0; a < 3; ++a) {
-            w[a] = r.lo[a];
-            w[3 + a] = r.hi[a];
-        }
-        w[6] = __int_as_float(r.bad);
-    }
+    if ((tid & 63) == 0) range_store(r, red + (tid >> 6) * 7);
     __syncthreads();
     SceneRange t;
-    for (int a = 0; a < 3; ++a) {
-        t.lo[a] = INFINITY;
-        t.hi[a] = -INFINITY;
-    }
-    t.bad = 0;
-    for (int w = 0; w < nthr / 64; ++w) {
-        for (int a = 0; a < 3; ++a) {
-            t.lo[a] = fminf(t.lo[a], red[w * 7 + a]);
-            t.hi[a] = fmaxf(t.hi[a], red[w * 7 + 3 + a]);
-        }
-        t.bad += __float_as_int(red[w * 7 + 6]);
-    }
+    range_init(t);
+    for (int w = 0; w < nthr / 64; ++w) range_fold(t, red + w * 7);
     return t;
 }
 
@@ -117,30 +97,15 @@ __global__ __launch_bounds__(kSceneThreads) void scene_bounds_kernel(const Scene
     __shared__ float red[(kSceneThreads / 64) * 7];
     const int tid = threadIdx.x;
     SceneRange r;
-    for (int a = 0; a < 3; ++a) {
-        r.lo[a] = INFINITY;
-        r.hi[a] = -INFINITY;
-    }
-    r.bad = 0;
+    range_init(r);
     for (size_t i = (size_t)blockIdx.x * kSceneThreads + tid; i < (size_t)p.N; i += (size_t)gridDim.x * kSceneThreads) {
         const float *v = p.data + i * p.K;
-        const float x = v[0], y = v[1], z = v[2];
-        if (scene_finite(x, y, z)) {
-            r.lo[0] = fminf(r.lo[0], x); r.hi[0] = fmaxf(r.hi[0], x);
-            r.lo[1] = fminf(r.lo[1], y); r.hi[1] = fmaxf(r.hi[1], y);
-            r.lo[2] = fminf(r.lo[2], z); r.hi[2] = fmaxf(r.hi[2], z);
-        } else {
-            r.bad += 1;
-        }
+        range_add(r, v[0], v[1], v[2]);
     }
     r = scene_reduce(r, red, tid, kSceneThreads);
     if (tid == 0) {
         float *w = p.records + (size_t)blockIdx.x * 8;
-        for (int a = 0; a < 3; ++a) {
-            w[a] = r.lo[a];
-            w[3 + a] = r.hi[a];
-        }
-        w[6] = __int_as_float(r.bad);
+        range_store(r, w);
         w[7] = 0.0f;
     }
 }
@@ -160,12 +125,8 @@ __global__ __launch_bounds__(kSceneMaxRecords) void scene_finish_kernel(const Sc
     __shared__ int ncells_s;
     const int tid = threadIdx.x;
     SceneRange r;
-    for (int a = 0; a < 3; ++a) {
-        r.lo[a] = INFINITY;
-        r.hi[a] = -INFINITY;
-    }
-    r.bad = 0;
-    if (tid < p.records_n) {
+    range_init(r);
+    if (tid < p.records_n) {                             // a thread takes one record: loaded over the empty range
         const float *w = p.records + (size_t)tid * 8;
         for (int a = 0; a < 3; ++a) {
             r.lo[a] = w[a];
@@ -249,36 +210,14 @@ __global__ __launch_bounds__(kSceneThreads) void scene_count_kernel(const SceneA
     }
 }
 
-// Exclusive prefix of v over the workgroup's threads, and the total.  lds: nthr / 64 ints.
-__device__ __forceinline__ int scene_exscan(int v, int *lds, int tid, int nthr, int *total)
-{
-    const int lane = tid & 63, wv = tid >> 6;
-    int x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < nthr / 64; ++w) {
-        const int s = lds[w];
-        if (w < wv) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + x - v;
-}
-
 __global__ __launch_bounds__(kScenePlanThreads) void scene_plan_kernel(const SceneArgs p)
 {
     __shared__ int scan_s[kScenePlanThreads / 64];
     const SceneHeader h = *p.hdr;
     const int tid = threadIdx.x;
     const int need = p.min_points < 1 ? 1 : p.min_points;
-    const int per = (h.ncells + kScenePlanThreads - 1) / kScenePlanThreads;
-    const int c0 = tid * per < h.ncells ? tid * per : h.ncells, c1 = c0 + per < h.ncells ? c0 + per : h.ncells;
+    int c0, c1;
+    wg_chunk(h.ncells, kScenePlanThreads, tid, &c0, &c1);
     int kept = 0, small = 0;
     for (int c = c0; c < c1; ++c) {
         const int n = p.count[c];
@@ -286,8 +225,8 @@ __global__ __launch_bounds__(kScenePlanThreads) void scene_plan_kernel(const Sce
         small += (n > 0 && n < need) ? 1 : 0;
     }
     int kept_all, small_all, dummy;
-    const int kbase = scene_exscan(kept, scan_s, tid, kScenePlanThreads, &kept_all);
-    (void)scene_exscan(small, scan_s, tid, kScenePlanThreads, &small_all);
+    const int kbase = wg_exscan(kept, scan_s, tid, kScenePlanThreads, &kept_all);
+    (void)wg_exscan(small, scan_s, tid, kScenePlanThreads, &small_all);
     const int limit = p.max_blocks < kSceneMaxCells ? p.max_blocks : kSceneMaxCells;
     int b = kbase, mine = 0;
     for (int c = c0; c < c1; ++c) {
@@ -300,7 +239,7 @@ __global__ __launch_bounds__(kScenePlanThreads) void scene_plan_kernel(const Sce
         }
         ++b;
     }
-    int off = scene_exscan(mine, scan_s, tid, kScenePlanThreads, &dummy);
+    int off = wg_exscan(mine, scan_s, tid, kScenePlanThreads, &dummy);
     b = kbase;
     for (int c = c0; c < c1; ++c) {
         const int n = p.count[c];
@@ -410,13 +349,6 @@ __global__ __launch_bounds__(kSceneThreads) void scene_fill_kernel(const SceneAr
     }
 }
 
-__device__ __forceinline__ int32_t scene_label(const SceneArgs &p, size_t idx)
-{
-    if (p.label_bytes == 1) return (int32_t) static_cast<const uint8_t *>(p.labels)[idx];
-    if (p.label_bytes == 4) return static_cast<const int32_t *>(p.labels)[idx];
-    return (int32_t) static_cast<const long long *>(p.labels)[idx];
-}
-
 // The emit of both modes.  kCover: block b is part j of its cell, (cell, list start + a_j, n_j, j * P) from the table --
 // n_j <= P members, the draws among them, the counter's first word behind j * P.
 template <bool kCover> __device__ __forceinline__ void scene_emit_body(const SceneArgs &p)
@@ -465,7 +397,7 @@ template <bool kCover> __device__ __forceinline__ void scene_emit_body(const Sce
             }
             const int row = list[m];
             idx[t] = row;
-            if (lab) lab[t] = scene_label(p, (size_t)row);
+            if (lab) lab[t] = row_label(p.labels, p.label_bytes, (size_t)row);
             const float *v = p.data + (size_t)row * K;
             mnx = fminf(mnx, v[0] - h.lo[0]);
             mny = fminf(mny, v[1] - h.lo[1]);

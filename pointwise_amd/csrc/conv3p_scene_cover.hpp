@@ -34,8 +34,8 @@ __global__ __launch_bounds__(kScenePlanThreads) void scene_cover_plan_kernel(con
     const SceneHeader h = *p.hdr;
     const int tid = threadIdx.x, P = p.P;
     const int need = p.min_points < 1 ? 1 : p.min_points;
-    const int per = (h.ncells + kScenePlanThreads - 1) / kScenePlanThreads;
-    const int c0 = tid * per < h.ncells ? tid * per : h.ncells, c1 = c0 + per < h.ncells ? c0 + per : h.ncells;
+    int c0, c1;
+    wg_chunk(h.ncells, kScenePlanThreads, tid, &c0, &c1);
     int kept = 0, small = 0, parts = 0;                  // sum of q <= kept + 9 N / P < 2^31
     for (int c = c0; c < c1; ++c) {
         const int n = p.count[c];
@@ -44,9 +44,9 @@ __global__ __launch_bounds__(kScenePlanThreads) void scene_cover_plan_kernel(con
         parts += n >= need ? (n + P - 1) / P : 0;
     }
     int kept_all, small_all, parts_all, listed_all, dummy;
-    const int kbase = scene_exscan(kept, scan_s, tid, kScenePlanThreads, &kept_all);
-    (void)scene_exscan(small, scan_s, tid, kScenePlanThreads, &small_all);
-    const int pbase = scene_exscan(parts, scan_s, tid, kScenePlanThreads, &parts_all);
+    const int kbase = wg_exscan(kept, scan_s, tid, kScenePlanThreads, &kept_all);
+    (void)wg_exscan(small, scan_s, tid, kScenePlanThreads, &small_all);
+    const int pbase = wg_exscan(parts, scan_s, tid, kScenePlanThreads, &parts_all);
     // listed cells: first block number < max_blocks.  The first block numbers ascend with the kept rank, so the listed
     // cells are the kept ranks 0 .. listed_all - 1 (< kSceneMaxCells, as the cells themselves)
     int k = kbase, first = pbase, mine = 0, listed = 0;
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(kScenePlanThreads) void scene_cover_plan_kernel(con
         ++k;
         first += (n + P - 1) / P;
     }
-    (void)scene_exscan(listed, scan_s, tid, kScenePlanThreads, &listed_all);
-    int off = scene_exscan(mine, scan_s, tid, kScenePlanThreads, &dummy);
+    (void)wg_exscan(listed, scan_s, tid, kScenePlanThreads, &listed_all);
+    int off = wg_exscan(mine, scan_s, tid, kScenePlanThreads, &dummy);
     k = kbase;
     first = pbase;
     for (int c = c0; c < c1; ++c) {

@@ -17,11 +17,13 @@
 //   rooms_pairs_kernel<0>     tile of 1024 rows: the rows' member cells by scene_axis_mask's comparisons, counted
 //   rooms_tile_scan_kernel    one workgroup: prefix of the tiles' pair counts -> M pairs, T sort tiles
 //   rooms_pairs_kernel<1>     the same rows again: the pairs, in row order, behind the tile's prefix
-//   3 x { rooms_sort_hist_kernel     per sort tile of 4096 pairs a histogram of 7 bits of the cell id
-//         rooms_sort_scan_kernel     one workgroup: prefix over (digit, tile)
-//         rooms_sort_scatter_kernel  one WAVE per sort tile, 64 pairs a step in order: the lanes of equal digit from
-//                                    seven ballots, rank = popcount below the lane, a running offset per digit in LDS;
-//                                    a pair's destination depends on nothing but the input order, so the sort is stable }
+//   3 x { rooms_sort_hist_kernel     per sort tile of 4096 pairs a histogram of 7 bits of the cell id (radix_hist_tile)
+//         rooms_sort_scan_kernel     one workgroup: prefix over (digit, tile), the whole histogram as one array
+//                                    (wg_exscan_inplace; no totals per digit, unlike the grid's and the adjacency's scan)
+//         rooms_sort_scatter_kernel  one WAVE per sort tile, 64 pairs a step in order (radix_scatter_tile): the lanes of
+//                                    equal digit from seven ballots, rank = popcount below the lane, a running offset per
+//                                    digit in LDS; a pair's destination depends on nothing but the input order, so the
+//                                    sort is stable }
 //   rooms_segments_kernel     sorted pairs: where the cell id changes, a list starts / ends -> count and offset per cell
 //   rooms_plan_kernel         one workgroup: all rooms' cells in order -> kept rank, first block number (scan over the
 //                             parts), the listed cells, and the prefixes at the rooms' boundaries
@@ -31,7 +33,8 @@
 //
 // No float atomics (the only atomics are the histogram's LDS integer adds and the check's one LDS atomicOr); every output
 // word is written once by a plain
-// store; the result does not depend on the launch geometry.
+// store; the result does not depend on the launch geometry.  The scans, the radix pass, the bounding-box records and the
+// room_start check are conv3p_workgroup.hpp's.
 #pragma once
 
 #include "conv3p_scene_cover.hpp"
@@ -94,54 +97,14 @@ struct RoomsArgs {
 // behind the last.  Terminates and stays inside room_start[0..R] whatever it holds.
 __device__ __forceinline__ int rooms_find(const int32_t *start, int R, int i)
 {
-    int lo = 0, hi = R + 1;                              // the number of entries <= i
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (start[mid] <= i) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
-
-template <typename T> __device__ __forceinline__ T rooms_exscan(T v, T *lds, int tid, int nthr, T *total)
-{
-    const int lane = tid & 63, wv = tid >> 6;
-    T x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int w = 0; w < nthr / 64; ++w) {
-        const T s = lds[w];
-        if (w < wv) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + x - v;
+    return lower_bound(0, R + 1, [&](int m) { return start[m] <= i; }) - 1;      // the number of entries <= i
 }
 
 __global__ __launch_bounds__(kRoomsScanThreads) void rooms_check_kernel(const RoomsArgs p)
 {
     __shared__ int bad_s;
-    const int tid = threadIdx.x;
-    if (tid == 0) bad_s = 0;
-    __syncthreads();
-    bool bad = false;
-    for (int i = tid; i <= p.R; i += kRoomsScanThreads) {
-        const int a = p.room_start[i];
-        if (i == 0 && a < 0) bad = true;
-        if (i == p.R && a > p.N) bad = true;
-        if (i < p.R) {
-            const int b = p.room_start[i + 1];
-            if (b < a || (long long)b - (long long)a > (long long)kSceneMaxN) bad = true;
-        }
-    }
-    if (bad) atomicOr(&bad_s, 1);
-    __syncthreads();
-    if (tid == 0) p.hdr->bad = bad_s;
+    const int bad = room_start_bad(p.room_start, p.R, p.N, kSceneMaxN, &bad_s, threadIdx.x, kRoomsScanThreads);
+    if (threadIdx.x == 0) p.hdr->bad = bad;
 }
 
 __global__ __launch_bounds__(kSceneThreads) void rooms_bounds_kernel(const RoomsArgs p)
@@ -167,30 +130,15 @@ __global__ __launch_bounds__(kSceneThreads) void rooms_bounds_kernel(const Rooms
         const int a = ra > t0 ? ra : t0, b = rb < t1 ? rb : t1;
         if (a >= b) continue;
         SceneRange g;
-        for (int e = 0; e < 3; ++e) {
-            g.lo[e] = INFINITY;
-            g.hi[e] = -INFINITY;
-        }
-        g.bad = 0;
+        range_init(g);
         for (int k = 0; k < 4; ++k) {
             const int i = t0 + tid + k * kSceneThreads;
-            if (i < a || i >= b) continue;
-            if (scene_finite(x[k], y[k], z[k])) {
-                g.lo[0] = fminf(g.lo[0], x[k]); g.hi[0] = fmaxf(g.hi[0], x[k]);
-                g.lo[1] = fminf(g.lo[1], y[k]); g.hi[1] = fmaxf(g.hi[1], y[k]);
-                g.lo[2] = fminf(g.lo[2], z[k]); g.hi[2] = fmaxf(g.hi[2], z[k]);
-            } else {
-                g.bad += 1;
-            }
+            if (i >= a && i < b) range_add(g, x[k], y[k], z[k]);
         }
         g = scene_reduce(g, red, tid, kSceneThreads);
         if (tid == 0) {
             float *w = p.records + (size_t)(tile + r) * 8;
-            for (int e = 0; e < 3; ++e) {
-                w[e] = g.lo[e];
-                w[3 + e] = g.hi[e];
-            }
-            w[6] = __int_as_float(g.bad);
+            range_store(g, w);
             w[7] = 0.0f;
         }
     }
@@ -204,29 +152,17 @@ __global__ __launch_bounds__(kSceneThreads) void rooms_finish_kernel(const Rooms
     for (int r = blockIdx.x; r < p.R; r += gridDim.x) {
         const int a = bad ? 0 : p.room_start[r], b = bad ? 0 : p.room_start[r + 1];
         SceneRange g;
-        for (int e = 0; e < 3; ++e) {
-            g.lo[e] = INFINITY;
-            g.hi[e] = -INFINITY;
-        }
-        g.bad = 0;
+        range_init(g);
         if (b > a) {
             const int ta = a / kRoomsRowTile, tb = (b - 1) / kRoomsRowTile;
-            for (int t = ta + tid; t <= tb; t += kSceneThreads) {
-                const float *w = p.records + (size_t)(t + r) * 8;
-                for (int e = 0; e < 3; ++e) {
-                    g.lo[e] = fminf(g.lo[e], w[e]);
-                    g.hi[e] = fmaxf(g.hi[e], w[3 + e]);
-                }
-                g.bad += __float_as_int(w[6]);
-            }
+            for (int t = ta + tid; t <= tb; t += kSceneThreads) range_fold(g, p.records + (size_t)(t + r) * 8);
         }
         g = scene_reduce(g, red, tid, kSceneThreads);
         if (tid == 0) {
             RoomFrame h;
             const bool any = g.bad < b - a;
             for (int e = 0; e < 3; ++e) {
-                // fminf is the device's min instruction, which takes -0.0 as below +0.0: a zero minimum has the sign the
-                // single-room call gives it, whatever the order of the reduction
+                // a zero minimum has the sign the single-room call gives it, whatever the order (see SceneRange)
                 h.lo[e] = any ? g.lo[e] : 0.0f;
                 h.lim[e] = any ? g.hi[e] - g.lo[e] : 0.0f;
             }
@@ -246,8 +182,8 @@ __global__ __launch_bounds__(kRoomsScanThreads) void rooms_base_kernel(const Roo
 {
     __shared__ long long scan_s[kRoomsScanThreads / 64];
     const int tid = threadIdx.x;
-    const int per = (p.R + kRoomsScanThreads - 1) / kRoomsScanThreads;
-    const int r0 = tid * per < p.R ? tid * per : p.R, r1 = r0 + per < p.R ? r0 + per : p.R;
+    int r0, r1;
+    wg_chunk(p.R, kRoomsScanThreads, tid, &r0, &r1);
     long long cells = 0, bad_rows = 0, errors = 0;
     for (int r = r0; r < r1; ++r) {
         cells += p.room[r].ncells;
@@ -255,9 +191,9 @@ __global__ __launch_bounds__(kRoomsScanThreads) void rooms_base_kernel(const Roo
         errors += p.room[r].error;
     }
     long long cells_all, bad_all, err_all;
-    long long base = rooms_exscan<long long>(cells, scan_s, tid, kRoomsScanThreads, &cells_all);
-    (void)rooms_exscan<long long>(bad_rows, scan_s, tid, kRoomsScanThreads, &bad_all);
-    (void)rooms_exscan<long long>(errors, scan_s, tid, kRoomsScanThreads, &err_all);
+    long long base = wg_exscan(cells, scan_s, tid, kRoomsScanThreads, &cells_all);
+    (void)wg_exscan(bad_rows, scan_s, tid, kRoomsScanThreads, &bad_all);
+    (void)wg_exscan(errors, scan_s, tid, kRoomsScanThreads, &err_all);
     const bool over = cells_all > (long long)kRoomsMaxCells;
     for (int r = r0; r < r1; ++r) {
         p.cell_base[r] = over ? 0 : (int)base;
@@ -321,7 +257,7 @@ template <bool kWrite> __global__ __launch_bounds__(kSceneThreads) void rooms_pa
         else row[k].mx = 0;
     }
     int total;
-    int pos = scene_exscan(n, scan_s, tid, kSceneThreads, &total);
+    int pos = wg_exscan(n, scan_s, tid, kSceneThreads, &total);
     if (!kWrite) {
         if (tid == 0) p.tile_pairs[tile] = total;
         return;
@@ -345,18 +281,8 @@ template <bool kWrite> __global__ __launch_bounds__(kSceneThreads) void rooms_pa
 __global__ __launch_bounds__(kRoomsScanThreads) void rooms_tile_scan_kernel(const RoomsArgs p)
 {
     __shared__ int scan_s[kRoomsScanThreads / 64];
-    const int tid = threadIdx.x, n = p.row_tiles;
-    const int per = (n + kRoomsScanThreads - 1) / kRoomsScanThreads;
-    const int a = tid * per < n ? tid * per : n, b = a + per < n ? a + per : n;
-    int mine = 0;
-    for (int t = a; t < b; ++t) mine += p.tile_pairs[t];
-    int total;
-    int run = scene_exscan(mine, scan_s, tid, kRoomsScanThreads, &total);
-    for (int t = a; t < b; ++t) {
-        const int v = p.tile_pairs[t];
-        p.tile_pairs[t] = run;
-        run += v;
-    }
+    const int tid = threadIdx.x;
+    const int total = wg_exscan_inplace(p.tile_pairs, p.row_tiles, scan_s, tid, kRoomsScanThreads);
     if (tid == 0) {
         // a row is in at most m x m cells, so total <= pairs_max; should the comparisons ever say otherwise the pairs
         // past the buffers are dropped and stats[7] says so (bit 3) instead of a result that is silently short
@@ -372,67 +298,25 @@ __global__ __launch_bounds__(kSceneThreads) void rooms_sort_hist_kernel(const Ro
                                                                         int shift)
 {
     __shared__ int hist_s[kRoomsDigits];
-    const int tid = threadIdx.x, M = p.hdr->pairs, T = p.hdr->sort_tiles;
-    for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
-        if (tid < kRoomsDigits) hist_s[tid] = 0;
-        __syncthreads();
-        const int i0 = tile * kRoomsSortTile, i1 = i0 + kRoomsSortTile < M ? i0 + kRoomsSortTile : M;
-        for (int i = i0 + tid; i < i1; i += kSceneThreads)
-            atomicAdd(&hist_s[(int)(src[i] >> (32 + shift)) & (kRoomsDigits - 1)], 1);
-        __syncthreads();
-        if (tid < kRoomsDigits) p.hist[(size_t)tid * T + tile] = hist_s[tid];
-        __syncthreads();
-    }
+    const int M = p.hdr->pairs, T = p.hdr->sort_tiles;
+    for (int tile = blockIdx.x; tile < T; tile += gridDim.x)
+        (void)radix_hist_tile<kRoomsDigitBits>(src, M, tile, kRoomsSortTile, 32 + shift, hist_s, p.hist, T, threadIdx.x,
+                                               kSceneThreads);
 }
 
 __global__ __launch_bounds__(kRoomsScanThreads) void rooms_sort_scan_kernel(const RoomsArgs p)
 {
     __shared__ int scan_s[kRoomsScanThreads / 64];
-    const int tid = threadIdx.x;
-    const long long n = (long long)p.hdr->sort_tiles * kRoomsDigits;
-    const long long per = (n + kRoomsScanThreads - 1) / kRoomsScanThreads;
-    const long long a = tid * per < n ? tid * per : n, b = a + per < n ? a + per : n;
-    int mine = 0;
-    for (long long e = a; e < b; ++e) mine += p.hist[e];
-    int total;
-    int run = scene_exscan(mine, scan_s, tid, kRoomsScanThreads, &total);
-    for (long long e = a; e < b; ++e) {
-        const int v = p.hist[e];
-        p.hist[e] = run;
-        run += v;
-    }
+    (void)wg_exscan_inplace(p.hist, (long long)p.hdr->sort_tiles * kRoomsDigits, scan_s, threadIdx.x, kRoomsScanThreads);
 }
 
 __global__ __launch_bounds__(64) void rooms_sort_scatter_kernel(const RoomsArgs p, const unsigned long long *src,
                                                                 unsigned long long *dst, int shift)
 {
     __shared__ int run_s[kRoomsDigits];
-    const int lane = threadIdx.x, M = p.hdr->pairs, T = p.hdr->sort_tiles;
-    for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
-        __syncthreads();
-        run_s[lane] = p.hist[(size_t)lane * T + tile];
-        run_s[lane + 64] = p.hist[(size_t)(lane + 64) * T + tile];
-        __syncthreads();
-        const int i0 = tile * kRoomsSortTile, i1 = i0 + kRoomsSortTile < M ? i0 + kRoomsSortTile : M;
-        for (int c0 = i0; c0 < i1; c0 += 64) {
-            const int i = c0 + lane;
-            const bool valid = i < i1;
-            const unsigned long long v = valid ? src[i] : 0ull;
-            const int digit = (int)(v >> (32 + shift)) & (kRoomsDigits - 1);
-            unsigned long long peer = __ballot(valid);
-            for (int bit = 0; bit < kRoomsDigitBits; ++bit) {
-                const bool one = (digit >> bit) & 1;
-                const unsigned long long m = __ballot(valid && one);
-                peer &= one ? m : ~m;
-            }
-            const int rank = __popcll(peer & ((1ull << lane) - 1ull));
-            const int pos = valid ? run_s[digit] + rank : 0;
-            __syncthreads();
-            if (valid && rank == 0) run_s[digit] += __popcll(peer);     // one lane per digit
-            __syncthreads();
-            if (valid) dst[pos] = v;                         // pos < M: a prefix of the M pairs' histogram
-        }
-    }
+    const int M = p.hdr->pairs, T = p.hdr->sort_tiles;
+    for (int tile = blockIdx.x; tile < T; tile += gridDim.x)
+        radix_scatter_tile<kRoomsDigitBits, int>(src, dst, M, tile, kRoomsSortTile, 32 + shift, p.hist, T, run_s, threadIdx.x);
 }
 
 __global__ __launch_bounds__(kSceneThreads) void rooms_segments_kernel(const RoomsArgs p, const unsigned long long *sorted)
@@ -454,8 +338,8 @@ __global__ __launch_bounds__(kRoomsScanThreads) void rooms_plan_kernel(const Roo
     const int tid = threadIdx.x, P = p.P, R = p.R;
     const int cells = p.hdr->cells;
     const int need = p.min_points < 1 ? 1 : p.min_points;
-    const int per = (cells + kRoomsScanThreads - 1) / kRoomsScanThreads;
-    const int c0 = tid * per < cells ? tid * per : cells, c1 = c0 + per < cells ? c0 + per : cells;
+    int c0, c1;
+    wg_chunk(cells, kRoomsScanThreads, tid, &c0, &c1);
     int kept = 0, small = 0, parts = 0, listed = 0;
     for (int g = c0; g < c1; ++g) {
         const int n = p.seg_end[g] - p.seg_start[g];
@@ -464,19 +348,12 @@ __global__ __launch_bounds__(kRoomsScanThreads) void rooms_plan_kernel(const Roo
         parts += n >= need ? (p.cover ? (n + P - 1) / P : 1) : 0;
     }
     int kept_all, small_all, parts_all, listed_all;
-    const int kbase = scene_exscan(kept, scan_s, tid, kRoomsScanThreads, &kept_all);
-    const int sbase = scene_exscan(small, scan_s, tid, kRoomsScanThreads, &small_all);
-    const int pbase = scene_exscan(parts, scan_s, tid, kRoomsScanThreads, &parts_all);
+    const int kbase = wg_exscan(kept, scan_s, tid, kRoomsScanThreads, &kept_all);
+    const int sbase = wg_exscan(small, scan_s, tid, kRoomsScanThreads, &small_all);
+    const int pbase = wg_exscan(parts, scan_s, tid, kRoomsScanThreads, &parts_all);
     int k = kbase, sm = sbase, first = pbase;
     int rp = 0;                                          // the first room whose cell_base is >= c0
-    if (c0 < c1) {
-        int lo = 0, hi = R + 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (p.cell_base[mid] < c0) lo = mid + 1; else hi = mid;
-        }
-        rp = lo;
-    }
+    if (c0 < c1) rp = lower_bound(0, R + 1, [&](int m) { return p.cell_base[m] < c0; });
     for (int g = c0; g < c1; ++g) {
         while (rp <= R && p.cell_base[rp] == g) p.room_pref[rp++] = make_int4(k, sm, first, 0);
         const int n = p.seg_end[g] - p.seg_start[g];
@@ -492,7 +369,7 @@ __global__ __launch_bounds__(kRoomsScanThreads) void rooms_plan_kernel(const Roo
         ++k;
         first += p.cover ? (n + P - 1) / P : 1;
     }
-    (void)scene_exscan(listed, scan_s, tid, kRoomsScanThreads, &listed_all);
+    (void)wg_exscan(listed, scan_s, tid, kRoomsScanThreads, &listed_all);
     for (int r = tid; r <= R; r += kRoomsScanThreads)    // the rooms behind the last cell
         if (p.cell_base[r] == cells) p.room_pref[r] = make_int4(kept_all, small_all, parts_all, 0);
     if (tid == 0) {
@@ -557,13 +434,6 @@ __global__ __launch_bounds__(kSceneThreads) void rooms_stats_kernel(const RoomsA
     }
 }
 
-__device__ __forceinline__ int32_t rooms_label(const RoomsArgs &p, size_t idx)
-{
-    if (p.label_bytes == 1) return (int32_t) static_cast<const uint8_t *>(p.labels)[idx];
-    if (p.label_bytes == 4) return static_cast<const int32_t *>(p.labels)[idx];
-    return (int32_t) static_cast<const long long *>(p.labels)[idx];
-}
-
 // scene_emit_body over the table: the block's room gives the frame and the key seed + room; the lists hold global rows.
 __global__ __launch_bounds__(kSceneThreads) void rooms_emit_kernel(const RoomsArgs p)
 {
@@ -614,7 +484,7 @@ __global__ __launch_bounds__(kSceneThreads) void rooms_emit_kernel(const RoomsAr
             }
             const int row = (int)(unsigned)pairs[off + m];   // inside the cell's list; the low word is the global row
             idx[t] = row;
-            if (lab) lab[t] = rooms_label(p, (size_t)row);
+            if (lab) lab[t] = row_label(p.labels, p.label_bytes, (size_t)row);
             const float *v = p.data + (size_t)row * K;
             mnx = fminf(mnx, v[0] - lox);
             mny = fminf(mny, v[1] - loy);

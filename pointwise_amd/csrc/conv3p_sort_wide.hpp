@@ -261,7 +261,7 @@ __global__ __launch_bounds__(kProviderTile) void provider_wide_gather_kernel(con
         xyz_s[3 * tid] = st[0];
         xyz_s[3 * tid + 1] = st[1];
         xyz_s[3 * tid + 2] = st[2];
-        if (p.labels_out && p.per_point) p.labels_out[o] = valid ? provider_label(p, (size_t)s * p.Nsrc + i) : -1;
+        if (p.labels_out && p.per_point) p.labels_out[o] = valid ? row_label(p.labels, p.label_bytes, (size_t)s * p.Nsrc + i) : -1;
         if (p.order_out) p.order_out[o] = i;
     }
     __syncthreads();
