@@ -1,4 +1,4 @@
-"""ctypes binding of libconv3p_hip.so -- the C ABI declared in include/conv3p.h.
+"""ctypes binding of libconv3p_hip.so -- the C ABI declared in include/conv3p.h and include/conv3p_graph.h.
 
 The product path has no CPU fallback: if the library is missing or a symbol is absent this
 module raises, loudly.
@@ -206,6 +206,14 @@ for _sfx, _real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
 
 SYMBOLS["conv3p_provider_batch_wide_f32"] = SYMBOLS["conv3p_provider_batch_f32"]   # the same parameter list
 
+# every symbol include/conv3p_graph.h declares, bound by load() next to SYMBOLS (a later maintenance change folds the
+# header and this table into the main ones)
+GRAPH_SYMBOLS = {
+    "conv3p_grid_agglomerate_scratch_bytes": (_sz, [ctypes.c_int64, ctypes.c_int64]),
+    "conv3p_grid_agglomerate_segments": (_i, [_vp] * 12 + [ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _i, _i] + [_vp] * 20
+                                         + [_vp, _sz, _vp]),
+}
+
 _LIB = None
 
 
@@ -223,7 +231,7 @@ def load():
             "libconv3p_hip.so not found at %s -- run `python -m pointwise_amd.build` "
             "(there is no CPU fallback in the product path)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(GRAPH_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1,4 +1,4 @@
-// conv3p_abi.hip -- host side of libconv3p_hip.so: the C ABI declared in include/conv3p.h.
+// conv3p_abi.hip -- host side of libconv3p_hip.so: the C ABI declared in include/conv3p.h and include/conv3p_graph.h.
 //
 // Replaces the host glue of the reference's GPU op (tf_conv3p_atrous.cu:541-642, :659-775):
 // no blocking D2H copies (stride / voxel arrive by value), no per-call temp allocation
@@ -19,6 +19,7 @@
 // conv3p_abi_{profile, layout, cache, search, routes, blocks}.hpp before the calls, conv3p_abi_stack.hpp (which composes
 // them) after, then the other subsystems (heads, pre-step, scene, grid).  DESIGN.md section 1 has the table.
 #include "../../include/conv3p.h"
+#include "../../include/conv3p_graph.h"
 #include "conv3p_host.hpp"
 #include "conv3p_kernels.hpp"
 #include "conv3p_stack_fused.hpp"
@@ -42,6 +43,7 @@
 #include "conv3p_grid_segments.hpp"
 #include "conv3p_grid_geometry.hpp"
 #include "conv3p_grid_adjacency.hpp"
+#include "conv3p_grid_agglomerate.hpp"
 #include "conv3p_grid_smooth.hpp"
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // conv3p_abi_grid.hpp -- host side of the voxel grid: subsample (single, rooms), project, neighbours, interpolate (plain,
-// rings), normals, segments (by label, smooth), absorb, segment geometry, segment pool, segment adjacency, merge.  Included
+// rings), normals, segments (by label, smooth), absorb, segment geometry, segment pool, segment adjacency, merge, agglomerate.  Included
 // by conv3p_abi.hip.
 namespace {
 
@@ -172,9 +172,8 @@ size_t carve_absorb(void *ws, int64_t M, AbsorbArgs &p)
 }
 // The adjacency call's: the counters, the radix passes' totals and histograms, the edge table of 2 max_edges + 64 slots (a
 // key and five counters each) and the two key buffers of the sort.  A function of max_edges alone: M only bounds it.
-size_t carve_adj(void *ws, int64_t max_edges, AdjArgs &p)
+void carve_adj_into(Carver &cv, int64_t max_edges, AdjArgs &p)
 {
-    Carver cv(ws);
     p.slots = 2ull * (unsigned long long)max_edges + kAdjSlack;
     p.sort_tiles = (int)(((size_t)max_edges + kAdjSortTile - 1) / kAdjSortTile);
     if (p.sort_tiles < 1) p.sort_tiles = 1;
@@ -185,17 +184,43 @@ size_t carve_adj(void *ws, int64_t max_edges, AdjArgs &p)
     p.vals = cv.take<int32_t>((size_t)p.slots * kAdjVals);
     p.sort_a = cv.take<unsigned long long>((size_t)max_edges);
     p.sort_b = cv.take<unsigned long long>((size_t)max_edges);
+}
+size_t carve_adj(void *ws, int64_t max_edges, AdjArgs &p)
+{
+    Carver cv(ws);
+    carve_adj_into(cv, max_edges, p);
     return cv.bytes();
 }
 // The merge call's: the tiles' roots, lab, parent, members, and the 64-bit label keys.
-size_t carve_merge(void *ws, int64_t M, MergeArgs &p)
+void carve_merge_into(Carver &cv, int64_t M, MergeArgs &p)
 {
-    Carver cv(ws);
     p.tile_count = cv.take<int32_t>(gseg_tiles(M));
     p.lab = cv.take<int32_t>((size_t)M);
     p.parent = cv.take<int32_t>((size_t)M);
     p.members = cv.take<int32_t>((size_t)M);
     p.best = cv.take<unsigned long long>((size_t)M);
+}
+size_t carve_merge(void *ws, int64_t M, MergeArgs &p)
+{
+    Carver cv(ws);
+    carve_merge_into(cv, M, p);
+    return cv.bytes();
+}
+// The agglomeration's: its header, the groups' words (grp, the weights, the tiles' log rows, the label keys, best), a column
+// for the edge_voxels adj_finish_kernel writes and H8 does not produce, then the adjacency call's and the merge call's as
+// they stand.
+size_t carve_agg(void *ws, int64_t M, int64_t max_edges, AggArgs &p, MergeArgs &m)
+{
+    Carver cv(ws);
+    p.hdr = cv.take<AggHeader>(1);
+    p.grp = cv.take<int32_t>((size_t)M);
+    p.weight_of = cv.take<int32_t>((size_t)M);
+    p.tile_count = cv.take<int32_t>(gseg_tiles(M));
+    p.label_key = cv.take<unsigned long long>((size_t)M);
+    p.best = cv.take<unsigned long long>((size_t)M);
+    p.t.edge_voxels = cv.take<int32_t>((size_t)max_edges);
+    carve_adj_into(cv, max_edges, p.t);
+    carve_merge_into(cv, M, m);
     return cv.bytes();
 }
 unsigned gseg_grid(size_t work) { return (unsigned)(work < (size_t)kGsegMaxGrid ? (work ? work : 1) : (size_t)kGsegMaxGrid); }
@@ -315,6 +340,40 @@ size_t carve_grid_rooms(void *ws, const GridPlan &w, int64_t N, int64_t R, GridR
     return cv.bytes();
 }
 
+// The seven launches of conv3p_grid_merge_segments, for it and for the agglomeration.
+void merge_launch(const MergeArgs &p, hipStream_t s)
+{
+    const unsigned per_thread = gseg_grid(((size_t)p.M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)p.ntiles);
+    hipLaunchKernelGGL(merge_init_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(merge_union_kernel, dim3(gseg_grid(((size_t)p.P + kGsegThreads - 1) / kGsegThreads)), dim3(kGsegThreads), 0,
+                       s, p);
+    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p.lab, p.parent, p.M, p.ntiles,
+                       p.tile_count);
+    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, p.tile_count, static_cast<int32_t *>(nullptr),
+                       p.ntiles, p.stats_out, static_cast<int32_t *>(nullptr));
+    hipLaunchKernelGGL(merge_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(merge_assign_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    hipLaunchKernelGGL(merge_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+}
+// The compaction, the 6 b launches of the radix passes and the finish of conv3p_grid_segment_adjacency, for it and for the
+// agglomeration: b the bytes of M - 1 >= S - 1, the passes a half of the key can need.
+void adj_order_launch(const AdjArgs &p, hipStream_t s)
+{
+    const unsigned per_slot = capped_grid(((size_t)p.slots + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
+    const unsigned per_tile = capped_grid((size_t)p.sort_tiles, kAdjMaxGrid);
+    const size_t rows = std::max((size_t)p.M + 1, (size_t)p.max_edges);
+    int bytes = 1;
+    while (bytes < kAdjMaxBytes && ((uint64_t)(p.M - 1) >> (8 * bytes))) ++bytes;
+    hipLaunchKernelGGL(adj_compact_kernel, dim3(per_slot), dim3(kAdjThreads), 0, s, p);
+    for (int half = 0; half < 2; ++half)
+        for (int j = 0; j < bytes; ++j) {                // a pass above the top byte of S - 1 returns at once
+            hipLaunchKernelGGL(adj_sort_hist_kernel, dim3(per_tile), dim3(kAdjThreads), 0, s, p, half, j);
+            hipLaunchKernelGGL(adj_sort_scan_kernel, dim3(kAdjDigits), dim3(kAdjScanThreads), 0, s, p, half, j);
+            hipLaunchKernelGGL(adj_sort_scatter_kernel, dim3(per_tile), dim3(64), 0, s, p, half, j);
+        }
+    hipLaunchKernelGGL(adj_finish_kernel, dim3(capped_grid((rows + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid)),
+                       dim3(kAdjThreads), 0, s, p);
+}
 }  // namespace
 
 extern "C" {
@@ -621,22 +680,9 @@ int conv3p_grid_segment_adjacency(const int32_t *neigh, const int32_t *segment, 
     const size_t cells = std::max((size_t)p.slots * kAdjVals, (size_t)M * 4);
     const unsigned per_cell = capped_grid((cells + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
     const unsigned per_voxel = capped_grid(((size_t)M + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
-    const unsigned per_slot = capped_grid(((size_t)p.slots + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
-    const unsigned per_tile = capped_grid((size_t)p.sort_tiles, kAdjMaxGrid);
-    const size_t rows = std::max((size_t)M + 1, (size_t)max_edges);
-    int bytes = 1;                                       // of M - 1 >= S - 1: the passes a half of the key can need
-    while (bytes < kAdjMaxBytes && ((uint64_t)(M - 1) >> (8 * bytes))) ++bytes;
     hipLaunchKernelGGL(adj_init_kernel, dim3(per_cell), dim3(kAdjThreads), 0, s, p);
     hipLaunchKernelGGL(adj_walk_kernel, dim3(per_voxel), dim3(kAdjThreads), 0, s, p);
-    hipLaunchKernelGGL(adj_compact_kernel, dim3(per_slot), dim3(kAdjThreads), 0, s, p);
-    for (int half = 0; half < 2; ++half)
-        for (int j = 0; j < bytes; ++j) {                // a pass above the top byte of S - 1 returns at once
-            hipLaunchKernelGGL(adj_sort_hist_kernel, dim3(per_tile), dim3(kAdjThreads), 0, s, p, half, j);
-            hipLaunchKernelGGL(adj_sort_scan_kernel, dim3(kAdjDigits), dim3(kAdjScanThreads), 0, s, p, half, j);
-            hipLaunchKernelGGL(adj_sort_scatter_kernel, dim3(per_tile), dim3(64), 0, s, p, half, j);
-        }
-    hipLaunchKernelGGL(adj_finish_kernel, dim3(capped_grid((rows + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid)),
-                       dim3(kAdjThreads), 0, s, p);
+    adj_order_launch(p, s);
     hipLaunchKernelGGL(adj_stats_kernel, dim3(1), dim3(64), 0, s, p);
     return hip_ok();
 }
@@ -671,17 +717,86 @@ int conv3p_grid_merge_segments(const int32_t *segment, const int32_t *seg_root, 
     p.M = (int)M; p.ntiles = (int)gseg_tiles(M);
     p.seg_map = seg_map; p.segment_out = segment_out; p.root_out = root_out; p.size_out = size_out; p.rows_out = rows_out;
     p.label_out = label_out; p.stats_out = stats_out; p.merge_stats = merge_stats;
-    const unsigned per_thread = gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads), per_tile = gseg_grid((size_t)p.ntiles);
-    hipLaunchKernelGGL(merge_init_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
-    hipLaunchKernelGGL(merge_union_kernel, dim3(gseg_grid(((size_t)P + kGsegThreads - 1) / kGsegThreads)), dim3(kGsegThreads), 0,
-                       s, p);
-    hipLaunchKernelGGL(gseg_flatten_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p.lab, p.parent, p.M, p.ntiles,
-                       p.tile_count);
-    hipLaunchKernelGGL(gseg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, p.tile_count, static_cast<int32_t *>(nullptr),
-                       p.ntiles, stats_out, static_cast<int32_t *>(nullptr));
-    hipLaunchKernelGGL(merge_number_kernel, dim3(per_tile), dim3(kGsegThreads), 0, s, p);
-    hipLaunchKernelGGL(merge_assign_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
-    hipLaunchKernelGGL(merge_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
+    merge_launch(p, s);
+    return hip_ok();
+}
+
+size_t conv3p_grid_agglomerate_scratch_bytes(int64_t M, int64_t max_edges)
+{
+    AggArgs p;
+    MergeArgs m;
+    if (M <= 0 || M > (int64_t)INT32_MAX || max_edges < 0 || max_edges > (int64_t)INT32_MAX) return 0;
+    return carve_agg(nullptr, M, max_edges, p, m);
+}
+
+// Every status first, in the order include/conv3p_graph.h gives; then 15 + 6 max_rounds + 6 b launches, b the bytes of
+// M - 1: fixed by (M, max_rounds).
+int conv3p_grid_agglomerate_segments(const int32_t *segment, const int32_t *seg_root, const int32_t *seg_size,
+                                     const int32_t *seg_rows, const int32_t *seg_label, const int32_t *seg_stats,
+                                     const int32_t *adj_start, const int32_t *edge_src, const int32_t *edge_dst,
+                                     const int32_t *edge_contacts, const int32_t *edge_offset, const int64_t *adj_stats,
+                                     int64_t M, int64_t max_edges, int min_size, int weight, int same_label,
+                                     int min_contacts, int max_rounds, int32_t *log_a, int32_t *log_b, int32_t *log_round,
+                                     int32_t *log_contacts, int32_t *seg_map, int32_t *segment_out, int32_t *root_out,
+                                     int32_t *size_out, int32_t *rows_out, int32_t *label_out, int32_t *stats_out,
+                                     int32_t *merge_stats, int32_t *voxel_label, int32_t *start_out, int32_t *src_out,
+                                     int32_t *dst_out, int32_t *contacts_out, int32_t *offset_out, int32_t *twin_out,
+                                     int64_t *agg_stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (M < 0 || max_edges < 0 || min_size < 1 || (weight != 0 && weight != 1) || (same_label != 0 && same_label != 1) ||
+        min_contacts < 1 || max_rounds < 1 || max_rounds > kAggMaxRounds)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M == 0) return CONV3P_OK;
+    if (!segment || !seg_root || !seg_size || !seg_rows || !seg_label || !seg_stats || !adj_start || !adj_stats || !log_a ||
+        !log_b || !log_round || !log_contacts || !seg_map || !segment_out || !root_out || !size_out || !rows_out ||
+        !label_out || !stats_out || !merge_stats || !voxel_label || !start_out || !agg_stats)
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (max_edges > 0 && (!edge_src || !edge_dst || !edge_contacts || !edge_offset || !src_out || !dst_out || !contacts_out ||
+                          !offset_out || !twin_out))
+        return CONV3P_ERR_INVALID_ARGUMENT;
+    if (M > (int64_t)INT32_MAX || max_edges > (int64_t)INT32_MAX) return CONV3P_ERR_UNSUPPORTED;
+    AggArgs p{};
+    MergeArgs m{};
+    const size_t need = carve_agg(workspace, M, max_edges, p, m);
+    if (!workspace || workspace_bytes < need) return CONV3P_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    p.seg_size = seg_size; p.seg_rows = seg_rows; p.seg_label = seg_label; p.seg_stats = seg_stats;
+    p.edge_src = edge_src; p.edge_dst = edge_dst; p.edge_contacts = edge_contacts; p.edge_offset = edge_offset;
+    p.adj_stats = reinterpret_cast<const long long *>(adj_stats);
+    p.M = (int)M; p.ntiles = (int)gseg_tiles(M); p.min_size = min_size; p.weight = weight; p.same_label = same_label;
+    p.min_contacts = min_contacts;
+    p.log_a = log_a; p.log_b = log_b; p.log_round = log_round; p.log_contacts = log_contacts;
+    p.seg_map = seg_map; p.segment_out = segment_out; p.label_out = label_out; p.stats_out = stats_out;
+    p.voxel_label = voxel_label; p.agg_stats = reinterpret_cast<long long *>(agg_stats);
+    p.t.seg_stats = stats_out;                           // the contracted graph is over the result's groups
+    p.t.M = (int)M; p.t.max_edges = (int)max_edges;
+    p.t.adj_start = start_out; p.t.edge_src = src_out; p.t.edge_dst = dst_out; p.t.edge_contacts = contacts_out;
+    p.t.edge_offset = offset_out; p.t.edge_twin = twin_out;
+    m.segment = segment; m.seg_root = seg_root; m.seg_size = seg_size; m.seg_rows = seg_rows; m.seg_label = seg_label;
+    m.seg_stats = seg_stats; m.pair_a = log_a; m.pair_b = log_b; m.select = nullptr; m.P = (long long)M;
+    m.M = (int)M; m.ntiles = p.ntiles;
+    m.seg_map = seg_map; m.segment_out = segment_out; m.root_out = root_out; m.size_out = size_out; m.rows_out = rows_out;
+    m.label_out = label_out; m.stats_out = stats_out; m.merge_stats = merge_stats;
+    const size_t cells = std::max((size_t)p.t.slots * kAdjVals, (size_t)M);
+    const dim3 per_cell(capped_grid((cells + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid)), threads(kAdjThreads);
+    const dim3 per_edge(capped_grid(((size_t)std::max<int64_t>(max_edges, 1) + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid));
+    const dim3 per_slot(capped_grid(((size_t)p.t.slots + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid));
+    const dim3 per_tile(gseg_grid((size_t)p.ntiles)), per_voxel(gseg_grid(((size_t)M + kGsegThreads - 1) / kGsegThreads));
+    hipLaunchKernelGGL(agg_init_kernel, per_cell, threads, 0, s, p);
+    for (int round = 0; round <= max_rounds; ++round) {  // the last one only chooses, for agg_stats[4:6]
+        hipLaunchKernelGGL(agg_contract_kernel, per_edge, threads, 0, s, p, static_cast<const int32_t *>(p.grp), 0);
+        hipLaunchKernelGGL(agg_choose_kernel, per_slot, threads, 0, s, p);
+        if (round == max_rounds) break;
+        hipLaunchKernelGGL(agg_count_kernel, per_tile, dim3(kGsegThreads), 0, s, p);
+        hipLaunchKernelGGL(agg_scan_kernel, dim3(1), dim3(kGsegScanThreads), 0, s, p);
+        hipLaunchKernelGGL(agg_log_kernel, per_tile, dim3(kGsegThreads), 0, s, p, round);
+        hipLaunchKernelGGL(agg_flatten_kernel, per_cell, threads, 0, s, p);
+    }
+    hipLaunchKernelGGL(agg_census_kernel, per_cell, threads, 0, s, p);
+    merge_launch(m, s);
+    hipLaunchKernelGGL(agg_contract_kernel, per_edge, threads, 0, s, p, static_cast<const int32_t *>(seg_map), 1);
+    adj_order_launch(p.t, s);
+    hipLaunchKernelGGL(agg_finish_kernel, per_voxel, dim3(kGsegThreads), 0, s, p);
     return hip_ok();
 }
 

@@ -36,6 +36,10 @@ tests/grid_ref.py restates it in numpy.
                      and summed direction of every edge and the border counts of every segment
                      (tests/grid_adjacency_ref.py); GridSegments.merge / SegmentAdjacency.merge: segments joined along
                      any selection of pairs -> a GridSegments again
+    SegmentAdjacency.agglomerate   -> SegmentAgglomeration: small groups of segments folded into the neighbour they touch
+                     most, round after round on the device, with the merged segments, their label per voxel, the log of
+                     the merges and the contracted graph (include/conv3p_graph.h, kernels in
+                     csrc/conv3p_grid_agglomerate.hpp; tests/grid_agglomerate_ref.py)
     grid_subsample_rooms    many clouds (N, K) with room_start (R + 1) on the device -> GridRoomSubsample: the same, the
                      voxels numbered room after room, plus voxel_room, voxel_start, room_stats
 
@@ -364,7 +368,7 @@ class GridSubsample:
         refused for a missing normal, by angle, by curvature, by features, labelled voxels without a normal, 0}.  The same
         seven launches behind a 64-byte memset.  geometry(), adjacency(), merge(), pool() and g.project(seg.segment) work
         on it as on any other; absorb() and clean_labels() do not: rule A2 assumes that neighbours of one class share a
-        segment.  Small patches are folded in with adjacency() and merge() (README: smooth segments).  With all six
+        segment.  Small patches are folded in with adjacency().agglomerate() (README: smooth segments).  With all six
         keywords at their defaults the call is the plain one, argument for argument."""
         dev = self.voxel_count.device
         M = self.voxel_count.shape[0]
@@ -842,6 +846,134 @@ class SegmentAdjacency:
         """The segments joined along the selected edges -> GridSegments: segments.merge(src, dst, select)."""
         _require(self._segments is not None, "merge works on the object adjacency() returned")
         return self._segments.merge(self.src, self.dst, select, out)
+
+    def agglomerate(self, min_size, weight="voxels", same_label=False, min_contacts=1, max_rounds=8, out=None):
+        """Small groups of segments folded into the neighbour they touch most, round after round, on the device ->
+        SegmentAgglomeration (include/conv3p_graph.h: conv3p_grid_agglomerate_segments, rules H1-H10;
+        tests/grid_agglomerate_ref.py).  The ready-made policy and its fixed point: what a loop of adjacency() and merge()
+        with a host read per round gives, without the reads and without a second walk over the voxels -- after a merge
+        the new graph is this one with its endpoints renamed and its parallel edges summed.
+
+        A group is small when it has fewer than min_size voxels (weight "voxels") or raw rows ("rows").  Every small
+        group proposes to the neighbouring group it has the most contacts with -- one that is not small before any small
+        one, the lowest number on a tie -- among those with at least min_contacts contacts and, with same_label, the same
+        label (a group's label is that of its member with the most voxels).  A round joins all proposals; the rounds end
+        when none is left (converged()) or after max_rounds (1 .. 32).  On a plain segmentation whose adjacency has the
+        connectivity the segments were made with, neighbours never share a label, so same_label merges nothing there: it
+        is for smooth and merged segmentations and for an adjacency at a wider connectivity.
+
+        The result carries segments, a GridSegments exactly like the one merge() returns on the log (geometry, adjacency,
+        merge, pool and g.project work on it); voxel_label, its label per voxel, so g.project(res.voxel_label) is the
+        cleaned label per raw row; the log of the merges (log_a, log_b, log_round, log_contacts: a dendrogram, and
+        merge(log_a, log_b, log_round < k) is the state after k rounds); and the contracted graph start, src, dst,
+        contacts, offset, twin over the result's groups, equal to segments.adjacency()'s at this connectivity.  voxels and
+        border are not additive under a merge and are not produced: call result.segments.adjacency() for them.
+
+        Works on the object adjacency() returned and on its trim(), for plain, smooth, merged and many-clouds
+        segmentations: no edge crosses a room, so nothing merges across rooms.  An adjacency that overflowed is unusable:
+        the result is the identity and stats[6] is 1.  out: a SegmentAgglomeration of an earlier call with the same M and
+        max_edges.  15 + 6 max_rounds + 6 b launches, b the bytes of M - 1 (fixed by M and max_rounds, whatever the
+        data), nothing synchronised on."""
+        _require_int(min_size, "min_size must be a positive integer", 1, 2 ** 31 - 1)
+        _require(isinstance(weight, str) and weight in _GEOMETRY_WEIGHTS, "weight must be \"voxels\" or \"rows\"")
+        _require(isinstance(same_label, bool), "same_label must be a bool")
+        _require_int(min_contacts, "min_contacts must be a positive integer", 1, 2 ** 31 - 1)
+        _require_int(max_rounds, "max_rounds must be an integer from 1 to 32", 1, 32)
+        seg = self._segments
+        _require(seg is not None and seg._source is not None,
+                 "agglomerate works on the object adjacency() returned, or on its trim()")
+        dev = self.start.device
+        M, max_edges = self.shape
+        _require_table(dev, (("segment", seg.segment, (M,)), ("root", seg.root, (M,)), ("size", seg.size, (M,)),
+                             ("rows", seg.rows, (M,)), ("label", seg.label, (M,)), ("stats", seg.stats, (8,)),
+                             ("start", self.start, (M + 1,)), ("src", self.src, (max_edges,)), ("dst", self.dst, (max_edges,)),
+                             ("contacts", self.contacts, (max_edges,)), ("offset", self.offset, (max_edges, 3))))
+        _require(_is_tensor(self.stats, torch.int64, (8,), dev), "stats must be a contiguous int64 (8,) tensor on the segments' device")
+        if out is not None:
+            _require(isinstance(out, SegmentAgglomeration) and out.shape == (M, max_edges) and out.start.device == dev
+                     and out.segments is not seg, "out was made for another shape")
+        _require(dev.type == "cuda", _NO_CPU)
+        if out is None:
+            out = SegmentAgglomeration(M, max_edges, dev)
+        res = out.segments
+        res._source = (seg._source[0], None, 0, seg._source[3], seg._source[4])
+        out.connectivity = self.connectivity
+        if M == 0:
+            _fill_empty(out)
+            res.stats.zero_()
+            res.merge_stats.zero_()
+            return out
+        lib = _lib.load()
+        ws = _grow(out, "workspace", int(lib.conv3p_grid_agglomerate_scratch_bytes(M, max_edges)), dev)
+        with torch.cuda.device(dev):
+            _call(lib.conv3p_grid_agglomerate_segments, seg.segment.data_ptr(), seg.root.data_ptr(), seg.size.data_ptr(),
+                  seg.rows.data_ptr(), seg.label.data_ptr(), seg.stats.data_ptr(), self.start.data_ptr(), _ptr(self.src),
+                  _ptr(self.dst), _ptr(self.contacts), _ptr(self.offset), self.stats.data_ptr(), M, max_edges, min_size,
+                  _GEOMETRY_WEIGHTS[weight], int(same_label), min_contacts, max_rounds, out.log_a.data_ptr(),
+                  out.log_b.data_ptr(), out.log_round.data_ptr(), out.log_contacts.data_ptr(), res.seg_map.data_ptr(),
+                  res.segment.data_ptr(), res.root.data_ptr(), res.size.data_ptr(), res.rows.data_ptr(), res.label.data_ptr(),
+                  res.stats.data_ptr(), res.merge_stats.data_ptr(), out.voxel_label.data_ptr(), out.start.data_ptr(),
+                  _ptr(out.src), _ptr(out.dst), _ptr(out.contacts), _ptr(out.offset), _ptr(out.twin), out.stats.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _stream(dev))
+        return out
+
+
+class SegmentAgglomeration:
+    """The outputs of SegmentAdjacency.agglomerate (include/conv3p_graph.h, rules H1-H10).  segments: a GridSegments as
+    merge() returns it (seg_map, merge_stats; geometry, adjacency, merge, pool work on it).  voxel_label int32 (M): the
+    label of every voxel's group, -1 outside every segment.  The log, int32 (M) each, a row per merge in ascending (round,
+    log_a): log_a and log_b, the root segments of the proposer and of its target in the numbers of the INPUT segmentation;
+    log_round; log_contacts, the contacts between the two groups at that round; rows past the last hold -1, -1, -1, 0.
+    The contracted graph over the result's groups, as SegmentAdjacency states it: start int32 (M + 1); src, dst, contacts,
+    twin int32 (max_edges), offset int32 (max_edges, 3).  stats int64 (8) on the device = {groups, segments, rounds that
+    had a proposal, merges P, small groups left, of those the ones that still have a candidate, input unusable, edges of
+    the contracted graph}."""
+
+    _FILL = (("voxel_label", -1), ("log_a", -1), ("log_b", -1), ("log_round", -1), ("log_contacts", 0), ("start", 0),
+             ("src", -1), ("dst", -1), ("contacts", 0), ("offset", 0), ("twin", -1), ("stats", 0))
+
+    def __init__(self, num_voxels, max_edges, device):
+        M, E = int(num_voxels), int(max_edges)
+        self.shape = (M, E)
+        self.segments = GridSegments(M, device)
+        self.segments._merged = True
+        self.segments.seg_map = torch.empty((M,), dtype=torch.int32, device=device)
+        self.segments.merge_stats = torch.zeros((4,), dtype=torch.int32, device=device)
+        self.voxel_label = torch.empty((M,), dtype=torch.int32, device=device)
+        for name in ("log_a", "log_b", "log_round", "log_contacts"):
+            setattr(self, name, torch.empty((M,), dtype=torch.int32, device=device))
+        self.start = torch.empty((M + 1,), dtype=torch.int32, device=device)
+        for name in ("src", "dst", "contacts", "twin"):
+            setattr(self, name, torch.empty((E,), dtype=torch.int32, device=device))
+        self.offset = torch.empty((E, 3), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((8,), dtype=torch.int64, device=device)
+        self.workspace = None
+        self.connectivity = None
+
+    def num_groups(self):
+        """The number of groups, the segments of the result: a host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def num_rounds(self):
+        """The rounds that merged something.  A host read."""
+        return int(self.stats[2])
+
+    def converged(self):
+        """Whether the fixed point was reached: no small group with a candidate is left (and the input was usable).  A
+        host read."""
+        s = self.stats.cpu()
+        return int(s[5]) == 0 and int(s[6]) == 0
+
+    def trim(self):
+        """Views of the log's rows and of the contracted graph's edge rows that are in use, as a SegmentAgglomeration
+        (segments, voxel_label, start and stats shared).  One host read."""
+        s = self.stats.cpu()
+        P, E = int(s[3]), int(s[7])
+        t = _view(self, SegmentAgglomeration, slice(P), ("log_a", "log_b", "log_round", "log_contacts"),
+                  ("segments", "voxel_label", "start", "stats", "connectivity"), shape=(self.shape[0], E), workspace=None)
+        for name in ("src", "dst", "contacts", "offset", "twin"):
+            setattr(t, name, getattr(self, name)[:E])
+        return t
 
 
 _GEOMETRY_WEIGHTS = {"voxels": 0, "rows": 1}
