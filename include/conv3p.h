@@ -1194,6 +1194,8 @@ int conv3p_grid_merge_segments(const int32_t *segment, const int32_t *seg_root, 
  *     65 <= M <= 128  with N > 312
  * which the forward serves.  Scratch from conv3p_fc_workspace_bytes: 0 where the FORWARD's constraints fail; it does
  * not reflect the backward's two regions (it is non-zero there).
+ * One size serves the forward, the backward and conv3p_fc_backward_step_f32, and each of them checks its buffer against
+ * that size (CONV3P_ERR_WORKSPACE), whichever part of it the call itself uses.
  * A non-finite input reaches exactly the outputs whose sums it enters (padded rows, columns and K-steps are zero on
  * both operands: no 0 * Inf).  M == 0: nothing forward; the backward writes dW = 0 and, when given, db = 0.
  * ------------------------------------------------------------------------------------------- */
@@ -1270,7 +1272,8 @@ int conv3p_seg_head_f64(const double *act, const int32_t *labels, size_t rows, i
  *   both in [0, num_class); exact.  Two launches.
  *
  * Scratch: conv3p_seg_head_weighted_workspace_bytes covers conv3p_seg_weight_total_* and conv3p_seg_head_weighted_*
- * (one buffer may serve both calls on one stream), conv3p_seg_confusion_workspace_bytes the matrix; 0 for a refused
+ * (one buffer may serve both calls on one stream; each checks for the whole of it, as conv3p_seg_head_* check for the
+ * whole of conv3p_seg_head_workspace_bytes), conv3p_seg_confusion_workspace_bytes the matrix; 0 for a refused
  * shape.  Status, decided before any launch: CONV3P_ERR_INVALID_ARGUMENT for rows == 0, num_class < 2, a NULL act /
  * labels / loss_sum / counts (total; pred / confusion), label_smoothing outside [0, 1) or NaN; CONV3P_ERR_UNSUPPORTED
  * above the class limit of conv3p_seg_head_* (fp32 and the confusion matrix 128, fp64 79); CONV3P_ERR_WORKSPACE.

@@ -18,16 +18,26 @@ template <typename T> bool seg_plan(size_t rows, int C, SegPlan &p)
 }
 // The head's workspace: one partial record per workgroup.
 inline size_t carve_seg(void *ws, unsigned grid, int C, char *&part) { return carve_one(ws, (size_t)grid * seg_record_bytes(C), part); }
+// What conv3p_seg_head_workspace_bytes declares: one-wave workgroups, the most records either element type takes.  A call
+// checks its buffer against the size its export declares, not against what this call's plan happens to use, so that a
+// caller who allocates less learns it at the first call and not when another shape changes the plan.
+inline size_t seg_declared_bytes(size_t rows, int C)
+{
+    char *part;
+    return carve_seg(nullptr, capped_grid((rows + 63) / 64, kSegMaxGrid), C, part);
+}
 
 template <typename T>
 int seg_head_impl(const T *act, const int32_t *labels, size_t rows, int C, T grad_scale, T *grad_act, int32_t *pred,
-                  double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream)
+                  double *loss_sum, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream,
+                  size_t declared = 0)
 {
     if (rows == 0 || C < 2 || !act || !labels || !loss_sum || !counts) return CONV3P_ERR_INVALID_ARGUMENT;
     SegPlan p;
     if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;   // (int32 partial counters)
     char *part;
-    TRY(buf_check(workspace, workspace_bytes, carve_seg(workspace, p.grid, C, part)));
+    // declared: bytes the entry point's own export declares (the weighted head's covers this one's)
+    TRY(buf_check(workspace, workspace_bytes, std::max({carve_seg(workspace, p.grid, C, part), seg_declared_bytes(rows, C), declared})));
     hipStream_t s = static_cast<hipStream_t>(stream);
     {
         Scope sc(K_SEG_HEAD, s);
@@ -53,6 +63,8 @@ inline unsigned seg_conf_grid(size_t rows)
     return capped_grid(wgs, kSegConfMaxGrid);
 }
 inline size_t seg_total_bytes(size_t rows) { return up((size_t)seg_total_grid(rows) * sizeof(SegTotalRecord)); }
+// What conv3p_seg_head_weighted_workspace_bytes declares: one buffer serves the total and the head.
+inline size_t seg_weighted_declared_bytes(size_t rows, int C) { return std::max(seg_declared_bytes(rows, C), seg_total_bytes(rows)); }
 
 template <typename T>
 int seg_weight_total_impl(const int32_t *labels, size_t rows, int C, const T *class_weight, const T *point_weight,
@@ -61,7 +73,7 @@ int seg_weight_total_impl(const int32_t *labels, size_t rows, int C, const T *cl
     if (rows == 0 || C < 2 || !labels || !total) return CONV3P_ERR_INVALID_ARGUMENT;
     SegPlan p;
     if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;
-    TRY(buf_check(workspace, workspace_bytes, seg_total_bytes(rows)));
+    TRY(buf_check(workspace, workspace_bytes, seg_weighted_declared_bytes(rows, C)));
     hipStream_t s = static_cast<hipStream_t>(stream);
     SegTotalRecord *part = static_cast<SegTotalRecord *>(workspace);
     const unsigned grid = seg_total_grid(rows);
@@ -85,11 +97,11 @@ int seg_head_weighted_impl(const T *act, const int32_t *labels, size_t rows, int
     const T ls = (T)smoothing;                                                         // what the kernel smooths with
     if (!class_weight && !point_weight && ls == T(0) && !denominator)                  // the plain head, bit for bit
         return seg_head_impl<T>(act, labels, rows, C, grad_scale, grad_act, pred, loss_sum, counts, workspace,
-                                workspace_bytes, stream);
+                                workspace_bytes, stream, seg_weighted_declared_bytes(rows, C));
     SegPlan p;
     if (rows > ((size_t)1 << 40) || !seg_plan<T>(rows, C, p)) return CONV3P_ERR_UNSUPPORTED;
     char *part;
-    TRY(buf_check(workspace, workspace_bytes, carve_seg(workspace, p.grid, C, part)));
+    TRY(buf_check(workspace, workspace_bytes, std::max(carve_seg(workspace, p.grid, C, part), seg_weighted_declared_bytes(rows, C))));
     hipStream_t s = static_cast<hipStream_t>(stream);
     {
         Scope sc(K_SEG_HEAD, s);
@@ -350,7 +362,8 @@ int conv3p_fc_backward_f32(const float *x, const float *W, const float *y, const
     FcPlan p;
     if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;
     float *dz;
-    TRY(buf_check(workspace, workspace_bytes, carve_fc_dz(workspace, M, N, dz)));
+    // (against the declared size, which also covers the forward's partials: see seg_declared_bytes)
+    TRY(buf_check(workspace, workspace_bytes, std::max(carve_fc_dz(workspace, M, N, dz), conv3p_fc_workspace_bytes(M, K, N))));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int dw_steps = M <= 32 ? 16 : M <= 64 ? 32 : 64;
     if ((size_t)2 * dw_steps * (N + 1) * 4 > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // before anything is launched
@@ -376,8 +389,7 @@ int conv3p_fc_backward_f32(const float *x, const float *W, const float *y, const
 size_t conv3p_seg_head_workspace_bytes(size_t rows, int num_class)
 {
     if (rows == 0 || num_class < 2 || num_class > kSegMaxClass) return 0;
-    char *part;   // (one-wave workgroups, the most records either element type takes)
-    return carve_seg(nullptr, capped_grid((rows + 63) / 64, kSegMaxGrid), num_class, part);
+    return seg_declared_bytes(rows, num_class);
 }
 int conv3p_seg_head_f32(const float *act, const int32_t *labels, size_t rows, int num_class, float grad_scale,
                         float *grad_act, int32_t *pred, double *loss_sum, int64_t *counts, void *workspace,
@@ -398,8 +410,7 @@ size_t conv3p_seg_head_weighted_workspace_bytes(size_t rows, int num_class)
 {
     const size_t head = conv3p_seg_head_workspace_bytes(rows, num_class);
     if (head == 0) return 0;
-    const size_t total = seg_total_bytes(rows);
-    return head > total ? head : total;
+    return seg_weighted_declared_bytes(rows, num_class);
 }
 int conv3p_seg_weight_total_f32(const int32_t *labels, size_t rows, int num_class, const float *class_weight,
                                 const float *point_weight, double *total, void *workspace, size_t workspace_bytes,
@@ -509,7 +520,8 @@ int conv3p_fc_backward_step_f32(const float *x, float *W, float *b, const float 
     FcPlan p;
     if (!fc_plan(M, K, N, p)) return CONV3P_ERR_UNSUPPORTED;
     float *dz;
-    TRY(buf_check(workspace, workspace_bytes, carve_fc_dz(workspace, M, N, dz)));
+    // (against the declared size, which also covers the forward's partials: see seg_declared_bytes)
+    TRY(buf_check(workspace, workspace_bytes, std::max(carve_fc_dz(workspace, M, N, dz), conv3p_fc_workspace_bytes(M, K, N))));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int dw_steps = M <= 32 ? 16 : M <= 64 ? 32 : 64;
     if ((size_t)2 * dw_steps * (N + 1) * 4 > kMaxLds) return CONV3P_ERR_UNSUPPORTED;   // before anything is launched
