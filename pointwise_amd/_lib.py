@@ -1,4 +1,5 @@
-"""ctypes binding of libconv3p_hip.so -- the C ABI declared in include/conv3p.h and include/conv3p_graph.h.
+"""ctypes binding of libconv3p_hip.so -- the C ABI declared in include/conv3p.h, include/conv3p_graph.h and
+include/conv3p_knn.h.
 
 The product path has no CPU fallback: if the library is missing or a symbol is absent this
 module raises, loudly.
@@ -214,6 +215,17 @@ GRAPH_SYMBOLS = {
                                          + [_vp, _sz, _vp]),
 }
 
+# every symbol include/conv3p_knn.h declares, bound by load() next to the other two tables
+_i64 = ctypes.c_int64
+KNN_SYMBOLS = {
+    "conv3p_grid_knn_scratch_bytes": (_sz, [_i64, _i64]),
+    "conv3p_grid_knn_f32": (_i, [_vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, ctypes.c_float, _i, _i, _i]
+                            + [_vp] * 7 + [_vp, _sz, _vp]),
+    "conv3p_grid_interpolate_knn_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "conv3p_grid_interpolate_knn_i64": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "conv3p_grid_normals_knn_f32": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _LIB = None
 
 
@@ -231,7 +243,7 @@ def load():
             "libconv3p_hip.so not found at %s -- run `python -m pointwise_amd.build` "
             "(there is no CPU fallback in the product path)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(GRAPH_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(GRAPH_SYMBOLS.items()) + list(KNN_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -21,6 +21,9 @@
 //                         these, set the time.  The sweep count is fixed, every rotation is taken (one whose off-diagonal
 //                         entry is 0 is the identity by a select), so two calls give the same bits.
 //
+// R4, R5 / R6 and the stores are functions (normals_flag, normals_solve, normals_store): grid_knn_normals_kernel of
+// conv3p_grid_knn.hpp, the same rules on the neighbours of a k-NN table, calls them too.
+//
 // The only atomics are the integer adds of the four counts (per thread into LDS after its loop, then one add per workgroup
 // and count); every output word is written once by a plain store; a voxel's result depends on its own inputs alone, so
 // nothing depends on the launch geometry.
@@ -55,6 +58,79 @@ __device__ __forceinline__ void normals_rotate(double &app, double &aqq, double 
     const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
     const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
     v0p = a0; v0q = b0; v1p = a1; v1q = b1; v2p = a2; v2q = b2;
+}
+
+// R5 and R6 for a voxel with flags 0: the unit eigenvector of the smallest eigenvalue of the moments' covariance, oriented,
+// and the curvature.  p is the voxel's representative.
+__device__ __forceinline__ void normals_solve(float cxx, float cxy, float cxz, float cyy, float cyz, float czz, float px, float py,
+                                              float pz, int v, const int32_t *voxel_room, const float *viewpoint, int V,
+                                              float &nx, float &ny, float &nz, float &cv)
+{
+    double a00 = cxx, a01 = cxy, a02 = cxz, a11 = cyy, a12 = cyz, a22 = czz;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll
+    for (int sweep = 0; sweep < kNormalsSweeps; ++sweep) {
+        normals_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+        normals_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+        normals_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+    }
+    const int k = (a00 <= a11 && a00 <= a22) ? 0 : (a11 <= a22 ? 1 : 2);     // the lowest of equal eigenvalues
+    const double l0 = k == 0 ? a00 : (k == 1 ? a11 : a22);
+    const double ex = k == 0 ? v00 : (k == 1 ? v01 : v02);
+    const double ey = k == 0 ? v10 : (k == 1 ? v11 : v12);
+    const double ez = k == 0 ? v20 : (k == 1 ? v21 : v22);
+    const double len = sqrt((ex * ex + ey * ey) + ez * ez);
+    nx = (float)(ex / len); ny = (float)(ey / len); nz = (float)(ez / len);
+    cv = (float)(l0 / ((a00 + a11) + a22));
+    cv = fminf(fmaxf(cv, 0.0f), 1.0f / 3.0f);
+    float s = 0.0f;                              // R6, on the float32 vector about to be stored
+    bool have = false;
+    if (viewpoint) {
+        int r = 0;
+        if (V > 1) r = voxel_room ? voxel_room[v] : -1;
+        if (r >= 0 && r < V) {
+            const float *wv = viewpoint + (size_t)r * 3;
+            s = ((wv[0] - px) * nx + (wv[1] - py) * ny) + (wv[2] - pz) * nz;
+            have = normals_finite(s) && s != 0.0f;
+        }
+    }
+    bool flip;
+    if (have) {
+        flip = s < 0.0f;
+    } else {                                     // the largest magnitude positive, the lowest axis of a tie
+        const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
+        const float top = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+        flip = top < 0.0f;
+    }
+    if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+}
+
+// R4 from the sample count and the moments
+__device__ __forceinline__ int normals_flag(int n, int min_neighbors, float mx, float my, float mz, float cxx, float cxy, float cxz,
+                                            float cyy, float cyz, float czz)
+{
+    const bool fin = normals_finite(mx) && normals_finite(my) && normals_finite(mz) && normals_finite(cxx) &&
+                     normals_finite(cxy) && normals_finite(cxz) && normals_finite(cyy) && normals_finite(cyz) &&
+                     normals_finite(czz);
+    const float tr = (cxx + cyy) + czz;
+    return n < min_neighbors ? 1 : ((!fin || !(tr > 0.0f)) ? 2 : 0);
+}
+
+// a voxel's outputs, every word written once
+__device__ __forceinline__ void normals_store(int v, float nx, float ny, float nz, float cv, int n, int fl, float mx, float my,
+                                              float mz, float cxx, float cxy, float cxz, float cyy, float cyz, float czz,
+                                              float *normals, float *curvature, int32_t *samples, int32_t *flags, float *moments)
+{
+    normals[(size_t)v * 3 + 0] = nx;
+    normals[(size_t)v * 3 + 1] = ny;
+    normals[(size_t)v * 3 + 2] = nz;
+    curvature[v] = cv;
+    samples[v] = n;
+    flags[v] = fl;
+    if (moments) {
+        float *mo = moments + (size_t)v * 9;
+        mo[0] = mx; mo[1] = my; mo[2] = mz; mo[3] = cxx; mo[4] = cxy; mo[5] = cxz; mo[6] = cyy; mo[7] = cyz; mo[8] = czz;
+    }
 }
 
 __global__ __launch_bounds__(kNormalsThreads) void grid_normals_kernel(const float *voxel_data, int K, const int32_t *neigh,
@@ -116,61 +192,10 @@ __global__ __launch_bounds__(kNormalsThreads) void grid_normals_kernel(const flo
                 czz = ok ? czz + ez * ez : czz;
             }
             cxx = cxx / fn; cxy = cxy / fn; cxz = cxz / fn; cyy = cyy / fn; cyz = cyz / fn; czz = czz / fn;
-            const bool fin = normals_finite(mx) && normals_finite(my) && normals_finite(mz) && normals_finite(cxx) &&
-                             normals_finite(cxy) && normals_finite(cxz) && normals_finite(cyy) && normals_finite(cyz) &&
-                             normals_finite(czz);
-            const float tr = (cxx + cyy) + czz;
-            fl = n < min_neighbors ? 1 : ((!fin || !(tr > 0.0f)) ? 2 : 0);   // R4
+            fl = normals_flag(n, min_neighbors, mx, my, mz, cxx, cxy, cxz, cyy, cyz, czz);   // R4
         }
-        if (fl == 0) {                                   // R5
-            double a00 = cxx, a01 = cxy, a02 = cxz, a11 = cyy, a12 = cyz, a22 = czz;
-            double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-#pragma unroll
-            for (int sweep = 0; sweep < kNormalsSweeps; ++sweep) {
-                normals_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-                normals_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-                normals_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-            }
-            const int k = (a00 <= a11 && a00 <= a22) ? 0 : (a11 <= a22 ? 1 : 2);     // the lowest of equal eigenvalues
-            const double l0 = k == 0 ? a00 : (k == 1 ? a11 : a22);
-            const double ex = k == 0 ? v00 : (k == 1 ? v01 : v02);
-            const double ey = k == 0 ? v10 : (k == 1 ? v11 : v12);
-            const double ez = k == 0 ? v20 : (k == 1 ? v21 : v22);
-            const double len = sqrt((ex * ex + ey * ey) + ez * ez);
-            nx = (float)(ex / len); ny = (float)(ey / len); nz = (float)(ez / len);
-            cv = (float)(l0 / ((a00 + a11) + a22));
-            cv = fminf(fmaxf(cv, 0.0f), 1.0f / 3.0f);
-            float s = 0.0f;                              // R6, on the float32 vector about to be stored
-            bool have = false;
-            if (viewpoint) {
-                int r = 0;
-                if (V > 1) r = voxel_room ? voxel_room[v] : -1;
-                if (r >= 0 && r < V) {
-                    const float *wv = viewpoint + (size_t)r * 3;
-                    s = ((wv[0] - px) * nx + (wv[1] - py) * ny) + (wv[2] - pz) * nz;
-                    have = normals_finite(s) && s != 0.0f;
-                }
-            }
-            bool flip;
-            if (have) {
-                flip = s < 0.0f;
-            } else {                                     // the largest magnitude positive, the lowest axis of a tie
-                const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
-                const float top = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
-                flip = top < 0.0f;
-            }
-            if (flip) { nx = -nx; ny = -ny; nz = -nz; }
-        }
-        normals[(size_t)v * 3 + 0] = nx;
-        normals[(size_t)v * 3 + 1] = ny;
-        normals[(size_t)v * 3 + 2] = nz;
-        curvature[v] = cv;
-        samples[v] = n;
-        flags[v] = fl;
-        if (moments) {
-            float *mo = moments + (size_t)v * 9;
-            mo[0] = mx; mo[1] = my; mo[2] = mz; mo[3] = cxx; mo[4] = cxy; mo[5] = cxz; mo[6] = cyy; mo[7] = cyz; mo[8] = czz;
-        }
+        if (fl == 0) normals_solve(cxx, cxy, cxz, cyy, cyz, czz, px, py, pz, v, voxel_room, viewpoint, V, nx, ny, nz, cv);   // R5, R6
+        normals_store(v, nx, ny, nz, cv, n, fl, mx, my, mz, cxx, cxy, cxz, cyy, cyz, czz, normals, curvature, samples, flags, moments);
         c_ok += fl == 0;
         c_few += fl == 1;
         c_deg += fl == 2;

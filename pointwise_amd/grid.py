@@ -21,6 +21,10 @@ tests/grid_ref.py restates it in numpy.
                      a row with no voted voxel in its 27 cells searches ring after ring (tests/grid_interp_rings_ref.py)
     GridSubsample.normals       -> GridNormals: a unit normal, a curvature, the sample count and a flag per voxel, from the
                      representatives of the 3 x 3 x 3 cells around it (tests/grid_normals_ref.py)
+    GridSubsample.knn           -> GridKnn: the k nearest voxels of every voxel or raw row, an exact k-NN within `rings` cells
+                     with a per-query proof that nothing nearer lies further out (include/conv3p_knn.h, kernels in
+                     csrc/conv3p_grid_knn.hpp; tests/grid_knn_ref.py); GridKnn.interpolate and GridKnn.normals are
+                     interpolate and normals on those neighbours: rows next to a hole, thin and sparse surfaces
     GridSubsample.with_normals  data and those normals side by side, (M, K + 3): what scene_blocks takes in place of data
     GridSubsample.segments      voxel labels -> GridSegments: the connected pieces of one class over the 27-cell table (a
                      lock-free union-find), their root, size, rows and label (tests/grid_segments_ref.py);
@@ -93,6 +97,27 @@ def _require_table(dev, entries, vector=True):
     for name, t, shape in entries:
         _require(_is_tensor(t, torch.int32, shape, dev) and (shape is not None or not vector or (t.dim() == 1 and t.numel() >= 1)),
                  _TABLE_MESSAGE % name)
+
+
+def _check_viewpoint(grid, viewpoint, dev, rooms):
+    """The viewpoint argument of the normals calls checked -> the three numbers to upload, None for a tensor or no
+    viewpoint."""
+    upload = None
+    if viewpoint is not None and not isinstance(viewpoint, torch.Tensor):
+        try:
+            upload = [float(x) for x in viewpoint]
+        except (TypeError, ValueError):
+            upload = None
+        _require(upload is not None and len(upload) == 3 and all(math.isfinite(x) for x in upload)
+                 and all(abs(x) <= float(np.finfo(np.float32).max) for x in upload), _VIEWPOINT)
+    elif viewpoint is not None:
+        _require(_is_tensor(viewpoint, torch.float32, dev=dev, ndim=2) and viewpoint.shape[1] == 3 and viewpoint.shape[0] >= 1,
+                 _VIEWPOINT)
+        if viewpoint.shape[0] != 1:
+            _require(rooms is not None, "a viewpoint per room needs a GridRoomSubsample")
+            _require(viewpoint.shape[0] == grid.voxel_start.numel() - 1,
+                     "viewpoint must have one row, or one per room (%d)" % (grid.voxel_start.numel() - 1))
+    return upload
 
 
 class GridSubsample:
@@ -285,21 +310,7 @@ class GridSubsample:
         rooms = getattr(self, "voxel_room", None)
         _require_int(min_neighbors, "min_neighbors must be an integer in [3, 27]", 3, 27)
         _require(isinstance(return_moments, bool), "return_moments must be a bool")
-        upload = None
-        if viewpoint is not None and not isinstance(viewpoint, torch.Tensor):
-            try:
-                upload = [float(x) for x in viewpoint]
-            except (TypeError, ValueError):
-                upload = None
-            _require(upload is not None and len(upload) == 3 and all(math.isfinite(x) for x in upload)
-                     and all(abs(x) <= float(np.finfo(np.float32).max) for x in upload), _VIEWPOINT)
-        elif viewpoint is not None:
-            _require(_is_tensor(viewpoint, torch.float32, dev=dev, ndim=2) and viewpoint.shape[1] == 3 and viewpoint.shape[0] >= 1,
-                     _VIEWPOINT)
-            if viewpoint.shape[0] != 1:
-                _require(rooms is not None, "a viewpoint per room needs a GridRoomSubsample")
-                _require(viewpoint.shape[0] == self.voxel_start.numel() - 1,
-                         "viewpoint must have one row, or one per room (%d)" % (self.voxel_start.numel() - 1))
+        upload = _check_viewpoint(self, viewpoint, dev, rooms)
         _require(_is_tensor(self.data, torch.float32) and K >= 3, "data must be a contiguous float32 (M, K >= 3) tensor")
         if rooms is not None:
             _require_tensor(rooms, "voxel_room must be a contiguous int32 (M,) tensor on the cloud's device", torch.int32, (M,), dev)
@@ -335,6 +346,70 @@ class GridSubsample:
         _require(isinstance(curvature, bool), "curvature must be a bool")
         parts = [self.data, nrm.normals] + ([nrm.curvature[:, None]] if curvature else [])
         return torch.cat(parts, dim=1).contiguous()
+
+    def knn(self, voxel, points=None, query_voxel=None, k=8, rings=2, valid_labels=None, exclude_self=False, out=None):
+        """The k nearest voxels of every query -> GridKnn: an exact k-NN among the cells within Chebyshev distance `rings`
+        of the query's own cell, in ascending (d2, voxel), with the proof per query of whether those are the k nearest of
+        the whole room (include/conv3p_knn.h: conv3p_grid_knn_f32, rules K1-K8; tests/grid_knn_ref.py).
+
+        voxel is the lattice step the subsampling was given (the object does not keep it); it only decides how early a
+        query may stop, never which neighbours it gets.  points=None: the voxels query themselves (Q = max_voxels; the
+        table GridKnn.normals takes).  points: the raw (N, K) tensor the subsampling was given, query_voxel defaulting to
+        inverse; or any float32 (Q, K >= 3) rows with query_voxel int32 (Q), the voxel whose cell each row lies in (a
+        negative entry: no neighbours).  k in [1, 16], rings in [1, 8].  valid_labels int32 (M): voxels with a negative
+        entry are no neighbours; a SceneScores: its labels().  exclude_self: a query's own voxel is no neighbour.  out: a
+        GridKnn of an earlier call with the same shapes.  Works on a trimmed object and on many clouds as they stand
+        (rooms share nothing).  Nothing is synchronised on; the launches depend on nothing but rings > 1 (plus the
+        neighbour table's launch on first use); the scratch is kept on the object."""
+        from .scene import SceneScores
+        dev = self.data.device
+        M, K = self.data.shape
+        _require(isinstance(voxel, (int, float, np.integer, np.floating)) and not isinstance(voxel, bool) and math.isfinite(voxel)
+                 and math.isfinite(float(np.float32(voxel))) and float(np.float32(voxel)) > 0, "voxel must be finite and positive")
+        voxel = float(np.float32(voxel))
+        if points is None:
+            _require(query_voxel is None, "query_voxel needs points")
+            _require(_is_tensor(self.data, torch.float32) and K >= 3, "data must be a contiguous float32 (M, K >= 3) tensor")
+            query, Q = self.data, M
+        else:
+            _require(_is_tensor(points, torch.float32, ndim=2, contiguous=False) and points.shape[1] >= 3,
+                     "points must be a float32 (Q, K >= 3) tensor, xyz first")
+            _require(points.is_contiguous() and points.device == dev, "points must be contiguous and on the cloud's device")
+            query, Q = points, points.shape[0]
+            if query_voxel is None:
+                query_voxel = self.inverse
+            _require_tensor(query_voxel, "query_voxel must be a contiguous int32 (Q,) tensor on the cloud's device (the default, "
+                            "inverse, has %d rows)" % self.inverse.numel(), torch.int32, (Q,), dev)
+        _require_int(k, "k must be an integer in [1, 16]", 1, 16)
+        _require_int(rings, "rings must be an integer in [1, 8]", 1, 8)
+        _require(isinstance(exclude_self, bool), "exclude_self must be a bool")
+        if isinstance(valid_labels, SceneScores):
+            _require(valid_labels.device == dev, "valid_labels must live on the cloud's device")
+        elif valid_labels is not None:
+            _require_tensor(valid_labels, "valid_labels must be a contiguous int32 (M,) tensor on the cloud's device, or a "
+                            "SceneScores", torch.int32, (M,), dev)
+        if out is not None:
+            _require(isinstance(out, GridKnn) and out.shape == (Q, k) and out.index.device == dev, "out was made for another shape")
+        room, start = self._table(dev, M, vector=True)
+        _require(dev.type == "cuda", _NO_CPU)
+        if isinstance(valid_labels, SceneScores):
+            valid_labels = valid_labels.labels()
+            _require(valid_labels.numel() == M, "valid_labels has %d rows, the subsampling %d voxels" % (valid_labels.numel(), M))
+        if out is None:
+            out = GridKnn(Q, k, dev)
+        out.grid, out.voxel_queries = self, points is None
+        rooms = room is not None and M > 0
+        num_rooms = start.numel() - 1 if rooms else 0
+        neigh = self.neighbors()
+        lib = _lib.load()
+        ws = _grow(self, "_knn_scratch", int(lib.conv3p_grid_knn_scratch_bytes(Q, num_rooms)), dev)
+        with torch.cuda.device(dev):
+            _call(lib.conv3p_grid_knn_f32, _ptr(query), Q, query.shape[1], _ptr(query_voxel), _ptr(self.data), K, _ptr(neigh),
+                  _ptr(self.voxel_cell), _ptr(room, rooms), _ptr(start, rooms), num_rooms, self.stats.data_ptr(), M,
+                  _ptr(valid_labels), voxel, k, rings, int(exclude_self), _ptr(out.index), _ptr(out.d2), _ptr(out.count),
+                  _ptr(out.ring), _ptr(out.scanned), _ptr(out.certified), out.stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                  _stream(dev))
+        return out
 
     def segments(self, voxel_labels=None, num_class=None, connectivity=26, out=None, *, normals=None, max_angle=None,
                  signed=False, max_curvature=None, features=None, max_difference=None):
@@ -1039,6 +1114,110 @@ class SegmentGeometry:
         S = self.num_segments()
         return _view(self, SegmentGeometry, slice(S), ("cell_box", "box", "moments", "centroid", "eigenvalues", "axes", "extent"),
                      ("stats",), shape=(S,))
+
+
+class GridKnn:
+    """The outputs of GridSubsample.knn: index int32 (Q, k), the k nearest voxels of every query in ascending (d2, voxel),
+    -1 past the kept ones; d2 float32 (Q, k), +inf there; count int32 (Q), the kept; ring int32 (Q), the largest Chebyshev
+    cell distance among them; scanned int32 (Q), the ring the search stopped at; certified int32 (Q), 1 where the kept
+    are proven to be the k nearest of the whole room; stats int64 (16) on the device = {queries with k neighbours, with
+    fewer, with none, queries that are not live, certified queries, the sum of scanned, queries by ring 0 .. 8, 0}."""
+
+    def __init__(self, num_queries, k, device):
+        Q, k = int(num_queries), int(k)
+        self.shape = (Q, k)
+        self.index = torch.empty((Q, k), dtype=torch.int32, device=device)
+        self.d2 = torch.empty((Q, k), dtype=torch.float32, device=device)
+        self.count = torch.empty((Q,), dtype=torch.int32, device=device)
+        self.ring = torch.empty((Q,), dtype=torch.int32, device=device)
+        self.scanned = torch.empty((Q,), dtype=torch.int32, device=device)
+        self.certified = torch.empty((Q,), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((16,), dtype=torch.int64, device=device)
+        self.grid, self.voxel_queries = None, False
+
+    def num_certified(self):
+        """The number of certified queries: the one host read (a synchronisation)."""
+        return int(self.stats[4])
+
+    def interpolate(self, voxel_scores, k=None, return_scores=False, out=None):
+        """Scores per voxel -> a label per query (Q) int32, or (labels, scores float32 (Q, C)) with return_scores: rule 5
+        of GridSubsample.interpolate on the first min(k, count) neighbours of the table (include/conv3p_knn.h:
+        conv3p_grid_interpolate_knn_f32 / _i64).  k=None: the table's width.  voxel_scores: a contiguous float32 (M, C)
+        tensor, C <= 128, or a SceneScores, whose exact int64 sums are read as they are.  Which voxels are neighbours
+        was decided by knn()'s valid_labels.  -1 and a zero score row for a query without a neighbour; interp_stats int64
+        (2) on the device = {rows interpolated, rows without a neighbour}.  One kernel launch behind a 16-byte memset,
+        nothing synchronised on."""
+        from .scene import SceneScores
+        dev = self.index.device
+        Q, width = self.shape
+        if k is None:
+            k = width
+        _require_int(k, "k must be an integer in [1, %d], the table's width" % width, 1, width)
+        if isinstance(voxel_scores, SceneScores):
+            _require(voxel_scores.device == dev, "voxel_scores must live on the cloud's device")
+            scores, entry = voxel_scores.scores, "conv3p_grid_interpolate_knn_i64"
+        else:
+            _require_tensor(voxel_scores, "voxel_scores must be a contiguous float32 (M, C) tensor on the cloud's device, or a "
+                            "SceneScores", torch.float32, dev=dev, ndim=2)
+            scores, entry = voxel_scores, "conv3p_grid_interpolate_knn_f32"
+        M, C = scores.shape
+        _require(1 <= C <= 128, "at most 128 classes (and at least one)")
+        _require(out is None or not return_scores or (isinstance(out, (tuple, list)) and len(out) == 2),
+                 "out must be (labels, scores) with return_scores")
+        lab = sc = None
+        if out is not None:
+            lab, sc = (out[0], out[1]) if return_scores else (out, None)
+            _require_tensor(lab, "out labels must be a contiguous int32 (Q,) tensor on the cloud's device", torch.int32, (Q,), dev)
+            _require(not return_scores or _is_tensor(sc, torch.float32, (Q, C), dev),
+                     "out scores must be a contiguous float32 (Q, C) tensor on the cloud's device")
+        _require(dev.type == "cuda", _NO_CPU)
+        if lab is None:
+            lab = torch.empty((Q,), dtype=torch.int32, device=dev)
+        if return_scores and sc is None:
+            sc = torch.empty((Q, C), dtype=torch.float32, device=dev)
+        if getattr(self, "interp_stats", None) is None:
+            self.interp_stats = torch.zeros((2,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _call(getattr(_lib.load(), entry), _ptr(self.index), _ptr(self.d2), _ptr(self.count), Q, width, k, _ptr(scores), M, C,
+                  _ptr(lab), _ptr(sc), self.interp_stats.data_ptr(), _stream(dev))
+        return (lab, sc) if return_scores else lab
+
+    def normals(self, viewpoint=None, min_neighbors=6, return_moments=False, out=None):
+        """GridSubsample.normals with the table's neighbours as the samples, in rank order, in place of the 27 cells around
+        the voxel -> GridNormals (include/conv3p_knn.h: conv3p_grid_normals_knn_f32, rule R2').  For a table of voxel
+        queries only (knn() without points); without exclude_self a voxel is its own first sample, as it is among the 27
+        cells.  min_neighbors in [3, 16]; viewpoint, return_moments and out as GridSubsample.normals has them.  One kernel
+        launch behind a 16-byte memset, nothing synchronised on."""
+        g = self.grid
+        _require(g is not None and self.voxel_queries, "normals need the table of voxel queries: knn() without points")
+        dev = g.data.device
+        M, K = g.data.shape
+        rooms = getattr(g, "voxel_room", None)
+        _require(self.shape[0] == M, "the table was made for another subsampling (%d voxels here)" % M)
+        _require_int(min_neighbors, "min_neighbors must be an integer in [3, 16]", 3, 16)
+        _require(isinstance(return_moments, bool), "return_moments must be a bool")
+        upload = _check_viewpoint(g, viewpoint, dev, rooms)
+        _require(_is_tensor(g.data, torch.float32) and K >= 3, "data must be a contiguous float32 (M, K >= 3) tensor")
+        if rooms is not None:
+            _require_tensor(rooms, "voxel_room must be a contiguous int32 (M,) tensor on the cloud's device", torch.int32, (M,), dev)
+        if out is not None:
+            _require(isinstance(out, GridNormals) and out.shape == (M, return_moments) and out.normals.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", _NO_CPU)
+        if out is None:
+            out = GridNormals(M, return_moments, dev)
+        if M == 0:
+            out.stats.zero_()
+            return out
+        if upload is not None:
+            viewpoint = _upload(torch.tensor([upload], dtype=torch.float32), dev)
+        with torch.cuda.device(dev):
+            _call(_lib.load().conv3p_grid_normals_knn_f32, g.data.data_ptr(), K, self.index.data_ptr(), self.count.data_ptr(),
+                  self.shape[1], g.stats.data_ptr(), _ptr(rooms), _ptr(viewpoint),
+                  viewpoint.shape[0] if viewpoint is not None else 0, M, min_neighbors, out.normals.data_ptr(),
+                  out.curvature.data_ptr(), out.samples.data_ptr(), out.flags.data_ptr(), _ptr(out.moments),
+                  out.stats.data_ptr(), _stream(dev))
+        return out
 
 
 class GridNormals:
