@@ -1,5 +1,5 @@
-"""ctypes binding of libconv3p_hip.so -- the C ABI declared in include/conv3p.h, include/conv3p_graph.h and
-include/conv3p_knn.h.
+"""ctypes binding of libconv3p_hip.so -- the C ABI declared in include/conv3p.h, include/conv3p_graph.h,
+include/conv3p_knn.h and include/conv3p_match.h.
 
 The product path has no CPU fallback: if the library is missing or a symbol is absent this
 module raises, loudly.
@@ -226,6 +226,14 @@ KNN_SYMBOLS = {
     "conv3p_grid_normals_knn_f32": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# every symbol include/conv3p_match.h declares, bound by load() next to the other three tables
+MATCH_SYMBOLS = {
+    "c3p_grid_match_scratch_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "c3p_grid_match_segments": (_i, [_vp] * 5 + [_i64, _i64, _i64, _i, _vp, _vp, _i, _i, _i, _i64] + [_vp] * 21 + [_vp, _sz, _vp]),
+}
+MATCH_MAX_UNITS = 1 << 24         # c3p_grid_match_segments' limits: M, N and T; classes
+MATCH_MAX_CLASS = 128
+
 _LIB = None
 
 
@@ -243,7 +251,8 @@ def load():
             "libconv3p_hip.so not found at %s -- run `python -m pointwise_amd.build` "
             "(there is no CPU fallback in the product path)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(GRAPH_SYMBOLS.items()) + list(KNN_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(GRAPH_SYMBOLS.items()) + list(KNN_SYMBOLS.items())
+                              + list(MATCH_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

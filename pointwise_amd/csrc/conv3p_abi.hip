@@ -1,5 +1,5 @@
 // conv3p_abi.hip -- host side of libconv3p_hip.so: the C ABI declared in include/conv3p.h, include/conv3p_graph.h and
-// include/conv3p_knn.h.
+// include/conv3p_knn.h; include/conv3p_match.h declares the segment matching.
 //
 // Replaces the host glue of the reference's GPU op (tf_conv3p_atrous.cu:541-642, :659-775):
 // no blocking D2H copies (stride / voxel arrive by value), no per-call temp allocation
@@ -18,10 +18,11 @@
 // One translation unit.  This file holds the single-layer calls (forward, backward, prepare, neighbour count, SELU) and
 // their exports; everything they are made of is in host-only headers, one concern each, included in dependency order:
 // conv3p_abi_{profile, layout, cache, search, routes, blocks}.hpp before the calls, conv3p_abi_stack.hpp (which composes
-// them) after, then the other subsystems (heads, pre-step, scene, grid, the k-nearest-voxel search).  DESIGN.md section 1 has the table.
+// them) after, then the other subsystems (heads, pre-step, scene, grid, the k-nearest-voxel search, the segment matching).  DESIGN.md section 1 has the table.
 #include "../../include/conv3p.h"
 #include "../../include/conv3p_graph.h"
 #include "../../include/conv3p_knn.h"
+#include "../../include/conv3p_match.h"
 #include "conv3p_host.hpp"
 #include "conv3p_kernels.hpp"
 #include "conv3p_stack_fused.hpp"
@@ -48,6 +49,7 @@
 #include "conv3p_grid_agglomerate.hpp"
 #include "conv3p_grid_smooth.hpp"
 #include "conv3p_grid_knn.hpp"
+#include "conv3p_grid_match.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -420,3 +422,4 @@ int conv3p_abi_version(void) { return CONV3P_ABI_VERSION; }
 #include "conv3p_abi_scene.hpp"
 #include "conv3p_abi_grid.hpp"
 #include "conv3p_abi_knn.hpp"
+#include "conv3p_abi_match.hpp"

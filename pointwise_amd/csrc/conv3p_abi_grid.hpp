@@ -355,22 +355,37 @@ void merge_launch(const MergeArgs &p, hipStream_t s)
     hipLaunchKernelGGL(merge_assign_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
     hipLaunchKernelGGL(merge_finish_kernel, dim3(per_thread), dim3(kGsegThreads), 0, s, p);
 }
-// The compaction, the 6 b launches of the radix passes and the finish of conv3p_grid_segment_adjacency, for it and for the
-// agglomeration: b the bytes of M - 1 >= S - 1, the passes a half of the key can need.
-void adj_order_launch(const AdjArgs &p, hipStream_t s)
+// The bytes of n - 1 (1 .. 4): the radix passes a half of a key below n can need.
+int adj_key_bytes(int64_t n)
 {
-    const unsigned per_slot = capped_grid(((size_t)p.slots + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
-    const unsigned per_tile = capped_grid((size_t)p.sort_tiles, kAdjMaxGrid);
-    const size_t rows = std::max((size_t)p.M + 1, (size_t)p.max_edges);
     int bytes = 1;
-    while (bytes < kAdjMaxBytes && ((uint64_t)(p.M - 1) >> (8 * bytes))) ++bytes;
-    hipLaunchKernelGGL(adj_compact_kernel, dim3(per_slot), dim3(kAdjThreads), 0, s, p);
-    for (int half = 0; half < 2; ++half)
+    while (bytes < kAdjMaxBytes && ((uint64_t)(n - 1) >> (8 * bytes))) ++bytes;
+    return bytes;
+}
+// The 3 launches of every radix pass over `bytes` bytes of the halves [half0, half1) of p's keys (0: the low words).
+void adj_passes_launch(const AdjArgs &p, int half0, int half1, int bytes, hipStream_t s)
+{
+    const unsigned per_tile = capped_grid((size_t)p.sort_tiles, kAdjMaxGrid);
+    for (int half = half0; half < half1; ++half)
         for (int j = 0; j < bytes; ++j) {                // a pass above the top byte of S - 1 returns at once
             hipLaunchKernelGGL(adj_sort_hist_kernel, dim3(per_tile), dim3(kAdjThreads), 0, s, p, half, j);
             hipLaunchKernelGGL(adj_sort_scan_kernel, dim3(kAdjDigits), dim3(kAdjScanThreads), 0, s, p, half, j);
             hipLaunchKernelGGL(adj_sort_scatter_kernel, dim3(per_tile), dim3(64), 0, s, p, half, j);
         }
+}
+// The compaction and the 6 b launches of the radix passes, b the bytes of M - 1 >= S - 1: the passes a half of the key can
+// need.  For the adjacency, the agglomeration and the segment matching.
+void adj_sort_launch(const AdjArgs &p, hipStream_t s)
+{
+    const unsigned per_slot = capped_grid(((size_t)p.slots + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid);
+    hipLaunchKernelGGL(adj_compact_kernel, dim3(per_slot), dim3(kAdjThreads), 0, s, p);
+    adj_passes_launch(p, 0, 2, adj_key_bytes(p.M), s);
+}
+// The sort and the finish of conv3p_grid_segment_adjacency, for it and for the agglomeration.
+void adj_order_launch(const AdjArgs &p, hipStream_t s)
+{
+    const size_t rows = std::max((size_t)p.M + 1, (size_t)p.max_edges);
+    adj_sort_launch(p, s);
     hipLaunchKernelGGL(adj_finish_kernel, dim3(capped_grid((rows + kAdjThreads - 1) / kAdjThreads, kAdjMaxGrid)),
                        dim3(kAdjThreads), 0, s, p);
 }

@@ -812,6 +812,83 @@ class GridSegments:
                   out.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
         return out
 
+    def match(self, truth, num_truth, weight="rows", pred_class=None, truth_class=None, num_class=None, iou=(1, 2),
+              max_pairs=None, out=None):
+        """This segmentation scored against ground-truth instances -> SegmentMatch: the exact overlap table between
+        segments and instances in CSR form and its transpose, the best partner of every segment and instance, the
+        one-to-one matching at the IoU threshold, and the integer counters behind panoptic quality, precision / recall and
+        coverage (include/conv3p_match.h: c3p_grid_match_segments, rules M1-M10; tests/grid_match_ref.py).
+
+        truth: a contiguous int32 tensor of instance ids in [0, num_truth), -1 for unannotated; one per raw row (N,) with
+        weight "rows" -- a row's segment is that of its voxel, grid.inverse -- or one per voxel (M,) with "voxels".  An id
+        outside [-1, num_truth) is void and counted in stats[5].  pred_class int32 (M,), a row per segment (seg.label,
+        pool.label, ...), truth_class int32 (num_truth,) and num_class (1 .. 128) go together: a segment and an instance
+        match only within a class, and an instance whose class is outside [0, num_class) is void (an ignored category).
+        With none of the three everything has class 0.  iou = (num, den): a pair matches when its IoU is ABOVE num / den,
+        compared exactly; 1 <= num < den <= 32768 and num / den >= 1/2, which makes the matching unique (M8).  max_pairs
+        is the number of rows of the pair arrays; None takes M.  If there are more pairs num_pairs() is -1, the sizes stay
+        exact, and a retry with max_pairs=m.pairs_bound() always fits.  out: a SegmentMatch of an earlier call with the
+        same M, num_truth, max_pairs and num_class.
+
+            m = patches.match(room_instances, T, pred_class=pool.label, truth_class=inst_class, num_class=13)
+            m.summary()["pq"]                            # the knobs of segments(), agglomerate() and pool(), compared
+
+        Works on the object segments(), merge() or agglomerate().segments returned, not on its trim(), and on the
+        many-clouds result as it stands: segment numbers are global and no segment crosses a room.  8 + 9 b launches, b the
+        bytes of max(M, num_truth) - 1 (fixed by the shapes, whatever the data), nothing synchronised on."""
+        _require(isinstance(weight, str) and weight in _GEOMETRY_WEIGHTS, "weight must be \"rows\" or \"voxels\"")
+        _require_int(num_truth, "num_truth must be an integer from 1 to 2^24", 1, _lib.MATCH_MAX_UNITS)
+        _require(self._source is not None,
+                 "match works on the object segments(), merge() or agglomerate() returned, not on its trim()")
+        grid = self._source[0]
+        dev = self.segment.device
+        M, N, T = self.shape[0], grid.inverse.numel(), num_truth
+        units = N if weight == "rows" else M
+        _require_tensor(truth, "truth must be a contiguous int32 (%d,) tensor on the segments' device: an instance id per %s"
+                        % (units, "raw row" if weight == "rows" else "voxel"), torch.int32, (units,), dev)
+        given = [x is not None for x in (pred_class, truth_class, num_class)]
+        _require(all(given) or not any(given), "pred_class, truth_class and num_class go together: all three or none")
+        if num_class is None:
+            num_class = 1
+        else:
+            _require_int(num_class, "num_class must be an integer from 1 to %d" % _lib.MATCH_MAX_CLASS, 1, _lib.MATCH_MAX_CLASS)
+            _require_tensor(pred_class, "pred_class must be a contiguous int32 (%d,) tensor on the segments' device: a row per "
+                            "segment" % M, torch.int32, (M,), dev)
+            _require_tensor(truth_class, "truth_class must be a contiguous int32 (%d,) tensor on the segments' device: a row per "
+                            "instance" % T, torch.int32, (T,), dev)
+        _require(isinstance(iou, (tuple, list)) and len(iou) == 2 and _is_int(iou[0], 1, 32767) and _is_int(iou[1], 2, 32768)
+                 and iou[0] < iou[1] and 2 * iou[0] >= iou[1],
+                 "iou must be (num, den) with 1 <= num < den <= 32768 and num / den at least 1/2")
+        if max_pairs is None:
+            max_pairs = M
+        _require_int(max_pairs, "max_pairs must be a non-negative integer below 2^31", 0, 2 ** 31 - 1)
+        _require(M <= _lib.MATCH_MAX_UNITS and N <= _lib.MATCH_MAX_UNITS, "match takes at most 2^24 voxels and 2^24 rows")
+        _require_table(dev, (("inverse", grid.inverse, (N,)), ("stats", grid.stats, (8,)), ("segment", self.segment, (M,)),
+                             ("stats", self.stats, (8,))))
+        if out is not None:
+            _require(isinstance(out, SegmentMatch) and out.shape == (M, T, max_pairs, num_class) and out.start.device == dev,
+                     "out was made for another shape")
+        _require(dev.type == "cuda", _NO_CPU)
+        if out is None:
+            out = SegmentMatch(M, T, max_pairs, num_class, dev)
+        out.iou = (iou[0], iou[1])
+        if M == 0 or N == 0:
+            _fill_empty(out)
+            return out
+        lib = _lib.load()
+        ws = _grow(out, "workspace", int(lib.c3p_grid_match_scratch_bytes(M, N, T, max_pairs)), dev)
+        with torch.cuda.device(dev):
+            _call(lib.c3p_grid_match_segments, self.segment.data_ptr(), self.stats.data_ptr(), _ptr(grid.inverse),
+                  grid.stats.data_ptr(), truth.data_ptr(), M, N, T, _GEOMETRY_WEIGHTS[weight], _ptr(pred_class),
+                  _ptr(truth_class), num_class, iou[0], iou[1], max_pairs, out.pred_size.data_ptr(), out.pred_void.data_ptr(),
+                  out.truth_size.data_ptr(), out.truth_missed.data_ptr(), _ptr(out.pair_pred), _ptr(out.pair_truth),
+                  _ptr(out.pair_inter), out.start.data_ptr(), out.t_start.data_ptr(), _ptr(out.t_pair),
+                  out.best_truth.data_ptr(), out.best_truth_inter.data_ptr(), out.best_truth_union.data_ptr(),
+                  out.best_pred.data_ptr(), out.best_pred_inter.data_ptr(), out.best_pred_union.data_ptr(),
+                  out.pred_match.data_ptr(), out.truth_match.data_ptr(), out.pred_iou_q30.data_ptr(),
+                  out.class_stats.data_ptr(), out.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+        return out
+
     def merge(self, pair_a, pair_b, select=None, out=None):
         """Segments joined along pairs -> a GridSegments: the pairs (pair_a[p], pair_b[p]) with select[p] != 0 (all of them
         with select=None) and both numbers in [0, S) are collapsed by union-find, transitively; the groups are numbered in
@@ -865,6 +942,101 @@ class GridSegments:
                   out.rows.data_ptr(), out.label.data_ptr(), out.stats.data_ptr(), out.merge_stats.data_ptr(), ws.data_ptr(),
                   ws.numel(), _stream(dev))
         return out
+
+
+def match_summary(class_stats, stats):
+    """SegmentMatch.summary()'s arithmetic on the integer counters: class_stats rows {TP, FP, FN, sum of iou_q30 over the
+    TP, instances, segments} and the 16 stats, as lists of Python ints -> a dict.  Per class, a list each, None where the
+    denominator is 0:
+
+        sq = (sum_iou / 2^30) / TP        rq = TP / (TP + FP / 2 + FN / 2)        pq = (sum_iou / 2^30) / (TP + FP / 2 + FN / 2)
+        precision = TP / (TP + FP)        recall = TP / (TP + FN)
+
+    and tp, fp, fn.  mean_pq, mean_sq, mean_rq, mean_precision, mean_recall: the means over the classes where the value
+    is defined (None with none).  mcov = stats[8] / 2^30 / stats[3], the mean over the instances of the IoU with their
+    best segment; mwcov = stats[9] / 2^30 / stats[10], the same weighted by the instances' sizes.  Plain float division
+    of exact integers (all below 2^53 at the sizes the call takes), so a perfect segmentation gives exactly 1.0."""
+    one = float(1 << 30)
+    div = lambda a, b: (a / b) if b else None
+    out = {k: [] for k in ("pq", "sq", "rq", "precision", "recall", "tp", "fp", "fn")}
+    for tp, fp, fn, siou, _inst, _segs in class_stats:
+        half = 2 * tp + fp + fn                          # twice the denominator of rq: an integer
+        out["tp"].append(tp)
+        out["fp"].append(fp)
+        out["fn"].append(fn)
+        out["sq"].append(div(siou / one, tp))
+        out["rq"].append(div(2 * tp, half))
+        out["pq"].append(div(2 * (siou / one), half))
+        out["precision"].append(div(tp, tp + fp))
+        out["recall"].append(div(tp, tp + fn))
+    for k in ("pq", "sq", "rq", "precision", "recall"):
+        have = [x for x in out[k] if x is not None]
+        out["mean_" + k] = div(sum(have), len(have))
+    out["mcov"] = div(stats[8] / one, stats[3])
+    out["mwcov"] = div(stats[9] / one, stats[10])
+    return out
+
+
+class SegmentMatch:
+    """The outputs of GridSegments.match (include/conv3p_match.h, rules M1-M10); a unit is a raw row or a voxel, as weight
+    said.  Per segment, int32 (M): pred_size, its units on annotated ground; pred_void, its units on void ground;
+    best_truth, best_truth_inter, best_truth_union, the instance with the largest IoU (the lowest number on a tie; -1, 0, 0
+    with none); pred_match, the instance it matches or -1; pred_iou_q30, floor(IoU * 2^30) of the match, 0 without.  Per
+    instance, int32 (T): truth_size, truth_missed (its units in no segment), best_pred, best_pred_inter, best_pred_union,
+    truth_match.  The table, a row per pair with at least one common unit in ascending (segment, instance), max_pairs
+    rows: pair_pred, pair_truth, pair_inter; start int32 (M + 1), the CSR over the segments; t_start int32 (T + 1) and
+    t_pair, the pair rows in ascending (instance, segment); rows past the last pair hold -1, -1, 0, -1.  class_stats int64
+    (num_class, 6) = {TP, FP, FN, sum of pred_iou_q30 over the TP, instances with a unit, segments of the class}.  stats
+    int64 (16) on the device = {pairs P, B = units in a segment on annotated ground, segments, instances with a unit, void
+    units, invalid truth ids, units of an instance in no segment, overflow, coverage sum, weighted coverage sum, sum of
+    truth_size, 0 ...}; on overflow (P > max_pairs) {-1, B, ..., 1, 0, 0, sum} with every pair row filler, start and t_start
+    all 0, every best / match output -1 / 0 and class_stats 0, the sizes still exact."""
+
+    _FILL = (("pred_size", 0), ("pred_void", 0), ("truth_size", 0), ("truth_missed", 0), ("pair_pred", -1), ("pair_truth", -1),
+             ("pair_inter", 0), ("start", 0), ("t_start", 0), ("t_pair", -1), ("best_truth", -1), ("best_truth_inter", 0),
+             ("best_truth_union", 0), ("best_pred", -1), ("best_pred_inter", 0), ("best_pred_union", 0), ("pred_match", -1),
+             ("truth_match", -1), ("pred_iou_q30", 0), ("class_stats", 0), ("stats", 0))
+    _PER_SEGMENT = ("pred_size", "pred_void", "best_truth", "best_truth_inter", "best_truth_union", "pred_match", "pred_iou_q30")
+    _PER_INSTANCE = ("truth_size", "truth_missed", "best_pred", "best_pred_inter", "best_pred_union", "truth_match")
+    _PER_PAIR = ("pair_pred", "pair_truth", "pair_inter", "t_pair")
+
+    def __init__(self, num_voxels, num_truth, max_pairs, num_class, device):
+        M, T, P, C = int(num_voxels), int(num_truth), int(max_pairs), int(num_class)
+        self.shape = (M, T, P, C)
+        for names, n in ((self._PER_SEGMENT, M), (self._PER_INSTANCE, T), (self._PER_PAIR, P)):
+            for name in names:
+                setattr(self, name, torch.empty((n,), dtype=torch.int32, device=device))
+        self.start = torch.empty((M + 1,), dtype=torch.int32, device=device)
+        self.t_start = torch.empty((T + 1,), dtype=torch.int32, device=device)
+        self.class_stats = torch.zeros((C, 6), dtype=torch.int64, device=device)
+        self.stats = torch.zeros((16,), dtype=torch.int64, device=device)
+        self.workspace = None
+        self.iou = None
+
+    def num_pairs(self):
+        """The number of pairs, -1 on overflow: the one host read (a synchronisation)."""
+        return int(self.stats[0])
+
+    def pairs_bound(self):
+        """B, the units that lie in a segment and on annotated ground: at least the number of pairs, whatever max_pairs
+        was, so a match(max_pairs=pairs_bound()) always fits.  A host read."""
+        return int(self.stats[1])
+
+    def overflowed(self):
+        """Whether the pairs did not fit max_pairs.  A host read."""
+        return int(self.stats[7]) != 0
+
+    def trim(self):
+        """Views of the first num_pairs() pair rows (none on overflow), as a SegmentMatch (everything else shared)."""
+        P = max(self.num_pairs(), 0)
+        return _view(self, SegmentMatch, slice(P), self._PER_PAIR,
+                     self._PER_SEGMENT + self._PER_INSTANCE + ("start", "t_start", "class_stats", "stats", "iou"),
+                     shape=self.shape[:2] + (P,) + self.shape[3:], workspace=None)
+
+    def summary(self):
+        """PQ, SQ, RQ, precision and recall per class and as means, and mCov / mWCov: match_summary on the counters.  A
+        host read of class_stats and stats."""
+        return match_summary(self.class_stats.cpu().tolist(), self.stats.cpu().tolist())
 
 
 class SegmentAdjacency:
